@@ -514,6 +514,28 @@ def device_digest(torch, d_results, n, chunk=1 << 24):
     return int(total.item()) & 0xFFFFFFFFFFFFFFFF
 
 
+DUMP_SAMPLE = 1 << 20  # records --dump-outputs keeps of a larger step: six float64 arrays of 8 MiB, 48 MiB in all
+
+
+def dump_outputs(torch, d_results, n, out_dir, sample=DUMP_SAMPLE, seed=0x5EED):
+    """--dump-outputs: the n hc_result_rec records the last timed step left in d_results — what a caller of hc_score_cands_device receives —
+    as float64 .npy files under out_dir: x1, x2, mm, n and cls (the class as the device wrote it), one entry per record.  Up to `sample`
+    records: all of them; more: a fixed, seeded sample of `sample` record positions in ascending order, saved as index.npy.  The workloads
+    are seeded too, so two builds given the same arguments can be compared file for file."""
+    if n > sample:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=sample, replace=False))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    w = d_results.view(torch.int64).view(-1, 3)[torch.from_numpy(idx).to(d_results.device)].cpu().numpy()
+    word = w[:, 2].view(np.uint64)  # mm | n_cls << 32
+    n_cls = word >> np.uint64(32)
+    arrays = {"index": idx, "x1": w[:, 0].view(np.float64), "x2": w[:, 1].view(np.float64), "mm": word & np.uint64(0xFFFFFFFF),
+              "n": n_cls & np.uint64(0x0FFFFFFF), "cls": n_cls >> np.uint64(28)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def parity_record(torch, sc, reads, settings, cand, d_out, n, digest_timed, digest_untimed, stretches=4, stretch=1 << 18):
     """What the last timed step left in d_out against (a) the digest of an untimed launch into another buffer and (b) the CPU oracle on
     `stretches` stretches of `stretch` records spread over the batch, bit for bit; and the step's admitted-edge count.  Raises on any
@@ -559,8 +581,9 @@ def parity_record(torch, sc, reads, settings, cand, d_out, n, digest_timed, dige
             "edges": edges, "ambiguous_band_records": n_amb}
 
 
-def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, world, with_gather, gather_mode="ring"):
-    """Timed steps + kernel timing of one workload on this rank; returns (record for the JSON line, reads, candidates, settings)."""
+def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, world, with_gather, gather_mode="ring", dump_dir=None):
+    """Timed steps + kernel timing of one workload on this rank; returns (record for the JSON line, reads, candidates, settings).
+    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs)."""
     import haploconduct_amd as hc
     from haploconduct_amd import parallel
     from haploconduct_amd.records import REC_COMPACT
@@ -697,6 +720,8 @@ def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, 
         t = torch.tensor([dt], device=coll, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump_dir and rank == 0:  # outside the timed region, before anything else launches into d_out
+        dump_outputs(torch, d_out, n, dump_dir)
     # parity, timed half: the digest of what the last timed step left, and stretches of it against the CPU oracle
     parity = parity_record(torch, sc, reads, settings, cand, d_out, n, device_digest(torch, d_out, n), digest_untimed)
     # kernel-only: hipEvents on the stream the kernel is launched on
@@ -979,6 +1004,9 @@ def main():
                     help="N > 1: CUs the scoring launches leave free for the exchange's kernels (0 = none, the exchange is not gated either; "
                          "-1 = decided by trying 0, 16 and 32 during set-up)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result records of the headline workload's last timed step (rank 0's) to DIR/<name>.npy as float64: "
+                         f"x1, x2, mm, n, cls and the record positions (index); above {DUMP_SAMPLE} records a fixed, seeded sample of them")
     ap.add_argument("--dump-rows", default=None, help="N > 1 (or HC_BENCH_FORCE_GATHER=1): rank 0 writes the rows collected in the last step to this .npy file")
     ap.add_argument("--no-stage", action="store_true", help="skip the stage end-to-end measurement")
     ap.add_argument("--stage-threads", type=int, default=0, help="--threads of the stage (0 = min(32, hardware threads))")
@@ -986,6 +1014,8 @@ def main():
                     help="candidate order inside the batch: sfo = sorted by (min id, max id) as scripts/sfo2overlaps.py:53 "
                          "writes overlap files (default); grouped = by read1; shuffled = random (experiment knobs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries exactly one line, the JSON record of rank 0.  Libraries underneath write there too (RCCL prints
     # its version banner through C stdio, flushed at exit): park fd 1 on stderr until the record is printed.
@@ -1031,7 +1061,8 @@ def main():
     from haploconduct_amd.parallel import GATHER_MODES
 
     modes = list(GATHER_MODES) if args.gather in ("both", "all") else [args.gather]
-    main_rec, reads, cand, settings = run_workload(args.workload, args.order, scaling, args, torch, dist, rank, local_rank, world, with_gather, modes[0])
+    main_rec, reads, cand, settings = run_workload(args.workload, args.order, scaling, args, torch, dist, rank, local_rank, world, with_gather, modes[0],
+                                                   dump_dir=args.dump_outputs)
     out = None
 
     def leg_record(rec, mode_name):

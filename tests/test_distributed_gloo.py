@@ -86,7 +86,7 @@ for mode in parallel.GATHER_MODES:  # "ring": one all-gather of the fixed-capaci
         overflow = True
     small.finish()
     np.save(os.path.join(os.environ["HC_OUT"], f"overflow_{tag}{rank}.npy"), np.array([overflow]))
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))  # the barrier, on the host: dist.barrier() looks for an accelerator and so opens the GPU where there is one
 # a row that does not fit the 24-byte form is refused, not truncated: 20 000 overlapped positions
 big = res.copy()
 big["n_cls"][np.nonzero(big["n_cls"] >> 28 != 0)[0][:1]] = 20000 | (2 << 28)

@@ -2,7 +2,9 @@
 other thresholds, singles instead of pairs, a file with odd lines) through ONE resident process — whose contexts, text blocks and page-locked
 buffers are taken over from call to call (hc_reset, keep_devices_resident) — must write, call for call, the bytes a process of its own writes."""
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -33,7 +35,9 @@ def test_a_pipeline_of_changing_stages_through_one_resident_process(tmp_path):
     from haploconduct_amd import synth
 
     d = str(tmp_path) + "/"
-    env = dict(os.environ, HC_RESIDENT_DIR=d + "res", HC_RESIDENT_IDLE_S="60")
+    # the socket's path must fit in sun_path (108 bytes): a short directory under /tmp, not tmp_path ($TMPDIR can be long)
+    sock_base = tempfile.mkdtemp(prefix="hcres-", dir="/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None)
+    env = dict(os.environ, HC_RESIDENT_DIR=os.path.join(sock_base, "res"), HC_RESIDENT_IDLE_S="60")
     cases = []
     r1, m1 = synth.make_paired_dataset(4000, 6000, flip_frac=0.25, seed=21)
     cases.append(_case(d, "a", r1, synth.paired_candidates(m1, n_candidates=100000, seed=22), ["--edge_threshold", "0.97", "--min_overlap_len", "150"]))
@@ -81,6 +85,7 @@ def test_a_pipeline_of_changing_stages_through_one_resident_process(tmp_path):
         assert ok.returncode == 0 and open(o + "edges.tsv", "rb").read() == open(f"{d}out_1_1_own/edges.tsv", "rb").read()
     finally:
         subprocess.run([EXE, "--resident_stop"], env=env, timeout=60)
+        shutil.rmtree(sock_base, ignore_errors=True)
 
 
 def test_stages_of_one_process_take_over_each_others_devices(tmp_path):

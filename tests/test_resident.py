@@ -3,7 +3,9 @@ child of the launcher, which links neither libhcedge nor the HIP runtime) and re
 that need no device — --help, the reference's argument checks (src/ViralQuasispecies.cpp:103-154), a missing FASTQ file — behave as in a
 process of their own.  The stage itself through the resident process: tests/test_gpu_resident.py."""
 import os
+import shutil
 import subprocess
+import tempfile
 import time
 
 import pytest
@@ -24,8 +26,18 @@ def _base_env(**kw):
 
 
 @pytest.fixture
-def resident_env(tmp_path):
-    env = _base_env(HC_RESIDENT_DIR=str(tmp_path / "res"), HC_RESIDENT_IDLE_S="30")
+def sock_base():
+    """Where the tests' resident processes keep their sockets.  A Unix socket's path must fit in sun_path (108 bytes) and the launcher
+    refuses a longer one; pytest's tmp_path lies under $TMPDIR, which can be long enough to break that.  A directory of its own under /tmp
+    (where the launcher's default lies) keeps the path short."""
+    d = tempfile.mkdtemp(prefix="hcres-", dir="/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
+def resident_env(sock_base):
+    env = _base_env(HC_RESIDENT_DIR=os.path.join(sock_base, "res"), HC_RESIDENT_IDLE_S="30")
     yield env
     subprocess.run([EXE, "--resident_stop"], env=env, timeout=30)
 
@@ -70,8 +82,8 @@ def test_one_resident_process_serves_many_calls_and_a_closed_pipe_does_not_end_i
     assert (tmp_path / "wd" / "viralquasispecies.log").exists(), "the log goes where the client stands (default --output is the working directory)"
 
 
-def test_stop_and_idle_time_out(tmp_path):
-    env = _base_env(HC_RESIDENT_DIR=str(tmp_path / "res2"), HC_RESIDENT_IDLE_S="1")
+def test_stop_and_idle_time_out(sock_base):
+    env = _base_env(HC_RESIDENT_DIR=os.path.join(sock_base, "res2"), HC_RESIDENT_IDLE_S="1")
     assert _run(["--resident", "--help"], env).returncode == 0
     sock = os.path.join(env["HC_RESIDENT_DIR"], "sock")
     assert os.path.exists(sock)
@@ -113,10 +125,10 @@ def test_a_rebuilt_library_retires_the_resident_process(resident_env, tmp_path):
 
 
 
-def test_many_clients_at_once_start_one_resident_process(tmp_path):
+def test_many_clients_at_once_start_one_resident_process(sock_base):
     """Eight clients started together on a socket nobody serves yet: every one is answered, one resident process remains (the others that
     were started by the race leave as soon as they see the socket served)."""
-    env = _base_env(HC_RESIDENT_DIR=str(tmp_path / "res4"), HC_RESIDENT_IDLE_S="30")
+    env = _base_env(HC_RESIDENT_DIR=os.path.join(sock_base, "res4"), HC_RESIDENT_IDLE_S="30")
     try:
         ps = [subprocess.Popen([EXE, "--resident", "--help"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE) for _ in range(8)]
         for p in ps:
@@ -194,10 +206,10 @@ def test_unenterable_directory_is_answered_with_code_1(resident_env, tmp_path):
     assert open(os.path.join(resident_env["HC_RESIDENT_DIR"], "pid")).read() == pid, "the resident process is still the same one"
 
 
-def test_device_visibility_is_part_of_the_resident_process_identity(tmp_path):
+def test_device_visibility_is_part_of_the_resident_process_identity(sock_base):
     """Round-5 advisor: two clients with different HIP_VISIBLE_DEVICES must not share one resident process (which devices a process sees is
     fixed when its runtime starts).  Each setting gets a sub-directory — socket, lock, pid — of its own."""
-    base = _base_env(HC_RESIDENT_DIR=str(tmp_path / "res5"), HC_RESIDENT_IDLE_S="30")
+    base = _base_env(HC_RESIDENT_DIR=os.path.join(sock_base, "res5"), HC_RESIDENT_IDLE_S="30")
     e0, e1 = dict(base, HIP_VISIBLE_DEVICES="0"), dict(base, HIP_VISIBLE_DEVICES="1")
     try:
         for env in (base, e0, e1, e0):
