@@ -107,6 +107,7 @@ static void apply_settings(hc_ctx* c, const hc_settings* settings) {
     c->params.rec_fmt = HC_REC_FULL;
     c->params.pad = 0;
     c->params.n_dev = nullptr;
+    c->params.order_off = nullptr;
 }
 
 static int create_ctx(hc_ctx* c, const hc_settings* settings) {
@@ -178,6 +179,7 @@ static void free_store(hc_ctx* c, bool scratch_too = true) {
     c->d_lut = nullptr;
     c->have_reads = false;
     c->store_bytes = 0;
+    c->loc_reads = 0;
 }
 
 int hc_destroy(hc_ctx* c) {
@@ -498,6 +500,20 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
         c->view.n_single = n_single;
         c->view.seq_syms = same_len ? (uint32_t)(2 * hc::slot_stride(seq_len[0], symbytes, slot_align)) : 0u;
     }
+    c->loc_reads = 0;
+    if (c->view.regular && n_reads > 1) {  // the locality order of the reads (hc_locality.hip); only regular stores take the locality launch
+        const size_t tmp = hc::locality_order_temp_bytes(n_reads);
+        const size_t keys_bytes = 2 * sizeof(uint64_t) * (size_t)n_reads, idx_bytes = sizeof(uint32_t) * (((size_t)n_reads + 3) & ~(size_t)3);
+        int rc = c->loc_tmp.ensure(keys_bytes + idx_bytes + tmp);
+        if (rc == HC_OK) rc = c->loc_order.ensure(sizeof(uint32_t) * (size_t)n_reads);
+        if (rc) return rc;
+        uint64_t* keys = c->loc_tmp.as<uint64_t>();
+        uint32_t* idx = (uint32_t*)(keys + 2 * (size_t)n_reads);
+        HC_HIP(hc::launch_locality_order(d_bases, d_raw_off, d_first, n_reads, keys, keys + n_reads, idx, c->loc_order.as<uint32_t>(),
+                                         (char*)idx + idx_bytes, tmp, c->stream));
+        HC_HIP(hipStreamSynchronize(c->stream));  // (the bases are freed on return)
+        c->loc_reads = n_reads;
+    }
     c->have_reads = true;
     {
         // How mixed the lengths are, by the 5th and 95th percentile (round 5; until then by the shortest and the longest sequence: ONE short
@@ -582,6 +598,18 @@ static int ensure_sort_workspace(hc_ctx* c, uint64_t n) {
 
 }  // extern "C"
 
+// The locality order (hc_locality.hip) from this many candidates on: its index passes cost a fixed ~0.09 ms (a binary search per read) plus
+// ~0.13 ms per 10^8 records (the permutation), and pay from somewhere between C2's 2 * 10^6 (0.153 -> 0.187 ms, slower) and C3-lite's
+// 2 * 10^7 (1.475 -> 1.387 ms); C3, 10^8: 6.56 -> 5.85 ms (profiles/r07_locality_order.md).  HC_LOCALITY=0 turns it off, HC_LOCALITY_MIN
+// moves the threshold (A/B and test knobs, read at every launch).
+static constexpr uint64_t kLocalityMinCandidates = 8000000;
+static bool locality_wanted(uint64_t n) {
+    const char* e = getenv("HC_LOCALITY");
+    if (e && atoi(e) == 0) return false;
+    const char* m = getenv("HC_LOCALITY_MIN");
+    return n >= (m ? strtoull(m, nullptr, 10) : kLocalityMinCandidates);
+}
+
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,
                  hc_gather_row* rows, unsigned long long* row_count, uint64_t cap, uint64_t base_index, const unsigned long long* n_dev,
                  const hc_line_rec* lines_in, hc_line_rec* lines_out, hc_bucket_ws* bucket) {
@@ -589,7 +617,11 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
     const bool want_perm = reorder && n > 1 && n < (1ull << 31);
     const bool want_bucket = c->view.balance && c->coop_fetch && n < (1ull << 32);
     const bool want_segments = rows && !lines_in && c->coop_fetch;
-    const bool ctx_scratch = want_perm || (want_bucket && !bucket) || want_segments;
+    // the locality order: compact records on a regular store, scored as a whole on the context's own entry points — not with a row sink (the
+    // multi-GPU gather wants its rows in ascending index order), not bucketed, not reordered, not a block on its own stream
+    const bool want_loc = !want_perm && !want_bucket && !rows && !lines_in && !bucket && fmt == HC_REC_COMPACT && c->coop_fetch && c->view.regular &&
+                          c->loc_reads == c->view.n_reads && c->loc_reads > 1 && n > 1 && n < (1ull << 32) && locality_wanted(n);
+    const bool ctx_scratch = want_perm || (want_bucket && !bucket) || want_segments || want_loc;
     if (ctx_scratch) {
         // one launch at a time on that scratch: a launch on another stream than the last one waits for it on the device
         if (!c->scratch_done) HC_HIP(hipEventCreateWithFlags(&c->scratch_done, hipEventDisableTiming));
@@ -607,10 +639,28 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
                                   c->sort_tmp_bytes, s));
         perm = perm_out;
     }
+    const uint32_t* order_off = nullptr;
+    if (want_loc) {  // flag, run boundaries (R + 2), run starts (R + 1), then the launch's permutation (n)
+        const uint32_t R = c->loc_reads;
+        const size_t head = ((size_t)R + 2 + (size_t)R + 1 + 1 + 3) & ~(size_t)3;
+        const size_t tmp = hc::locality_index_temp_bytes(R);
+        if ((head + n) * sizeof(uint32_t) > c->loc_ws.cap && c->scratch_used) HC_HIP(hipEventSynchronize(c->scratch_done));  // (as sink_rows)
+        int rc = c->loc_ws.ensure((head + n) * sizeof(uint32_t));
+        if (rc == HC_OK) rc = c->loc_tmp.ensure(tmp ? tmp : 16);
+        if (rc) return rc;
+        uint32_t* flag = c->loc_ws.as<uint32_t>();
+        uint32_t* bounds = flag + 1;
+        uint32_t* starts = bounds + R + 2;
+        uint32_t* lperm = c->loc_ws.as<uint32_t>() + head;
+        HC_HIP(hc::launch_locality_index(c->loc_order.as<uint32_t>(), R, d_in, n, n_dev, bounds, starts, flag, lperm, c->loc_tmp.p, tmp, s));
+        perm = lperm;
+        order_off = flag;
+    }
     hc::ScoreParams prm = c->params;
     prm.rec_fmt = fmt;
     prm.pad = 0;
     prm.n_dev = n_dev;
+    prm.order_off = order_off;
     uint32_t *bperm = nullptr, *bqueue = nullptr;
     if (want_bucket) {  // mixed sequence lengths: the launch buckets its candidates by length first
         hc_bucket_ws* ws = bucket ? bucket : &c->bucket;
@@ -665,6 +715,17 @@ extern "C" {
 int hc_set_reorder(hc_ctx* c, int mode) {
     if (!c || mode < HC_REORDER_NEVER || mode > HC_REORDER_AUTO) return fail(HC_ERR_ARG, "hc_set_reorder: bad argument");
     c->reorder_mode = mode;
+    return HC_OK;
+}
+
+int hc_get_locality_order(hc_ctx* c, uint32_t* out, uint64_t cap, uint64_t* n) {
+    if (!c || !n || (cap && !out)) return fail(HC_ERR_ARG, "hc_get_locality_order: bad argument");
+    *n = c->have_reads ? c->loc_reads : 0;
+    const uint64_t k = std::min<uint64_t>(cap, *n);
+    if (k) {
+        HC_HIP(hipSetDevice(c->device));
+        HC_HIP(hipMemcpy(out, c->loc_order.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
     return HC_OK;
 }
 

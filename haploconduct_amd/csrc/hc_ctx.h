@@ -58,6 +58,14 @@ hipError_t launch_comm_gate(const unsigned long long* started, unsigned long lon
 hipError_t launch_flush_rows(const void* src, void* dst_mapped, const unsigned long long* count, uint64_t cap, uint32_t row_bytes, uint32_t n_cu,
                              hipStream_t stream);
 
+// hc_locality.hip: the reads' locality order (hc_set_reads) and a launch's walk of its runs in that order (hc_ctx_score)
+size_t locality_order_temp_bytes(uint32_t n_reads);
+hipError_t launch_locality_order(const uint8_t* bases, const uint64_t* raw_off, const uint32_t* read_first_seq, uint32_t n_reads, uint64_t* keys_a,
+                                 uint64_t* keys_b, uint32_t* idx, uint32_t* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
+size_t locality_index_temp_bytes(uint32_t n_reads);
+hipError_t launch_locality_index(const uint32_t* order, uint32_t n_reads, const void* in, uint64_t n, const unsigned long long* n_dev, uint32_t* bounds,
+                                 uint32_t* start, uint32_t* flag, uint32_t* perm, void* temp, size_t temp_bytes, hipStream_t stream);
+
 int set_last_error(int status, const std::string& what);  // thread-local text behind hc_last_error()
 }  // namespace hc
 
@@ -158,6 +166,10 @@ struct hc_ctx {
     size_t sort_tmp_bytes = 0;
     uint64_t sort_cap = 0;
     hc_bucket_ws bucket;  // length-bucketed launches on the context's own entry points
+    // locality order (hc_locality.hip): the reads sorted by the minimiser of mate /1, built by hc_set_reads for a regular store and kept with
+    // it; the per-launch scratch (flag, run boundaries and starts, the launch's permutation) is grow-only and shares `scratch_done`
+    hc_scratch loc_order, loc_ws, loc_tmp;
+    uint32_t loc_reads = 0;  // reads loc_order holds (0: no order for this read set)
     hc_scratch sink_rows, sink_counts;  // hc_score_pack_device: the row sink's per-workgroup segments (hc_kernels.hip: RowSink)
     uint32_t sink_turn = 0;             // which of the two spill counters the next segmented launch uses
     bool sink_dirty = false;            // a segmented launch failed at enqueue: the spill counters are re-zeroed before the next one

@@ -161,6 +161,9 @@ struct ScoreParams {
     uint32_t rec_fmt;  // HC_REC_FULL / HC_REC_COMPACT: layout of the candidate records of this launch
     uint32_t pad;      // bits 8..11: 64-candidate steps per item of the wave queue (hc_kernels.hip: WQ), set by launch_score
     const unsigned long long* n_dev;  // nullptr, or where the device holds the number of records (<= the launch's n)
+    // nullptr, or the locality order's flag (hc_locality.hip): `perm` is the locality order of the launch and the ticket form deals its
+    // items by XCD while *order_off == 0; otherwise (the batch is not grouped by its smaller read id) perm is ignored
+    const uint32_t* order_off;
 };
 
 }  // namespace hc

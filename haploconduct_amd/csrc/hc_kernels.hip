@@ -1333,7 +1333,27 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
     const uint32_t dq_pieces = (DYN && WQ && blockIdx.x < n_pieces) ? (n_pieces - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;
     const uint32_t wq_items = !WQ ? 0u : (DYN ? dq_pieces * (uint32_t)(WG / 64) : (uint32_t)((n + 64ull * wq_steps - 1) / (64ull * wq_steps)));
     const uint32_t wq_per = !WQ ? 0u : (DYN ? wq_items : (wq_items + gridDim.x - 1) / gridDim.x);  // items of this workgroup: [wq_first, wq_end)
-    const uint32_t wq_first = DYN ? 0u : blockIdx.x * wq_per, wq_end = wq_first + wq_per < wq_items ? wq_first + wq_per : wq_items;
+    uint32_t wq_first = DYN ? 0u : blockIdx.x * wq_per, wq_end = wq_first + wq_per < wq_items ? wq_first + wq_per : wq_items;
+    // The locality order (hc_locality.hip, prm.order_off): neighbouring items share their reads' rows, and the workgroups that share an L2 —
+    // blockIdx % 8, dealt round-robin over the XCDs — take the items of one eighth of the order between them, interleaved: the group's m
+    // workgroups own the items [g_start, g_end) and workgroup l of the group takes g_start + l, g_start + l + m, ... in ticket order, so
+    // the group's 512 waves sweep one front of neighbouring items.  Where a workgroup actually runs changes the speed only: every item is
+    // still taken exactly once.  A batch that is not grouped (*order_off != 0) is scored as given, on the contiguous dealing.
+    uint32_t xq_base = 0, xq_stride = 0;  // xq_stride != 0: the item of ticket index t is xq_base + xq_stride * t
+    if (WQ && !DYN && prm.order_off) {  // kernel-argument-uniform
+        if (*prm.order_off) {
+            perm = nullptr;
+        } else if (wq_items) {
+            const uint32_t G = gridDim.x, g = blockIdx.x & 7u, l = blockIdx.x >> 3, q = G >> 3, r = G & 7u;
+            const uint32_t m = q + (g < r ? 1u : 0u);
+            const uint32_t g_start = (g * q + (g < r ? g : r)) * wq_per;
+            const uint32_t g_end = g_start + m * wq_per < wq_items ? g_start + m * wq_per : wq_items;
+            wq_first = 0;
+            wq_end = g_end > g_start + l ? (g_end - g_start - l + m - 1) / m : 0u;
+            xq_base = g_start + l;
+            xq_stride = m;
+        }
+    }
     uint32_t wq_item = 0, wq_next_raw = 0, wq_k = 0;
     auto wq_pull = [&]() -> uint32_t {  // issued by lane 0 (the other lanes hold 0); the answer is taken when the item is entered
         uint32_t t = 0;
@@ -1359,7 +1379,8 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
                 const uint32_t piece = q / n_tiles, tile = q - piece * n_tiles;
                 slot = (uint64_t)tile * kBucketTile + piece * WG + w * 64u + (tid & 63u);
             } else {
-                slot = ((uint64_t)wq_item * wq_steps + wq_k) * 64u + (tid & 63u);
+                const uint32_t item = xq_stride ? xq_base + xq_stride * wq_item : wq_item;
+                slot = ((uint64_t)item * wq_steps + wq_k) * 64u + (tid & 63u);
             }
             ++wq_k;
         } else if (DYN) {

@@ -62,6 +62,14 @@ class EdgeScorer:
         N.check(N.lib.hc_get_kernel_info_for(self._ctx, int(n), buf, 768), "hc_get_kernel_info_for")
         return buf.value.decode()
 
+    def locality_order(self):
+        """hc_get_locality_order: the reads in the order a launch scores their runs in (an empty array: no order for this read set)."""
+        n = C.c_uint64()
+        N.check(N.lib.hc_get_locality_order(self._ctx, None, 0, C.byref(n)), "hc_get_locality_order")
+        out = np.empty(n.value, np.uint32)
+        N.check(N.lib.hc_get_locality_order(self._ctx, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), "hc_get_locality_order")
+        return out
+
     def set_reorder(self, mode):
         """0 never, 1 always, 2 auto (hc_set_reorder)."""
         N.check(N.lib.hc_set_reorder(self._ctx, int(mode)), "hc_set_reorder")

@@ -360,6 +360,9 @@ int hc_get_kernel_info(hc_ctx* ctx, char* buf, uint32_t cap);
 /* The same for a launch of n candidates: the library picks the kernel's form by the launch's size too (register-staged rows for
  * small launches, LDS-DMA rows from 5 * 10^5 candidates on, the waves' work queue where every wave gets 64 steps and more). */
 int hc_get_kernel_info_for(hc_ctx* ctx, uint64_t n, char* buf, uint32_t cap);
+/* The reads in locality order (the smallest hashed 16-mer of mate /1, stable), which launches of a regular store score their runs of equal
+ * smaller read id in: copies min(cap, n) read indices to out, *n = how many the read set has (0: no order, the store is not regular). */
+int hc_get_locality_order(hc_ctx* ctx, uint32_t* out, uint64_t cap, uint64_t* n);
 
 /* ---- device primitives (csrc/hc_prims.hip), behind host-buffer entry points for their unit tests ------------------
  * The stage's device side sorts and compacts with its own kernels: a stable LSD radix sort (8 bits a pass; keys of 4 bytes
