@@ -9,8 +9,7 @@
 //   hc-edgecalc --resident_daemon <socket>  the resident process itself (hc_cli_daemon); not for users
 // Socket: $HC_RESIDENT_DIR, else $XDG_RUNTIME_DIR/hc-edgecalc, else /tmp/hc-edgecalc-<uid>; idle time-out HC_RESIDENT_IDLE_S (600).
 // Clients whose HIP_ / ROCR_ / CUDA_VISIBLE_DEVICES or GPU_DEVICE_ORDINAL differ get resident processes of their own (a sub-directory
-// per setting).  A job sees its client's HC_* variables, with one exception: the experiment-only launch knobs (HC_COOP_DMA, HC_WAVE_QUEUE,
-// HC_GRID_MULT, HC_COOP_DEPTH, HC_COOP_WG_PER_CU) are read once per process and stay what the first job saw.
+// per setting).  A job sees its client's HC_* variables.
 // Argv contract: /root/reference/scripts/pipeline_per_stage.py:223-247,272-298 — `--resident` is the one extra word.
 #include <dlfcn.h>
 #include <errno.h>

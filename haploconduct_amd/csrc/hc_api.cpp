@@ -613,15 +613,19 @@ static bool locality_wanted(uint64_t n) {
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,
                  hc_gather_row* rows, unsigned long long* row_count, uint64_t cap, uint64_t base_index, const unsigned long long* n_dev,
                  const hc_line_rec* lines_in, hc_line_rec* lines_out, hc_bucket_ws* bucket) {
+    // the multi-GPU step: CUs left to the collective library (hc_set_comm_reserve)
+    const uint32_t cus = c->comm_reserve && c->comm_reserve < c->n_cu ? c->n_cu - c->comm_reserve : c->n_cu;
+    const hc::RowSinkKind sink = !rows ? hc::RowSinkKind::none
+                                       : (!lines_in && cap < 0xFFFFFFFFull ? hc::RowSinkKind::segmented : hc::RowSinkKind::unsegmented);
+    const hc::ScorePlan plan = hc::plan_score_launch(c->view, c->coop_fetch, c->fetch_group, cus, n, sink);
+    const bool coop = plan.kernel && plan.kernel->coop;
     // Which of the context's own scratch this launch will use (blocks bring their own and take none of it)
     const bool want_perm = reorder && n > 1 && n < (1ull << 31);
-    const bool want_bucket = c->view.balance && c->coop_fetch && n < (1ull << 32);
-    const bool want_segments = rows && !lines_in && c->coop_fetch;
     // the locality order: compact records on a regular store, scored as a whole on the context's own entry points — not with a row sink (the
     // multi-GPU gather wants its rows in ascending index order), not bucketed, not reordered, not a block on its own stream
-    const bool want_loc = !want_perm && !want_bucket && !rows && !lines_in && !bucket && fmt == HC_REC_COMPACT && c->coop_fetch && c->view.regular &&
+    const bool want_loc = !want_perm && !plan.bucketed && !rows && !lines_in && !bucket && fmt == HC_REC_COMPACT && coop && c->view.regular &&
                           c->loc_reads == c->view.n_reads && c->loc_reads > 1 && n > 1 && n < (1ull << 32) && locality_wanted(n);
-    const bool ctx_scratch = want_perm || (want_bucket && !bucket) || want_segments || want_loc;
+    const bool ctx_scratch = want_perm || (plan.bucketed && !bucket) || plan.segmented || want_loc;
     if (ctx_scratch) {
         // one launch at a time on that scratch: a launch on another stream than the last one waits for it on the device
         if (!c->scratch_done) HC_HIP(hipEventCreateWithFlags(&c->scratch_done, hipEventDisableTiming));
@@ -661,47 +665,41 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
     prm.pad = 0;
     prm.n_dev = n_dev;
     prm.order_off = order_off;
-    uint32_t *bperm = nullptr, *bqueue = nullptr;
-    if (want_bucket) {  // mixed sequence lengths: the launch buckets its candidates by length first
+    hc::ScoreBuffers buf{rows, row_count, cap, base_index, lines_in, lines_out};
+    buf.started = (rows && !lines_in) ? c->d_started : nullptr;  // workgroup starts counted for hc_comm_gate_device
+    if (plan.bucketed) {  // mixed sequence lengths: the launch buckets its candidates by length first
         hc_bucket_ws* ws = bucket ? bucket : &c->bucket;
         int rc = ws->ensure(n);
         if (rc) return rc;
-        bperm = ws->perm();
-        bqueue = ws->queue();
+        buf.bucket_perm = ws->perm();
+        buf.bucket_queue = ws->queue();
     }
-    hc_gather_row* seg_buf = nullptr;
-    uint32_t* seg_count = nullptr;
-    uint64_t seg_total = 0;
-    if (want_segments) {  // the cooperative launches collect their rows in per-workgroup segments, spilling into `cap` rows behind them
-        seg_total = 2 * cap + hc::kSinkMaxGroups * 512;  // the expected share per workgroup and room for the small ones, then the spill area
+    if (plan.segmented) {  // the cooperative launches collect their rows in per-workgroup segments, spilling into `cap` rows behind them
+        buf.seg_total_rows = 2 * cap + hc::kSinkMaxGroups * 512;  // the expected share per workgroup and room for the small ones, then the spill area
         // (a grown buffer is a new one: the launches in flight on the old one are behind scratch_done, which this stream has waited for
         // or is itself ordered behind — but the runtime frees at once, so wait for them on the host before letting go of it)
-        if (seg_total * sizeof(hc_gather_row) > c->sink_rows.cap && c->scratch_used) HC_HIP(hipEventSynchronize(c->scratch_done));
-        int rc = c->sink_rows.ensure(seg_total * sizeof(hc_gather_row));
+        if (buf.seg_total_rows * sizeof(hc_gather_row) > c->sink_rows.cap && c->scratch_used) HC_HIP(hipEventSynchronize(c->scratch_done));
+        int rc = c->sink_rows.ensure(buf.seg_total_rows * sizeof(hc_gather_row));
         if (rc) return rc;
         if (!c->sink_counts.p) {
             if ((rc = c->sink_counts.ensure((hc::kSinkMaxGroups + 2) * sizeof(uint32_t))) != HC_OK) return rc;
             HC_HIP(hipMemsetAsync(c->sink_counts.p, 0, (hc::kSinkMaxGroups + 2) * sizeof(uint32_t), s));  // the spill counters start at zero
         }
-        seg_buf = c->sink_rows.as<hc_gather_row>();
-        seg_count = c->sink_counts.as<uint32_t>();
+        if (c->sink_dirty) {  // a segmented launch failed at enqueue: whatever it left in the spill counters goes
+            HC_HIP(hipMemsetAsync(c->sink_counts.as<uint32_t>() + hc::kSinkMaxGroups, 0, 2 * sizeof(uint32_t), s));
+            c->sink_dirty = false;
+        }
+        buf.seg_buf = c->sink_rows.as<hc_gather_row>();
+        buf.seg_count = c->sink_counts.as<uint32_t>();
+        buf.spill_turn = &c->sink_turn;
     }
-    if (want_segments && c->sink_dirty) {  // a segmented launch failed at enqueue: whatever it left in the spill counters goes
-        HC_HIP(hipMemsetAsync(c->sink_counts.as<uint32_t>() + hc::kSinkMaxGroups, 0, 2 * sizeof(uint32_t), s));
-        c->sink_dirty = false;
-    }
-    // the multi-GPU step: CUs left to the collective library (hc_set_comm_reserve), workgroup starts counted for hc_comm_gate_device
-    const uint32_t cus = c->comm_reserve && c->comm_reserve < c->n_cu ? c->n_cu - c->comm_reserve : c->n_cu;
-    unsigned long long* started = (rows && !lines_in) ? c->d_started : nullptr;
     uint32_t started_groups = 0;
-    const hipError_t le = hc::launch_score(c->view, prm, c->d_lut, d_in, n, (hc_result_rec*)d_out, perm, cus, c->coop_fetch ? 0 : c->fetch_group, c->fetch_group, rows,
-                                           row_count, cap, base_index, s, lines_in, lines_out, bperm, bqueue, seg_buf, seg_count, seg_total, &c->sink_turn, started,
-                                           &started_groups);
+    const hipError_t le = hc::launch_score(plan, c->view, prm, c->d_lut, d_in, n, (hc_result_rec*)d_out, perm, buf, s, &started_groups);
     if (le != hipSuccess) {
-        if (want_segments) c->sink_dirty = true;
+        if (plan.segmented) c->sink_dirty = true;
         return hc::set_last_error(HC_ERR_HIP, std::string("launch_score: ") + hipGetErrorString(le));
     }
-    if (started) c->started_target += started_groups;
+    if (buf.started) c->started_target += started_groups;
     if (ctx_scratch) {
         HC_HIP(hipEventRecord(c->scratch_done, s));
         c->scratch_stream = s;
@@ -1082,7 +1080,7 @@ int hc_get_kernel_info_for(hc_ctx* c, uint64_t n, char* buf, uint32_t cap) {
     if (!c || !buf || cap == 0) return fail(HC_ERR_ARG, "hc_get_kernel_info: null argument");
     buf[0] = 0;
     if (!c->have_reads) return fail(HC_ERR_STATE, "hc_get_kernel_info: hc_set_reads has not been called");
-    const std::string d = hc::describe_score_kernel(c->view, c->coop_fetch ? 0 : c->fetch_group, c->fetch_group, c->n_cu, n);
+    const std::string d = hc::describe_score_kernel(c->view, c->coop_fetch, c->fetch_group, c->n_cu, n);
     snprintf(buf, cap, "%s", d.c_str());
     return HC_OK;
 }

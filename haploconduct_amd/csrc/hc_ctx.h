@@ -17,21 +17,58 @@ hipError_t launch_encode(uint32_t symbytes, const uint8_t* bases, const uint8_t*
                          const uint64_t* seq_off, const uint32_t* rc_delta, const uint8_t* qmap, uint32_t n_seq, uint32_t K, void* sym,
                          uint8_t* seq_bad, const uint32_t* read_first_seq, uint32_t n_reads, ReadDesc* descs, uint32_t slot_align,
                          hipStream_t stream);
-hipError_t launch_score(const StoreView& st, const ScoreParams& prm, const double* lut_g, const void* in, uint64_t n,
-                        hc_result_rec* out, const uint32_t* perm, uint32_t n_cu, int fetch_group, int lane_fetch_group, hc_gather_row* rows,
-                        unsigned long long* row_count, uint64_t cap, uint64_t base_index, hipStream_t stream,
-                        const hc_line_rec* lines_in = nullptr, hc_line_rec* lines_out = nullptr, uint32_t* bucket_perm = nullptr,
-                        uint32_t* bucket_queue = nullptr, hc_gather_row* seg_buf = nullptr, uint32_t* seg_count = nullptr, uint64_t seg_total_rows = 0,
-                        uint32_t* spill_turn = nullptr, unsigned long long* started = nullptr, uint32_t* started_groups = nullptr);
-// started / started_groups: hc_comm_gate_device — the cooperative launch's workgroups add one each to *started as they start;
-// *started_groups = how many will (0: the launch took a kernel that does not count)
-// seg_buf (seg_total_rows rows: segments, then `cap` rows of spill area) / seg_count (kSinkMaxGroups counters + 2 spill counters, all
-// zero before the first launch) / spill_turn (host: which spill counter the next launch uses; advanced by a launch that used segments):
-// scratch of a launch that collects its rows in per-workgroup segments
-// bucket_perm (n uint32) / bucket_queue (one uint32): scratch of the length-bucketed launch (read sets of mixed sequence
-// length, StoreView::balance): without them such a set is scored in the order given
+// The scoring launch: plan_score_launch decides all of it (no HIP call in it), launch_score carries the plan out.
+// One row of the table of compiled scoring kernels (hc_kernels.hip); the first eight fields are the key.
+struct ScoreKernel {
+    bool coop;                  // score_kernel_coop; otherwise score_kernel (256 lanes) or score_kernel_wide_wg (512)
+    uint32_t symbytes, lg, wg;  // lg: the template's LG (5 for 16-bit symbols)
+    uint32_t group;             // per lane: G, 16-symbol chunks per fetch group
+    bool bal;                   // per lane: BAL; cooperative: DYN (the length-bucketed launch)
+    uint32_t depth;             // cooperative: DEPTH (0: the LDS-DMA form)
+    bool wq;                    // cooperative: WQ (the waves take their items by ticket)
+    const void* fn;
+    const char* name;           // as hc_get_kernel_info reports it
+};
+// segmented: rows that may collect in per-workgroup segments (hc_score_pack_device); unsegmented: rows appended straight to the payload
+// (a text block's lines travel with them, or a payload of 2^32 rows and more)
+enum class RowSinkKind { none, segmented, unsegmented };
+struct ScorePlan {
+    const ScoreKernel* kernel = nullptr;  // nullptr: the table has no kernel for the plan (a bug)
+    const ScoreKernel* staged = nullptr;  // cooperative: the register-staged form, which launches below the LDS-DMA threshold take
+    uint32_t blocks = 0;
+    size_t lds = 0;           // dynamic LDS per workgroup; more than lds_form when it keeps further workgroups off the CU
+    size_t lds_form = 0;
+    uint32_t waves_per_cu = 0;
+    bool bucketed = false;    // bucket_perm_kernel runs first (scratch: ScoreBuffers::bucket_perm / bucket_queue)
+    bool segmented = false;   // the rows collect in per-workgroup segments (scratch: ScoreBuffers::seg_* / spill_turn)
+};
+// coop_fetch: the cooperative fetch where the store and the table allow it; lane_group: the per-lane kernel's fetch groups otherwise (4 =
+// 64-symbol groups for short reads, 2 = 32-symbol groups for contig-length sequences), chosen per read set by hc_set_reads.
+ScorePlan plan_score_launch(const StoreView& st, bool coop_fetch, int lane_group, uint32_t n_cu, uint64_t n, RowSinkKind sink);
+struct ScoreBuffers {
+    // rows == nullptr: plain scoring; otherwise every non-dropped record is also appended to rows (hc_kernels.hip: RowSink)
+    hc_gather_row* rows = nullptr;
+    unsigned long long* row_count = nullptr;
+    uint64_t cap = 0, base_index = 0;
+    const hc_line_rec* lines_in = nullptr;
+    hc_line_rec* lines_out = nullptr;
+    // bucket_perm (n uint32) / bucket_queue (one uint32): scratch of the length-bucketed launch
+    uint32_t* bucket_perm = nullptr;
+    uint32_t* bucket_queue = nullptr;
+    // seg_buf (seg_total_rows rows: segments, then `cap` rows of spill area) / seg_count (kSinkMaxGroups counters + 2 spill counters, all
+    // zero before the first launch) / spill_turn (host: which spill counter the next launch uses; advanced by a launch that used segments)
+    hc_gather_row* seg_buf = nullptr;
+    uint32_t* seg_count = nullptr;
+    uint64_t seg_total_rows = 0;
+    uint32_t* spill_turn = nullptr;
+    // hc_comm_gate_device: the cooperative launch's workgroups add one each to *started as they start
+    unsigned long long* started = nullptr;
+};
+// *started_groups = how many workgroups add to ScoreBuffers::started (0: the launch took a kernel that does not count)
+hipError_t launch_score(const ScorePlan& plan, const StoreView& st, ScoreParams prm, const double* lut_g, const void* in, uint64_t n,
+                        hc_result_rec* out, const uint32_t* perm, const ScoreBuffers& buf, hipStream_t stream, uint32_t* started_groups);
 hipError_t set_score_kernel_lds_limit();
-std::string describe_score_kernel(const StoreView& st, int fetch_group, int lane_fetch_group, uint32_t n_cu = 256, uint64_t n = 0);  // n: the form a launch of n candidates takes (0: in general)
+std::string describe_score_kernel(const StoreView& st, bool coop_fetch, int lane_group, uint32_t n_cu, uint64_t n);  // n == 0: the forms in general
 // hc_util_kernels.hip
 size_t compact_temp_bytes(uint32_t n);
 hipError_t launch_compact(const hc_result_rec* res, uint32_t n, uint32_t* idx_out, unsigned long long* count_out, void* temp,

@@ -27,21 +27,13 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
 #include <cstdio>
 #include <string>
 
 #include "../../include/hcedge.h"
 #include "hc_device.h"
 #include "hc_resolve.h"
-
-// cache policy bits of the cooperative fetch's row loads (experiment: 2 = non-temporal)
-#ifndef HC_COOP_AUX_A
-#define HC_COOP_AUX_A 0
-#endif
-#ifndef HC_COOP_AUX_B
-#define HC_COOP_AUX_B 0
-#endif
+#include "hc_ctx.h"
 
 // Experiment builds only (tools/experiments/ablate.sh): HC_ABLATE is a bit mask of parts of the cooperative kernel that are
 // cut out to see what the others cost — results are garbage.  1: no table reads (the LDS look-up of every position becomes a
@@ -519,10 +511,10 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
                 // first out-of-range offset — no per-lane add per load; the range check takes the scalar offset into account)
 #if !(HC_ABLATE & 8)  // (ablation 8: no A rows are fetched — the image keeps what it held)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(stage + 1024u * j), 16,
-                                                         on ? la[j] : oob, at, 0, HC_COOP_AUX_A);
+                                                         on ? la[j] : oob, at, 0, 0);
 #endif
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(stage + 4096u + 1024u * j), 16,
-                                                         on ? lb[j] : oob, at, 0, HC_COOP_AUX_B);
+                                                         on ? lb[j] : oob, at, 0, 0);
             }
         };
 #if HC_ABLATE & 16
@@ -535,7 +527,7 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
                 for (int j = 0; j < 4; ++j) {
                     const bool on = at < lim[j];
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(stage + 4096u * half + 1024u * j), 16,
-                                                             on ? lb[j] : oob, at, 0, HC_COOP_AUX_B);
+                                                             on ? lb[j] : oob, at, 0, 0);
                 }
             };
             fetch_b(0, 0);
@@ -651,8 +643,8 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
             sA[j] = u32x4{0x01010101u + (on ? (la[j] + at) & 0x02020202u : 0u), 0x01010101u, 0x09090909u, 0x11111111u};  // valid symbols only
             sB[j] = u32x4{0x09090909u + (on ? (lb[j] + at) & 0x02020202u : 0u), 0x09090909u, 0x01010101u, 0x11111111u};
 #else
-            sA[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? la[j] : oob, at, HC_COOP_AUX_A);
-            sB[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? lb[j] : oob, at, HC_COOP_AUX_B);
+            sA[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? la[j] : oob, at, 0);
+            sB[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? lb[j] : oob, at, 0);
 #endif
         }
     };
@@ -1265,7 +1257,8 @@ __global__ __launch_bounds__(1024) void bucket_perm_kernel(StoreView st, uint32_
 // results, records and row sink as score_kernel.  WG: lanes per workgroup — one log table per workgroup, so a large table
 // (wide 8-bit symbols: 64 KiB; 16-bit symbols: up to 74 KiB) is shared by 1 024 lanes to keep 16 waves on a CU.
 // LDS: coop_stage_base().
-// SORT: the 128 sub-overlaps of a wave's 64 candidates (two per candidate at most) are dealt to its lanes by length —
+// SORT (always true; it stays in the signature, which names the kernel in hc_get_kernel_info, profiles/ and the tests): the 128
+// sub-overlaps of a wave's 64 candidates (two per candidate at most) are dealt to its lanes by length —
 // ranks from one pair of ballots per length class, longest first; lane t scores rank t and then rank 127 - t — so the 64
 // sub-overlaps the wave steps through together are the longer half, then the shorter half: a wave runs as long as its
 // longest lane, and with windows of 75..150 symbols next to each other a lane is busy 76 % of that time; sorted, the second
@@ -1273,6 +1266,8 @@ __global__ __launch_bounds__(1024) void bucket_perm_kernel(StoreView st, uint32_
 // workgroup barrier (a workgroup-wide sort saved more work and lost it again waiting at its seven barriers).
 // DEPTH: steps of pieces in flight (2: the launch for contig-length read sets, which keeps 8 waves per CU and so has the
 // registers for a second set, StoreView::long_rows).
+// DYN: the length-bucketed launch (bucket_perm_kernel), always with WQ: see below.  `queue` is not read (the bucketing's queue counter
+// served round 3's global workgroup queue, which the tickets replaced).
 // WQ (round 4, the LDS-DMA form): one resident workgroup per CU; the candidates are dealt to the workgroups in equal contiguous ranges and
 // every WAVE takes its items — 64 consecutive candidates each — from a ticket counter in LDS (ds_add_rtn; the first item is the wave's own
 // number, the next ticket is asked for before the current item is scored).  The waves of a CU then finish within one item of each other,
@@ -1283,8 +1278,8 @@ template <typename SymT, int LG, int WG, bool SORT, bool DYN, int DEPTH = 1, boo
 __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 2 : 1))) void score_kernel_coop(StoreView st, ScoreParams prm, const double* __restrict__ lut_g,
                                                             const void* __restrict__ in, uint64_t n, hc_result_rec* __restrict__ out,
                                                             const uint32_t* __restrict__ perm, RowSink sink, uint32_t* __restrict__ queue) {
-    // DYN (length-bucketed launches, bucket_perm_kernel): the workgroup takes WG consecutive ranks of a tile from `queue`;
-    // n_hint = the launch's n, which the queue's geometry was laid out for (the device may know fewer records)
+    static_assert(SORT && (WQ || !DYN), "score_kernel_coop: no launch takes the unsorted form or the bucketed form without tickets");
+    // DYN: n_hint = the launch's n, which the bucketing's geometry was laid out for (the device may know fewer records)
     const uint64_t n_hint = n;
     if (prm.n_dev) {
         const uint64_t nd = *prm.n_dev;
@@ -1301,7 +1296,6 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
     if (threadIdx.x == 0) {
         scratch[24] = 0;
         scratch[29] = 0;  // WQ: the workgroup's ticket counter
-        if (DYN && !WQ) scratch[26] = atomicAdd(queue, 1u);  // the workgroup's first queue entry; [26], [27]: this iteration's and the next one's
         if (sink.started) atomicAdd(sink.started, 1ull);     // kernel-argument-uniform branch
     }
     __syncthreads();
@@ -1317,17 +1311,12 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
     const uint32_t oob = (uint32_t)st.store_bytes;  // the first offset the descriptor's range check rejects (no wrap-around at +16)
     const uint32_t tid = threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * WG;
-    // DYN: queue entry q = piece (q / n_tiles) of tile (q % n_tiles), a piece being WG consecutive ranks — WG / 64 groups of
-    // neighbouring length, one per wave: piece p of every tile before piece p + 1 of any, i.e. the longest candidates of the launch
-    // first.  One atomic per workgroup and iteration, asked for before the current piece is scored and published in LDS behind it;
-    // the barrier that orders the two is the only one of the loop, and the waves reach it together because their groups are alike.
-    // (Round 3's first form queued groups per wave: 1.6 * 10^6 atomics on one address at C3's size, 2.5 x the plain launch on reads of
-    // 100..400 bp.)
+    // DYN: entry q of the order = piece (q / n_tiles) of tile (q % n_tiles), a piece being WG consecutive ranks — WG / 64 groups of
+    // neighbouring length, one per wave: piece p of every tile before piece p + 1 of any, i.e. the longest candidates of the launch first.
     const uint32_t n_tiles = DYN ? (uint32_t)((n_hint + kBucketTile - 1) / kBucketTile) : 0u;
     const uint32_t n_pieces = n_tiles * (kBucketTile / WG);
-    uint32_t q_ahead = 0, iter = 0;
     // WQ: this wave's item, the one it has asked for already, where it stands inside the item
-    const uint32_t wq_steps = WQ ? ((prm.pad >> 8) & 0xFu) : 0u;        // 64-candidate steps per item (1 unless HC_WAVE_QUEUE_STEPS says otherwise)
+    const uint32_t wq_steps = WQ ? ((prm.pad >> 8) & 0xFu) : 0u;        // 64-candidate steps per item (launch_score: kTicketSteps)
     // DYN with WQ (bucketed launches by ticket): the workgroup owns the pieces q = blockIdx, blockIdx + G, ... of the queue's order (every
     // workgroup a like mix of long and short ones) and its waves take (piece, group of 64 ranks) pairs by ticket: no global atomic, no barrier
     const uint32_t dq_pieces = (DYN && WQ && blockIdx.x < n_pieces) ? (n_pieces - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;
@@ -1364,7 +1353,7 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
         wq_item = wq_first + (tid >> 6);  // the first item of a wave: its own number (the tickets start behind the WG / 64 of them)
         if (wq_item < wq_end) wq_next_raw = wq_pull();
     }
-    for (uint64_t block_base = (uint64_t)blockIdx.x * WG;; block_base += stride, ++iter) {
+    for (uint64_t block_base = (uint64_t)blockIdx.x * WG;; block_base += stride) {
         uint64_t slot;
         if (WQ) {
             if (wq_k == wq_steps) {
@@ -1383,12 +1372,6 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
                 slot = ((uint64_t)item * wq_steps + wq_k) * 64u + (tid & 63u);
             }
             ++wq_k;
-        } else if (DYN) {
-            const uint32_t q = scratch[26 + (iter & 1u)];
-            if (q >= n_pieces) break;  // workgroup-uniform
-            if (tid == 0) q_ahead = atomicAdd(queue, 1u);
-            const uint32_t piece = q / n_tiles, tile = q - piece * n_tiles;
-            slot = (uint64_t)tile * kBucketTile + piece * WG + tid;  // (behind the end of the last tile: lanes without a candidate)
         } else {
             if (block_base >= n) break;
             slot = block_base + tid;
@@ -1419,7 +1402,7 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
         }
         const uint32_t L0 = l0 & 0x7FFFFFFFu, L1 = l1 & 0x7FFFFFFFu;
         SubScore s1, s2;
-        if (SORT) {
+        {  // SORT
             // rank of the wave's sub-overlap 2 lane + s, longest class first, by a counting sort over the 128 length classes in the
             // upper half of the wave's own image: every sub-overlap takes a ticket in its class (ds_add_rtn: the tickets of a class
             // are its members in some order), a 64-lane scan over the bins turns the counts into class starts.  (Round 2 ranked
@@ -1480,9 +1463,6 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
             s2.mm = q1[2];
             s2.n = q1[3] & 0x7FFFFFFFu;
             s2.err = q1[3] >> 31;
-        } else {
-            score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, sym, stage, a0, b0, L0, l0 >> 31, Kp, st.inv_n, s1);
-            if (__ballot(ns == 2) != 0ull) score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, sym, stage, a1, b1, L1, l1 >> 31, Kp, st.inv_n, s2);
         }
         if (ns != 2) {  // what a candidate without a second sub-overlap reports (compute_overlap, s-s)
             s2.x = __builtin_nan("");
@@ -1507,10 +1487,6 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
             if (sink.seg_count) append_rows_segment(sink, slot < n, res, i, seg_counter);
             else if (DYN) append_rows_wave(sink, slot < n, res, i);
             else append_rows_block(sink, slot < n, res, i, scratch);
-        }
-        if (DYN && !WQ) {
-            if (tid == 0) scratch[26 + ((iter + 1u) & 1u)] = q_ahead;
-            __syncthreads();
         }
     }
     if (sink.rows && sink.seg_count) {  // kernel-argument-uniform: every wave of the workgroup leaves its loop and arrives here
@@ -1566,425 +1542,230 @@ hipError_t launch_encode(uint32_t symbytes, const uint8_t* bases, const uint8_t*
     return hipGetLastError();
 }
 
-namespace {
-struct ScoreLaunch {
-    const StoreView& st;
-    const ScoreParams& prm;
-    const double* lut_g;
-    const void* in;
-    uint64_t n;
-    hc_result_rec* out;
-    const uint32_t* perm;
-    RowSink sink;
-    uint32_t blocks, wg;
-    size_t lds;
-    hipStream_t stream;
+// ---------------------------------------------------------------------------
+// The scoring kernels a launch can take: one row per instantiation, and nothing else is compiled.  Launching, the LDS limit and the
+// name in hc_get_kernel_info (tests, bench.py's `kernel`, profiles/) all come from here.  Never planned, so not compiled:
+//   score_kernel<uint8_t, G, 6 | 7, false>: a wide (64 KiB) table without bucketing leaves room for two 256-lane workgroups per CU, so
+//     512 lanes always share one table (score_kernel_wide_wg);
+//   score_kernel_coop<uint16_t, 5, 256, ...>: 16-bit symbols mean K >= 61, a table of 32 256 bytes at least: four 256-lane workgroups
+//     never fit a CU, so 1 024 lanes share it;
+//   score_kernel_coop<uint8_t, LG, 256, true, true, 1, true>: a bucketed 256-lane launch keeps at most two workgroups per CU and so
+//     always takes DEPTH = 2.
+#define HC_WQ_NAME_true ", true"
+#define HC_WQ_NAME_false ""
+#define HC_LANE(T, G, LG, BAL) \
+    {false, sizeof(T), LG, 256, G, BAL, 0, false, (const void*)&score_kernel<T, G, LG, BAL>, "hc::score_kernel<" #T ", " #G ", " #LG ", " #BAL ">"}
+#define HC_LANE2(T, G, LG) HC_LANE(T, G, LG, false), HC_LANE(T, G, LG, true)
+#define HC_LANE512(G, LG) \
+    {false, 1, LG, 512, G, false, 0, false, (const void*)&score_kernel_wide_wg<uint8_t, G, LG>, "hc::score_kernel_wide_wg<uint8_t, " #G ", " #LG ">"}
+#define HC_COOP(T, LG, WG, DYN, DEPTH, WQ)                                                                                       \
+    {true, sizeof(T), LG, WG, 0, DYN, DEPTH, WQ, (const void*)&score_kernel_coop<T, LG, WG, true, DYN, DEPTH, WQ>,              \
+     "hc::score_kernel_coop<" #T ", " #LG ", " #WG ", true, " #DYN ", " #DEPTH HC_WQ_NAME_##WQ ">"}
+// the register-staged forms of a 1 024-lane table: static grid (rows appended without segments), items by ticket, bucketed
+#define HC_COOP1024(T, LG) HC_COOP(T, LG, 1024, false, 1, false), HC_COOP(T, LG, 1024, false, 1, true), HC_COOP(T, LG, 1024, true, 1, true)
+static_assert(kWideDmaLanes == 768, "the table names the wide LDS-DMA form's workgroup size");
+static const ScoreKernel kScoreKernels[] = {
+    // one lane, one fetch; 16-bit symbols: 32-symbol fetch groups only (64-symbol groups need 196 registers)
+    HC_LANE2(uint8_t, 4, 3), HC_LANE2(uint8_t, 2, 3), HC_LANE2(uint8_t, 4, 4), HC_LANE2(uint8_t, 2, 4), HC_LANE2(uint8_t, 4, 5), HC_LANE2(uint8_t, 2, 5),
+    HC_LANE(uint8_t, 4, 6, true), HC_LANE(uint8_t, 2, 6, true), HC_LANE(uint8_t, 4, 7, true), HC_LANE(uint8_t, 2, 7, true),
+    HC_LANE512(4, 6), HC_LANE512(2, 6), HC_LANE512(4, 7), HC_LANE512(2, 7), HC_LANE2(uint16_t, 2, 5),
+    // cooperative, tables of at most 16 KiB: 256 lanes (static grid, bucketed); LDS-DMA (static grid for rows appended without segments,
+    // items by ticket)
+    HC_COOP(uint8_t, 3, 256, false, 1, false), HC_COOP(uint8_t, 4, 256, false, 1, false), HC_COOP(uint8_t, 5, 256, false, 1, false),
+    HC_COOP(uint8_t, 3, 256, true, 2, true), HC_COOP(uint8_t, 4, 256, true, 2, true), HC_COOP(uint8_t, 5, 256, true, 2, true),
+    HC_COOP(uint8_t, 3, 1024, false, 0, false), HC_COOP(uint8_t, 4, 1024, false, 0, false), HC_COOP(uint8_t, 5, 1024, false, 0, false),
+    HC_COOP(uint8_t, 3, 1024, false, 0, true), HC_COOP(uint8_t, 4, 1024, false, 0, true), HC_COOP(uint8_t, 5, 1024, false, 0, true),
+    // cooperative, the wide 8-bit table (64 KiB) and 16-bit symbols: one table for 1 024 lanes; the wide table's own LDS-DMA form
+    HC_COOP1024(uint8_t, 6), HC_COOP1024(uint8_t, 7), HC_COOP1024(uint16_t, 5),
+    HC_COOP(uint8_t, 6, 768, false, 0, true), HC_COOP(uint8_t, 7, 768, false, 0, true),
 };
+#undef HC_WQ_NAME_true
+#undef HC_WQ_NAME_false
+#undef HC_LANE
+#undef HC_LANE2
+#undef HC_LANE512
+#undef HC_COOP
+#undef HC_COOP1024
 
-template <typename SymT, int G, int LG>
-void launch_one(const ScoreLaunch& a) {
-    if (a.wg == 512) {
-        if constexpr (sizeof(SymT) == 1 && LG >= 6)
-            hipLaunchKernelGGL((score_kernel_wide_wg<SymT, G, LG>), dim3(a.blocks), dim3(512), a.lds, a.stream, a.st, a.prm, a.lut_g,
-                               a.in, a.n, a.out, a.perm, a.sink);
-        return;
-    }
-    if (a.st.balance)
-        hipLaunchKernelGGL((score_kernel<SymT, G, LG, true>), dim3(a.blocks), dim3(256), a.lds, a.stream, a.st, a.prm, a.lut_g, a.in,
-                           a.n, a.out, a.perm, a.sink);
-    else
-        hipLaunchKernelGGL((score_kernel<SymT, G, LG, false>), dim3(a.blocks), dim3(256), a.lds, a.stream, a.st, a.prm, a.lut_g, a.in,
-                           a.n, a.out, a.perm, a.sink);
+static const ScoreKernel* find_score_kernel(const ScoreKernel& key) {
+    for (const ScoreKernel& k : kScoreKernels)
+        if (k.coop == key.coop && k.symbytes == key.symbytes && k.lg == key.lg && k.wg == key.wg && k.group == key.group && k.bal == key.bal &&
+            k.depth == key.depth && k.wq == key.wq)
+            return &k;
+    return nullptr;
 }
 
-template <typename SymT, int LG>
-void launch_lg(int group, const ScoreLaunch& a) {
-    if constexpr (sizeof(SymT) == 2) {  // 16-bit symbols: 32-symbol fetch groups only (64-symbol groups need 196 registers)
-        launch_one<SymT, 2, LG>(a);
-    } else {
-        if (group == 2) launch_one<SymT, 2, LG>(a);
-        else launch_one<SymT, 4, LG>(a);
-    }
-}
-}  // namespace
-
+constexpr size_t kLdsBytes = 160 * 1024;  // of a CU
 // The LDS-DMA form of the cooperative fetch (score_sub_coop, DEPTH = 0) runs 1 024-lane workgroups, one per CU, whose waves take their items
 // by ticket: launches of fewer candidates than this keep the 256-lane register-staged form, which fills the chip with four times as many
 // workgroups.  2 * 10^5 candidates: 0.0224 against 0.0253 ms, 4 * 10^5: 0.0441 / 0.0482, 10^5: 0.0251 / 0.0198 (profiles/r04_tickets_reg.txt;
-// round 3, static grid: from 5 * 10^5 on).  HC_COOP_DMA=0 turns it off (a tuning knob).
+// round 3, static grid: from 5 * 10^5 on).
 constexpr uint64_t kDmaMinCandidates = 150000;
-static bool coop_dma_wanted() {
-    static const bool on = !(getenv("HC_COOP_DMA") && atoi(getenv("HC_COOP_DMA")) == 0);
-    return on;
+// Items by ticket: one 64-candidate step per item (C3 with 1 / 2 / 4 / 8 steps: 6.55 / 6.61 / 6.69 / 6.72 ms; profiles/r04_wq_local.txt).
+constexpr uint32_t kTicketSteps = 1;
+// The static grids: the LDS-DMA form queues 16 workgroups per CU, which even out what the CUs finish at different times (C3: 1 per CU
+// 7.32 ms, 4: 7.10, 16: 6.92, 64: 6.88, 256: 7.32, one per 1 024 candidates 7.63; profiles/r03_dma_grid.txt); the register-staged form
+// 4 per resident slot (C2: 1 / 2 / 4 alike, profiles/r04_grid_c2.txt), the per-lane kernel 4 per slot as well.
+constexpr uint64_t kDmaGridPerCu = 16, kGridPerSlot = 4;
+static uint64_t coop_dma_min() {  // HC_COOP_DMA_MIN: test knob — the LDS-DMA form for launches of that many candidates and more
+    const char* e = getenv("HC_COOP_DMA_MIN");
+    return e ? strtoull(e, nullptr, 10) : kDmaMinCandidates;
 }
 // HC_WIDE_DMA=0: the wide 8-bit table (64 KiB) keeps the register-staged form at every size (round 6's A/B knob; default: its own LDS-DMA form)
 static bool wide_dma_wanted() {  // (read at every launch: the tests switch it inside one process)
     const char* e = getenv("HC_WIDE_DMA");
     return !(e && atoi(e) == 0);
 }
-// HC_WAVE_QUEUE=0: the LDS-DMA form on the static grid (round 3's launch; an A/B knob); HC_WAVE_QUEUE_STEPS: 64-candidate steps per item (1)
-static bool wave_queue_on(uint32_t* steps_out) {
-    static const bool on = !(getenv("HC_WAVE_QUEUE") && atoi(getenv("HC_WAVE_QUEUE")) == 0);
-    static const uint32_t steps = getenv("HC_WAVE_QUEUE_STEPS") ? (uint32_t)std::min(8, std::max(1, atoi(getenv("HC_WAVE_QUEUE_STEPS")))) : 1u;
-    if (steps_out) *steps_out = steps;
-    return on;
-}
-static uint64_t coop_dma_min() {  // HC_COOP_DMA_MIN: test knob — the LDS-DMA form for launches of that many candidates and more
-    const char* e = getenv("HC_COOP_DMA_MIN");
-    return e ? strtoull(e, nullptr, 10) : kDmaMinCandidates;
-}
 
-// fetch_group: 0 = cooperative fetch (falls back to lane_fetch_group for stores of 4 GiB and more); per lane: 4 = 64-symbol
-// fetch groups (short reads), 2 = 32-symbol groups (contig-length sequences); chosen per
-// read set by hc_set_reads.  rows == nullptr: plain scoring; otherwise every non-dropped record is also appended to
-// rows (RowSink above).
-hipError_t launch_score(const StoreView& st, const ScoreParams& prm, const double* lut_g, const void* in, uint64_t n,
-                        hc_result_rec* out, const uint32_t* perm, uint32_t n_cu, int fetch_group, int lane_fetch_group, hc_gather_row* rows,
-                        unsigned long long* row_count, uint64_t cap, uint64_t base_index, hipStream_t stream,
-                        const hc_line_rec* lines_in, hc_line_rec* lines_out, uint32_t* bucket_perm, uint32_t* bucket_queue, hc_gather_row* seg_buf,
-                        uint32_t* seg_count, uint64_t seg_total_rows, uint32_t* spill_turn, unsigned long long* started, uint32_t* started_groups) {
-    if (started_groups) *started_groups = 0;
-    if (n == 0) return hipSuccess;
-    const uint32_t lg = lut_lg(st.K);
-    // rows != nullptr is hc_score_pack_device's layout: row_count = the first word of the 32-byte header row in front of `rows`.  A launch
-    // that appends through the counter itself (no segments) needs it zeroed first; a segmented launch leaves the header to its compaction.
-    auto zero_header = [&]() -> hipError_t { return rows ? hipMemsetAsync(row_count, 0, sizeof(hc_gather_row), stream) : hipSuccess; };
-    if (fetch_group == 0) {
-        // a 4 KiB image per wave next to the table: 256-lane workgroups while four of them fit a CU, else one table for 1 024 lanes
-        const bool coop = st.store_bytes < 0xFFFF0000ull;
-        const size_t lds_256 = coop_stage_base(st.lut_bytes, 256) + 4 * kStageBytesPerWave;
-        const uint32_t wg_c = 4 * lds_256 <= 160 * 1024 ? 256u : 1024u;
-        const size_t lds_c = coop_stage_base(st.lut_bytes, wg_c) + (wg_c / 64) * kStageBytesPerWave;
-        if (coop && lds_c <= 160 * 1024) {
-            uint32_t per_cu = (uint32_t)((160 * 1024) / lds_c);
-            per_cu = per_cu * (wg_c / 64) > 32 ? 32 / (wg_c / 64) : per_cu;
-            size_t lds_launch = lds_c;
-            static const int wg_per_cu = getenv("HC_COOP_WG_PER_CU") ? atoi(getenv("HC_COOP_WG_PER_CU")) : 0;  // experiment knob: fewer resident workgroups
-            // 8 waves per CU: contig-length sequences (StoreView::long_rows) and every length-bucketed launch (measured on reads of
-            // 100..400, 150..1 500 and 150..6 000 bp: 0.233 / 0.348 / 0.629 ms against 0.260 / 0.435 / 0.841 with 16)
-            const uint32_t want_per_cu = wg_per_cu > 0 ? (uint32_t)wg_per_cu : ((st.long_rows || st.balance) && wg_c == 256 ? 2u : 0u);
-            if (want_per_cu > 0 && want_per_cu < per_cu) {
-                per_cu = want_per_cu;
-                lds_launch = std::max(lds_c, (size_t)(160 * 1024) / (per_cu + 1) + 1024);  // LDS no other workgroup fits beside
-            }
-            // mixed sequence lengths: bucket the candidates by (tile, length class) first; the waves then take groups of 64
-            // ranks from a queue (bucket_perm_kernel)
-            const bool bucketed = st.balance && bucket_perm && bucket_queue && n < (1ull << 32);
-            uint64_t blocks_c = (n + wg_c - 1) / wg_c;
-            static const int grid_mult = getenv("HC_GRID_MULT") ? std::max(1, atoi(getenv("HC_GRID_MULT"))) : 4;  // experiment knob
-            const uint64_t cap_c = (uint64_t)n_cu * per_cu * (bucketed ? 1 : grid_mult);  // a queue needs resident workgroups only
-            if (blocks_c > cap_c) blocks_c = cap_c;
-            RowSink sink{rows, row_count, cap, base_index, lines_in, lines_out, nullptr, nullptr, 0u, 0u, nullptr, nullptr, started};
-            // the cooperative launches collect their rows in per-workgroup segments (RowSink); G = the launch's workgroups.  Of the
-            // seg_total_rows rows of scratch the last `cap` are the spill area, the others are dealt to the workgroups.
-            const bool segmented = rows && seg_buf && seg_count && spill_turn && !lines_in && cap < 0xFFFFFFFFull && seg_total_rows > cap;
-            bool seg_on = false;
-            auto use_segments = [&](uint64_t G) {
-                seg_on = segmented && G <= kSinkMaxGroups;  // seg_count holds that many counters (a larger grid only under HC_GRID_MULT)
-                if (!seg_on) return;
-                const uint64_t per = (seg_total_rows - cap) / G;
-                sink.seg_buf = seg_buf;
-                sink.seg_count = seg_count;
-                sink.seg_rows = (uint32_t)std::min<uint64_t>(per, 0xFFFFFFFFull);
-                sink.spill_buf = seg_buf + (seg_total_rows - cap);
-                sink.spill_cap = (uint32_t)cap;
-                sink.spill_count = seg_count + kSinkMaxGroups + (*spill_turn & 1u);
-            };
-            auto compact_segments = [&](uint64_t G) {
-                if (seg_on)
-                    hipLaunchKernelGGL(sink_compact_kernel, dim3((uint32_t)G), dim3(256), 0, stream, (const hc_gather_row*)seg_buf, (const uint32_t*)seg_count,
-                                       sink.seg_rows, (uint32_t)G, rows, (unsigned long long)cap, row_count, (const hc_gather_row*)sink.spill_buf,
-                                       (const uint32_t*)sink.spill_count, sink.spill_cap, seg_count + kSinkMaxGroups + ((*spill_turn + 1u) & 1u));
-                if (seg_on) ++*spill_turn;  // the next segmented launch spills through the counter this one has just zeroed
-            };
-            static const int deep_env = getenv("HC_COOP_DEPTH") ? atoi(getenv("HC_COOP_DEPTH")) : 0;  // experiment knob: 1 = one step in flight always
-            const bool deep = bucketed && per_cu <= 2 && wg_c == 256 && deep_env != 1;
-            if (bucketed) {
-                const uint32_t tiles = (uint32_t)((n + kBucketTile - 1) / kBucketTile);
-                if (st.symbytes == 2)
-                    hipLaunchKernelGGL((bucket_perm_kernel<2>), dim3(tiles), dim3(1024), 0, stream, st, prm.min_read_len, prm.rec_fmt, in, n, prm.n_dev,
-                                       perm, bucket_perm, bucket_queue);
-                else
-                    hipLaunchKernelGGL((bucket_perm_kernel<1>), dim3(tiles), dim3(1024), 0, stream, st, prm.min_read_len, prm.rec_fmt, in, n, prm.n_dev,
-                                       perm, bucket_perm, bucket_queue);
-                perm = bucket_perm;
-            }
-            // LDS-DMA form (score_sub_coop, DEPTH = 0): 8 KiB of image per wave, so one 1 024-lane workgroup with one table per CU;
-            // 8-bit symbols with a table of at most 16 KiB
-            const size_t lds_dma = coop_stage_base(st.lut_bytes, 1024) + 16 * 2 * kStageBytesPerWave;
-            {
-                // the wide 8-bit table (64 KiB) in the LDS-DMA form: 12 waves per CU instead of the register-staged form's 16 (round 6;
-                // HC_WIDE_DMA=0: the register-staged form, the A/B knob)
-                uint32_t steps = 1;
-                if (wide_dma_wanted() && coop_dma_wanted() && n >= coop_dma_min() && !bucketed && st.symbytes == 1 && lg >= 6 && st.lut_bytes == 65536u &&
-                    wave_queue_on(&steps) && !(rows && !segmented)) {
-                    const uint64_t blocks_w = std::min<uint64_t>((n + kWideDmaLanes - 1) / kWideDmaLanes, n_cu);
-                    ScoreParams pq = prm;
-                    pq.pad = (prm.pad & 0xFFu) | (steps << 8);
-                    use_segments(blocks_w);
-                    if (!seg_on) {
-                        const hipError_t ze = zero_header();
-                        if (ze != hipSuccess) return ze;
-                    }
-                    if (lg == 6)
-                        hipLaunchKernelGGL((score_kernel_coop<uint8_t, 6, (int)kWideDmaLanes, true, false, 0, true>), dim3((uint32_t)blocks_w),
-                                           dim3(kWideDmaLanes), 160 * 1024, stream, st, pq, lut_g, in, n, out, perm, sink, nullptr);
-                    else
-                        hipLaunchKernelGGL((score_kernel_coop<uint8_t, 7, (int)kWideDmaLanes, true, false, 0, true>), dim3((uint32_t)blocks_w),
-                                           dim3(kWideDmaLanes), 160 * 1024, stream, st, pq, lut_g, in, n, out, perm, sink, nullptr);
-                    compact_segments(blocks_w);
-                    if (started_groups) *started_groups = (uint32_t)blocks_w;
-                    return hipGetLastError();
-                }
-            }
-            if (coop_dma_wanted() && n >= coop_dma_min() && !bucketed && st.symbytes == 1 && lg <= 5 && lds_dma <= 160 * 1024) {
-                uint64_t blocks_d = (n + 1023) / 1024;
-                // one workgroup is resident per CU; 16 queued per CU even out what the CUs finish at different times (C3: 1 per CU 7.32 ms,
-                // 4: 7.10, 16: 6.92, 64: 6.88, 256: 7.32, one per 1 024 candidates 7.63; profiles/r03_dma_grid.txt)
-                static const int grid_mult_d = getenv("HC_GRID_MULT") ? std::max(1, atoi(getenv("HC_GRID_MULT"))) : 16;
-                const uint64_t cap_d = (uint64_t)n_cu * grid_mult_d;
-                if (blocks_d > cap_d) blocks_d = cap_d;
-                uint32_t steps = 1;
-                // (rows collected without segments — a payload of 2^32 rows and more — go through append_rows_block, whose barriers need every
-                // wave of a workgroup in the same iteration: that launch keeps the static grid)
-                if (wave_queue_on(&steps) && !(rows && !segmented)) {
-                    // one resident workgroup per CU; its waves take their items from a ticket counter in LDS (score_kernel_coop: WQ)
-                    blocks_d = std::min<uint64_t>((n + 1023) / 1024, n_cu);
-                    ScoreParams pq = prm;
-                    pq.pad = (prm.pad & 0xFFu) | (steps << 8);
-                    use_segments(blocks_d);
-                    if (!seg_on) {
-                        const hipError_t ze = zero_header();
-                        if (ze != hipSuccess) return ze;
-                    }
-#define HC_COOP_WQ_LAUNCH(LG_)                                                                                                                  \
-    hipLaunchKernelGGL((score_kernel_coop<uint8_t, LG_, 1024, true, false, 0, true>), dim3((uint32_t)blocks_d), dim3(1024), lds_dma, stream, st, \
-                       pq, lut_g, in, n, out, perm, sink, nullptr)
-                    if (lg == 3) HC_COOP_WQ_LAUNCH(3);
-                    else if (lg == 4) HC_COOP_WQ_LAUNCH(4);
-                    else HC_COOP_WQ_LAUNCH(5);
-#undef HC_COOP_WQ_LAUNCH
-                    compact_segments(blocks_d);
-                    if (started_groups) *started_groups = (uint32_t)blocks_d;
-                    return hipGetLastError();
-                }
-                use_segments(blocks_d);
-                if (!seg_on) {
-                    const hipError_t ze = zero_header();
-                    if (ze != hipSuccess) return ze;
-                }
-#define HC_COOP_DMA_LAUNCH(LG_)                                                                                                       \
-    hipLaunchKernelGGL((score_kernel_coop<uint8_t, LG_, 1024, true, false, 0>), dim3((uint32_t)blocks_d), dim3(1024), lds_dma, stream, st, prm, \
-                       lut_g, in, n, out, perm, sink, nullptr)
-                if (lg == 3) HC_COOP_DMA_LAUNCH(3);
-                else if (lg == 4) HC_COOP_DMA_LAUNCH(4);
-                else HC_COOP_DMA_LAUNCH(5);
-#undef HC_COOP_DMA_LAUNCH
-                compact_segments(blocks_d);
-                if (started_groups) *started_groups = (uint32_t)blocks_d;
-                return hipGetLastError();
-            }
-            using W256 = std::integral_constant<int, 256>;
-            using W1024 = std::integral_constant<int, 1024>;
-            // the plain register-staged launches of 1 024-lane workgroups (wide 8-bit and 16-bit symbol tables: one workgroup per CU) take their
-            // items by ticket too (WQ): C4 with 35 quality values 0.153 -> 0.122 ms, with 60 (16-bit symbols) 0.208 -> 0.179; 256-lane workgroups
-            // (four per CU, four waves each) gain nothing by it (0.0195 / 0.0198, 0.0505 / 0.0482 ms) and keep the static grid
-            // (profiles/r04_tickets_reg.txt)
-            uint32_t steps_c = 1;
-            const bool tickets = !bucketed && wg_c == 1024 && wave_queue_on(&steps_c) && !(rows && !segmented);  // (append_rows_block has barriers)
-            ScoreParams pq = prm;
-            if (tickets) {
-                pq.pad = (prm.pad & 0xFFu) | (steps_c << 8);
-                blocks_c = std::min<uint64_t>((n + wg_c - 1) / wg_c, (uint64_t)n_cu * per_cu);
-            }
-            // bucketed launches go by ticket as well: the workgroup owns the pieces blockIdx, blockIdx + G, ... of the longest-first order and
-            // its waves take (piece, group of 64 ranks) pairs from the LDS counter — no global queue atomic, no barrier per piece (round 3's
-            // workgroup queue: C5 0.627 -> 0.620 ms, singles of 150..1 500 bp 0.342 -> 0.324, 120..900 bp 0.283 -> 0.268; profiles/r04_bucket_tickets.txt)
-            if (bucketed) pq.pad = (prm.pad & 0xFFu) | (1u << 8);
-            // The instantiations a read set can reach: 8-bit symbols with a table of at most 16 KiB (LG 3..5) always fit four 256-lane
-            // workgroups per CU; the wide 8-bit encoding (64 KiB table) always shares one table among 1 024 lanes; 16-bit symbols take
-            // either, by table size.  Nothing else is compiled (round 3 carried 45 scoring kernels, a third of them unreachable).
-            auto launch_coop = [&](auto sym_tag, auto lg_tag, auto wg_tag) {
-                using T_ = decltype(sym_tag);
-                constexpr int LG_ = decltype(lg_tag)::value;
-                constexpr int WG_ = decltype(wg_tag)::value;
-                if (bucketed && deep) {
-                    if constexpr (WG_ == 256)
-                        hipLaunchKernelGGL((score_kernel_coop<T_, LG_, 256, true, true, 2, true>), dim3((uint32_t)blocks_c), dim3(256), lds_launch, stream, st, pq,
-                                           lut_g, in, n, out, perm, sink, bucket_queue);
-                } else if (bucketed) {
-                    hipLaunchKernelGGL((score_kernel_coop<T_, LG_, WG_, true, true, 1, true>), dim3((uint32_t)blocks_c), dim3(WG_), lds_launch, stream, st, pq, lut_g,
-                                       in, n, out, perm, sink, bucket_queue);
-                } else if (tickets) {
-                    if constexpr (WG_ == 1024)
-                        hipLaunchKernelGGL((score_kernel_coop<T_, LG_, 1024, true, false, 1, true>), dim3((uint32_t)blocks_c), dim3(1024), lds_launch, stream, st,
-                                           pq, lut_g, in, n, out, perm, sink, nullptr);
-                } else {
-                    hipLaunchKernelGGL((score_kernel_coop<T_, LG_, WG_, true, false>), dim3((uint32_t)blocks_c), dim3(WG_), lds_launch, stream, st, prm, lut_g,
-                                       in, n, out, perm, sink, nullptr);
-                }
-            };
-            use_segments(blocks_c);
-            if (!seg_on) {
-                const hipError_t ze = zero_header();
-                if (ze != hipSuccess) return ze;
-            }
-            if (st.symbytes == 2) {
-                if (wg_c == 256) launch_coop(uint16_t{}, std::integral_constant<int, 5>{}, W256{});
-                else launch_coop(uint16_t{}, std::integral_constant<int, 5>{}, W1024{});
-            } else if (lg >= 6) {
-                if (wg_c != 1024) return hipErrorInvalidConfiguration;  // (a 64 KiB table never leaves room for four workgroups)
-                if (lg == 6) launch_coop(uint8_t{}, std::integral_constant<int, 6>{}, W1024{});
-                else launch_coop(uint8_t{}, std::integral_constant<int, 7>{}, W1024{});
-            } else {
-                if (wg_c != 256) return hipErrorInvalidConfiguration;   // (tables of at most 16 KiB always do)
-                if (lg == 3) launch_coop(uint8_t{}, std::integral_constant<int, 3>{}, W256{});
-                else if (lg == 4) launch_coop(uint8_t{}, std::integral_constant<int, 4>{}, W256{});
-                else launch_coop(uint8_t{}, std::integral_constant<int, 5>{}, W256{});
-            }
-            compact_segments(blocks_c);
-            if (started_groups) *started_groups = (uint32_t)blocks_c;
-            return hipGetLastError();
+ScorePlan plan_score_launch(const StoreView& st, bool coop_fetch, int lane_group, uint32_t n_cu, uint64_t n, RowSinkKind sink) {
+    ScorePlan p;
+    const uint32_t lg = lut_lg(st.K), lgt = st.symbytes == 2 ? 5u : lg;  // (the template's LG: 5 for 16-bit symbols)
+    ScoreKernel key{};
+    key.symbytes = st.symbytes;
+    key.lg = lgt;
+    // a 4 KiB image per wave next to the table: 256-lane workgroups while four of them fit a CU, else one table for 1 024 lanes
+    const size_t lds_256 = coop_stage_base(st.lut_bytes, 256) + 4 * kStageBytesPerWave;
+    const uint32_t wg_c = 4 * lds_256 <= kLdsBytes ? 256u : 1024u;
+    const size_t lds_c = coop_stage_base(st.lut_bytes, wg_c) + (wg_c / 64) * kStageBytesPerWave;
+    if (coop_fetch && st.store_bytes < 0xFFFF0000ull && lds_c <= kLdsBytes) {
+        uint32_t per_cu = std::min<uint32_t>((uint32_t)(kLdsBytes / lds_c), 32 / (wg_c / 64));
+        p.lds = p.lds_form = lds_c;
+        // 8 waves per CU: contig-length sequences (StoreView::long_rows) and every length-bucketed launch (measured on reads of
+        // 100..400, 150..1 500 and 150..6 000 bp: 0.233 / 0.348 / 0.629 ms against 0.260 / 0.435 / 0.841 with 16)
+        if ((st.long_rows || st.balance) && wg_c == 256 && per_cu > 2) {
+            per_cu = 2;
+            p.lds = std::max(lds_c, kLdsBytes / 3 + 1024);  // LDS no third workgroup fits beside
         }
-        fetch_group = lane_fetch_group;
+        p.waves_per_cu = per_cu * (wg_c / 64);
+        // mixed sequence lengths: bucket the candidates by (tile, length class) first (bucket_perm_kernel)
+        p.bucketed = st.balance && n < (1ull << 32);
+        // rows appended without segments go through append_rows_block, whose barriers need every wave of a workgroup in the same
+        // iteration: those launches keep a static grid
+        const bool tickets_ok = sink != RowSinkKind::unsegmented;
+        // the register-staged form.  1 024-lane workgroups (one per CU) take their items by ticket (WQ): C4 with 35 quality values
+        // 0.153 -> 0.122 ms, with 60 (16-bit symbols) 0.208 -> 0.179; 256-lane workgroups (four per CU, four waves each) gain nothing by
+        // it (0.0195 / 0.0198, 0.0505 / 0.0482 ms) and keep the static grid (profiles/r04_tickets_reg.txt).  Bucketed launches go by
+        // ticket as well: the workgroup owns the pieces blockIdx, blockIdx + G, ... of the longest-first order and its waves take (piece,
+        // group of 64 ranks) pairs from the LDS counter (C5 0.627 -> 0.620 ms, singles of 150..1 500 bp 0.342 -> 0.324, 120..900 bp
+        // 0.283 -> 0.268; profiles/r04_bucket_tickets.txt)
+        const bool tickets = p.bucketed || (wg_c == 1024 && tickets_ok);
+        key.coop = true;
+        key.wg = wg_c;
+        key.bal = p.bucketed;
+        key.depth = p.bucketed && per_cu <= 2 && wg_c == 256 ? 2 : 1;  // 8 waves per CU leave the registers for a second step in flight
+        key.wq = tickets;
+        p.kernel = p.staged = find_score_kernel(key);
+        p.blocks = (uint32_t)std::min<uint64_t>((n + wg_c - 1) / wg_c, (uint64_t)n_cu * per_cu * (tickets ? 1 : kGridPerSlot));
+        if (n >= coop_dma_min() && !p.bucketed && st.symbytes == 1) {
+            // the LDS-DMA form: 8 KiB of image per wave, one workgroup with one table per CU.  Tables of at most 16 KiB: 1 024 lanes; the
+            // wide 8-bit table (64 KiB, round 6): 768 lanes, whose scratch words sit in an unaddressed row of the table (coop_stage_base)
+            const size_t lds_dma = coop_stage_base(st.lut_bytes, 1024) + 16 * 2 * kStageBytesPerWave;
+            const bool wide = lg >= 6 && st.lut_bytes == 65536u && wide_dma_wanted() && tickets_ok;
+            if (wide || (lg <= 5 && lds_dma <= kLdsBytes)) {
+                key.wg = wide ? kWideDmaLanes : 1024u;
+                key.bal = false;
+                key.depth = 0;
+                key.wq = tickets_ok;
+                p.kernel = find_score_kernel(key);
+                p.lds = p.lds_form = wide ? kLdsBytes : lds_dma;
+                p.waves_per_cu = key.wg / 64;
+                p.blocks = (uint32_t)std::min<uint64_t>((n + key.wg - 1) / key.wg, (uint64_t)n_cu * (tickets_ok ? 1 : kDmaGridPerCu));
+            }
+        }
+        // the cooperative launches collect their rows in per-workgroup segments (RowSink; seg_count holds kSinkMaxGroups counters)
+        p.segmented = sink == RowSinkKind::segmented && p.blocks <= kSinkMaxGroups;
+        return p;
     }
+    // one lane, one fetch.  Fill the chip: enough 256-lane workgroups for 8 waves per SIMD, bounded by LDS.
     auto lds_for = [&](uint32_t lanes) { return st.lut_bytes + (128 + (st.balance ? kBalItems : 1) * lanes + 32) * sizeof(uint32_t); };
-    // Fill the chip: enough 256-thread blocks for 8 waves per SIMD, bounded by LDS.
-    uint32_t blocks_per_cu = 8;
-    const uint32_t by_lds = (uint32_t)((160 * 1024) / lds_for(256));
-    if (by_lds < blocks_per_cu) blocks_per_cu = by_lds < 1 ? 1 : by_lds;
+    const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (uint32_t)(kLdsBytes / lds_for(256))));
     // large table, few workgroups per CU: let 512 lanes share each table (measured, C4, 35 quality values, 64 KiB
     // table: 256 lanes 0.169 ms, 512 lanes 0.152 ms, 1 024 lanes 0.174 ms)
-    const uint32_t wg = (!st.balance && st.symbytes == 1 && lg >= 6 && blocks_per_cu <= 2) ? 512u : 256u;
-    const size_t lds = lds_for(wg);
-    const uint64_t per_wg = (uint64_t)wg * (st.balance ? kBalItems : 1);  // candidates per workgroup iteration
-    uint64_t blocks = (n + per_wg - 1) / per_wg;
-    const uint64_t grid_cap = (uint64_t)n_cu * blocks_per_cu * 4;  // grid-stride beyond this
-    if (blocks > grid_cap) blocks = grid_cap;
-    {
-        const hipError_t ze = zero_header();
-        if (ze != hipSuccess) return ze;
-    }
-    const ScoreLaunch a{st, prm, lut_g, in, n, out, perm, RowSink{rows, row_count, cap, base_index, lines_in, lines_out, nullptr, nullptr, 0u, 0u, nullptr, nullptr}, (uint32_t)blocks, wg, lds, stream};
-    if (st.symbytes == 2) launch_lg<uint16_t, 5>(fetch_group, a);
-    else if (lg == 3) launch_lg<uint8_t, 3>(fetch_group, a);
-    else if (lg == 4) launch_lg<uint8_t, 4>(fetch_group, a);
-    else if (lg == 5) launch_lg<uint8_t, 5>(fetch_group, a);
-    else if (lg == 6) launch_lg<uint8_t, 6>(fetch_group, a);
-    else launch_lg<uint8_t, 7>(fetch_group, a);
-    return hipGetLastError();
+    key.wg = (!st.balance && st.symbytes == 1 && lg >= 6 && per_cu <= 2) ? 512u : 256u;
+    key.group = st.symbytes == 2 || lane_group == 2 ? 2 : 4;
+    key.bal = st.balance && key.wg == 256;
+    p.kernel = find_score_kernel(key);
+    p.lds = p.lds_form = lds_for(key.wg);
+    const uint64_t per_wg = (uint64_t)key.wg * (st.balance ? kBalItems : 1);  // candidates per workgroup iteration
+    p.blocks = (uint32_t)std::min<uint64_t>((n + per_wg - 1) / per_wg, (uint64_t)n_cu * per_cu * kGridPerSlot);  // grid-stride beyond
+    return p;
 }
 
-// Which kernel launch_score picks for this store, as text (hc_get_kernel_info: tests and bench.py name the measured kernel with it).
-std::string describe_score_kernel(const StoreView& st, int fetch_group, int lane_fetch_group, uint32_t n_cu, uint64_t n) {
-    const uint32_t lg = lut_lg(st.K);
-    const std::string sym = st.symbytes == 2 ? "uint16_t" : "uint8_t";
-    const std::string enc = st.symbytes == 2 ? "u16" : (lg >= 6 ? "wide8" : "packed8");
-    char buf[640];
-    if (fetch_group == 0) {
-        const bool coop = st.store_bytes < 0xFFFF0000ull;
-        const size_t lds_256 = coop_stage_base(st.lut_bytes, 256) + 4 * kStageBytesPerWave;
-        const uint32_t wg_c = 4 * lds_256 <= 160 * 1024 ? 256u : 1024u;
-        const size_t lds_c = coop_stage_base(st.lut_bytes, wg_c) + (wg_c / 64) * kStageBytesPerWave;
-        if (coop && lds_c <= 160 * 1024) {
-            uint32_t per_cu = (uint32_t)((160 * 1024) / lds_c);
-            per_cu = per_cu * (wg_c / 64) > 32 ? 32 / (wg_c / 64) : per_cu;
-            if ((st.long_rows || st.balance) && wg_c == 256 && per_cu > 2) per_cu = 2;
-            const bool deep = st.balance && per_cu <= 2 && wg_c == 256;
-            const uint32_t lgt = st.symbytes == 2 ? 5u : lg;
-            char small[128];
-            snprintf(small, sizeof small, "hc::score_kernel_coop<%s, %u, %u, true, %s, %d%s>", sym.c_str(), lgt, wg_c, st.balance ? "true" : "false", deep ? 2 : 1,
-                     (st.balance || (wg_c == 1024 && wave_queue_on(nullptr))) ? ", true" : "");
-            const size_t lds_dma = coop_stage_base(st.lut_bytes, 1024) + 16 * 2 * kStageBytesPerWave;
-            // the wide 8-bit table: its own LDS-DMA form, 768 lanes (launch_score)
-            if (!st.balance && st.symbytes == 1 && lg >= 6 && st.lut_bytes == 65536u && wide_dma_wanted() && coop_dma_wanted() && wave_queue_on(nullptr) &&
-                (n == 0 || n >= coop_dma_min())) {
-                snprintf(buf, sizeof buf, "hc::score_kernel_coop<%s, %u, %u, true, false, 0, true> encoding=%s table_bytes=%u lds_bytes=%u waves_per_cu=%u "
-                                          "LDS-DMA fetch for launches of %llu candidates and more (one workgroup per CU, the waves take their items from a "
-                                          "ticket counter in LDS; the scratch words sit in an unaddressed row of the table); smaller launches: %s",
-                         sym.c_str(), lg, kWideDmaLanes, enc.c_str(), st.lut_bytes, 160u * 1024u, kWideDmaLanes / 64u, (unsigned long long)coop_dma_min(), small);
-                return buf;
-            }
-            const bool dma = !st.balance && st.symbytes == 1 && lg <= 5 && lds_dma <= 160 * 1024 && coop_dma_wanted();
-            // n != 0: the form a launch of n candidates takes; n == 0: the read set's forms in general
-            if (dma && (n == 0 || n >= coop_dma_min())) {
-                const bool wq = wave_queue_on(nullptr);
-                (void)n_cu;
-                snprintf(buf, sizeof buf, "hc::score_kernel_coop<%s, %u, 1024, true, false, 0%s> encoding=%s table_bytes=%u lds_bytes=%zu waves_per_cu=16 "
-                                          "LDS-DMA fetch for launches of %llu candidates and more (one workgroup per CU, the waves take their items from a "
-                                          "ticket counter in LDS); smaller launches: %s",
-                         sym.c_str(), lgt, wq ? ", true" : "", enc.c_str(), st.lut_bytes, lds_dma, (unsigned long long)coop_dma_min(), small);
-            } else
-                snprintf(buf, sizeof buf, "%s encoding=%s table_bytes=%u lds_bytes=%zu waves_per_cu=%u%s", small, enc.c_str(), st.lut_bytes, lds_c,
-                         per_cu * (wg_c / 64), st.balance ? " length-bucketed (hc::bucket_perm_kernel, items by ticket)" : "");
-            return buf;
-        }
-        fetch_group = lane_fetch_group;
+hipError_t launch_score(const ScorePlan& plan, const StoreView& st, ScoreParams prm, const double* lut_g, const void* in, uint64_t n,
+                        hc_result_rec* out, const uint32_t* perm, const ScoreBuffers& b, hipStream_t stream, uint32_t* started_groups) {
+    if (started_groups) *started_groups = 0;
+    if (n == 0) return hipSuccess;
+    if (!plan.kernel) return hipErrorInvalidConfiguration;
+    const ScoreKernel& k = *plan.kernel;
+    if (plan.bucketed) {
+        const uint32_t tiles = (uint32_t)((n + kBucketTile - 1) / kBucketTile);
+        if (st.symbytes == 2)
+            hipLaunchKernelGGL((bucket_perm_kernel<2>), dim3(tiles), dim3(1024), 0, stream, st, prm.min_read_len, prm.rec_fmt, in, n, prm.n_dev, perm,
+                               b.bucket_perm, b.bucket_queue);
+        else
+            hipLaunchKernelGGL((bucket_perm_kernel<1>), dim3(tiles), dim3(1024), 0, stream, st, prm.min_read_len, prm.rec_fmt, in, n, prm.n_dev, perm,
+                               b.bucket_perm, b.bucket_queue);
+        perm = b.bucket_perm;
     }
-    const int g = st.symbytes == 2 ? 2 : (fetch_group == 2 ? 2 : 4);
-    snprintf(buf, sizeof buf, "hc::score_kernel<%s, %d, %u, %s> encoding=%s table_bytes=%u (one lane, one fetch)", sym.c_str(), g, st.symbytes == 2 ? 5u : lg,
-             st.balance ? "true" : "false", enc.c_str(), st.lut_bytes);
+    RowSink sink{b.rows, b.row_count, b.cap, b.base_index, b.lines_in, b.lines_out, nullptr, nullptr, 0u, 0u, nullptr, nullptr, k.coop ? b.started : nullptr};
+    // Of the seg_total_rows rows of segment scratch the last `cap` are the spill area, the others are dealt to the workgroups.
+    const uint64_t spill_at = b.seg_total_rows - b.cap;
+    if (plan.segmented) {
+        sink.seg_buf = b.seg_buf;
+        sink.seg_count = b.seg_count;
+        sink.seg_rows = (uint32_t)std::min<uint64_t>(spill_at / plan.blocks, 0xFFFFFFFFull);
+        sink.spill_buf = b.seg_buf + spill_at;
+        sink.spill_cap = (uint32_t)b.cap;
+        sink.spill_count = b.seg_count + kSinkMaxGroups + (*b.spill_turn & 1u);
+    } else if (b.rows) {
+        // rows is hc_score_pack_device's layout: row_count = the first word of the 32-byte header row in front of `rows`.  A launch that
+        // appends through the counter itself needs it zeroed first; a segmented launch leaves the header to its compaction.
+        const hipError_t ze = hipMemsetAsync(b.row_count, 0, sizeof(hc_gather_row), stream);
+        if (ze != hipSuccess) return ze;
+    }
+    if (k.wq) prm.pad = (prm.pad & 0xFFu) | (kTicketSteps << 8);
+    uint32_t* queue = plan.bucketed ? b.bucket_queue : nullptr;
+    void* args[] = {(void*)&st, &prm, &lut_g, &in, &n, &out, &perm, &sink, &queue};  // (the per-lane kernels take the first eight)
+    const hipError_t le = hipLaunchKernel(k.fn, dim3(plan.blocks), dim3(k.wg), args, plan.lds, stream);
+    if (plan.segmented) {
+        hipLaunchKernelGGL(sink_compact_kernel, dim3(plan.blocks), dim3(256), 0, stream, (const hc_gather_row*)b.seg_buf, (const uint32_t*)b.seg_count,
+                           sink.seg_rows, plan.blocks, b.rows, (unsigned long long)b.cap, b.row_count, (const hc_gather_row*)sink.spill_buf,
+                           (const uint32_t*)sink.spill_count, sink.spill_cap, b.seg_count + kSinkMaxGroups + ((*b.spill_turn + 1u) & 1u));
+        ++*b.spill_turn;  // the next segmented launch spills through the counter this one has just zeroed
+    }
+    if (started_groups && k.coop) *started_groups = plan.blocks;
+    const hipError_t e = hipGetLastError();
+    return le != hipSuccess ? le : e;
+}
+
+// The plan of a launch of n candidates without a row sink, as text (hc_get_kernel_info: tests and bench.py name the measured kernel with
+// it); n == 0: the read set's forms in general.
+std::string describe_score_kernel(const StoreView& st, bool coop_fetch, int lane_group, uint32_t n_cu, uint64_t n) {
+    const uint64_t dma_min = coop_dma_min();
+    const ScorePlan p = plan_score_launch(st, coop_fetch, lane_group, n_cu, n ? n : std::max<uint64_t>(dma_min, 1), RowSinkKind::none);
+    if (!p.kernel) return "no scoring kernel for this read set";
+    const uint32_t lg = lut_lg(st.K);
+    const char* enc = st.symbytes == 2 ? "u16" : (lg >= 6 ? "wide8" : "packed8");
+    char buf[640];
+    if (!p.kernel->coop)
+        snprintf(buf, sizeof buf, "%s encoding=%s table_bytes=%u (one lane, one fetch)", p.kernel->name, enc, st.lut_bytes);
+    else if (p.kernel->depth == 0)
+        snprintf(buf, sizeof buf, "%s encoding=%s table_bytes=%u lds_bytes=%zu waves_per_cu=%u LDS-DMA fetch for launches of %llu candidates and more "
+                                  "(one workgroup per CU, the waves take their items from a ticket counter in LDS%s); smaller launches: %s",
+                 p.kernel->name, enc, st.lut_bytes, p.lds_form, p.waves_per_cu, (unsigned long long)dma_min,
+                 p.kernel->wg == kWideDmaLanes ? "; the scratch words sit in an unaddressed row of the table" : "", p.staged->name);
+    else
+        snprintf(buf, sizeof buf, "%s encoding=%s table_bytes=%u lds_bytes=%zu waves_per_cu=%u%s", p.kernel->name, enc, st.lut_bytes, p.lds_form,
+                 p.waves_per_cu, p.bucketed ? " length-bucketed (hc::bucket_perm_kernel, items by ticket)" : "");
     return buf;
 }
 
-namespace {
-template <typename SymT, int LG>
-hipError_t set_lds_limit_lg() {
-    const int kMax = 160 * 1024;  // allow the full 160 KiB of LDS for large quality alphabets
-    hipError_t e;
-    if constexpr (sizeof(SymT) == 1) {
-        if ((e = hipFuncSetAttribute((const void*)score_kernel<SymT, 4, LG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)score_kernel<SymT, 4, LG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    }
-    if ((e = hipFuncSetAttribute((const void*)score_kernel<SymT, 2, LG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)score_kernel<SymT, 2, LG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if constexpr (sizeof(SymT) == 1 && LG >= 6) {
-        if ((e = hipFuncSetAttribute((const void*)score_kernel_wide_wg<SymT, 4, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)score_kernel_wide_wg<SymT, 2, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
+hipError_t set_score_kernel_lds_limit() {  // the full 160 KiB of LDS for every scoring kernel (large quality alphabets)
+    for (const ScoreKernel& k : kScoreKernels) {
+        const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-}  // namespace
-
-hipError_t set_score_kernel_lds_limit() {
-    hipError_t e;
-    const int kMax = 160 * 1024;
-#define HC_COOP_ATTR(T_, LG_, WG_)                                                                                                                         \
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<T_, LG_, WG_, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e; \
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<T_, LG_, WG_, true, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-#define HC_COOP_ATTR_DEEP(T_, LG_) \
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<T_, LG_, 256, true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-#define HC_COOP_ATTR_DMA(LG_)                                                                                                                                          \
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, LG_, 1024, true, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e; \
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, LG_, 1024, true, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, 6, (int)kWideDmaLanes, true, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, 7, (int)kWideDmaLanes, true, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    HC_COOP_ATTR_DMA(3)
-    HC_COOP_ATTR_DMA(4)
-    HC_COOP_ATTR_DMA(5)
-    HC_COOP_ATTR(uint8_t, 3, 256)
-    HC_COOP_ATTR(uint8_t, 4, 256)
-    HC_COOP_ATTR(uint8_t, 5, 256)
-    HC_COOP_ATTR(uint8_t, 6, 1024)
-    HC_COOP_ATTR(uint8_t, 7, 1024)
-    HC_COOP_ATTR(uint16_t, 5, 256)
-    HC_COOP_ATTR(uint16_t, 5, 1024)
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, 6, 1024, true, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint8_t, 7, 1024, true, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)score_kernel_coop<uint16_t, 5, 1024, true, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMax)) != hipSuccess) return e;
-    HC_COOP_ATTR_DEEP(uint8_t, 3)
-    HC_COOP_ATTR_DEEP(uint8_t, 4)
-    HC_COOP_ATTR_DEEP(uint8_t, 5)
-    HC_COOP_ATTR_DEEP(uint16_t, 5)
-#undef HC_COOP_ATTR
-#undef HC_COOP_ATTR_DEEP
-#undef HC_COOP_ATTR_DMA
-    if ((e = set_lds_limit_lg<uint8_t, 3>()) != hipSuccess) return e;
-    if ((e = set_lds_limit_lg<uint8_t, 4>()) != hipSuccess) return e;
-    if ((e = set_lds_limit_lg<uint8_t, 5>()) != hipSuccess) return e;
-    if ((e = set_lds_limit_lg<uint8_t, 6>()) != hipSuccess) return e;
-    if ((e = set_lds_limit_lg<uint8_t, 7>()) != hipSuccess) return e;
-    return set_lds_limit_lg<uint16_t, 5>();
 }
 
 }  // namespace hc

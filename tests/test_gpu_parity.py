@@ -488,6 +488,9 @@ def test_fetch_and_descriptor_paths_agree(oracle, monkeypatch, fetch, regular, n
     with hc.EdgeScorer(st) as sc:
         sc.set_reads(reads)
         assert sc.info()["qual_alphabet"] == n_quals
+        if fetch != "coop":  # the wide 8-bit tables take 512-lane workgroups, and the report names that kernel
+            want = "hc::score_kernel_wide_wg<uint8_t, " if n_quals in (40, 60) else "hc::score_kernel<"
+            assert sc.kernel_info(m).startswith(want), sc.kernel_info(m)
     check_parity(oracle, reads, st, cand)
 
 
