@@ -64,6 +64,13 @@ class hc_graph_counts(C.Structure):
                 ("n_tied_lists", C.c_uint64), ("first_bad", C.c_int64)]
 
 
+class hc_clean_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("edges_before", "edges_after", "transitive_count", "del_count", "rebuilt", "n_tied_lists")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 _vp = C.c_void_p
 _sig = {
     "hc_version": (C.c_char_p, []),
@@ -108,6 +115,11 @@ _sig = {
     "hc_graph_append": (C.c_int, [_vp, _vp, C.c_uint64]),
     "hc_graph_resolve": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, C.POINTER(hc_graph_counts)]),
     "hc_graph_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hc_graph_size": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hc_graph_load": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp]),
+    "hc_graph_remove_inclusions": (C.c_int, [_vp, C.POINTER(hc_clean_counts)]),
+    "hc_graph_remove_transitive": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(hc_clean_counts)]),
+    "hc_graph_fetch_inclusion_edges": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hc_reset": (C.c_int, [_vp, _vp]),
     "hc_set_comm_reserve": (C.c_int, [_vp, C.c_uint32]),
     "hc_comm_gate_device": (C.c_int, [_vp, _vp, C.c_uint32]),

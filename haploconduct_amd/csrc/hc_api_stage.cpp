@@ -1,7 +1,8 @@
 // hc_api_stage.cpp — what the stage (construct_edges) needs of the device beyond plain scoring (include/hcedge.h):
 //   hc_block_*  : one block of candidates in flight — H2D of the compact records, the scoring kernel appending the
 //                 non-dropped records straight into page-locked host memory, one event to wait on;
-//   hc_graph_*  : duplicate resolution + adjacency lists on the device (kernels: hc_graph_kernels.hip).
+//   hc_graph_*  : duplicate resolution + adjacency lists on the device (kernels: hc_graph_kernels.hip), and the
+//                 cleaning of that graph: removeInclusions + removeTransitiveEdges (kernels: hc_trans_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "../../include/hcedge.h"
 #include "hc_ctx.h"
 #include "hc_graph.h"
+#include "hc_trans.h"
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
 
@@ -128,6 +130,7 @@ int hc_graph_begin(hc_ctx* c) {
     if (!c) return fail(HC_ERR_ARG, "hc_graph_begin: null context");
     c->graph.n_appended = 0;
     c->graph.valid = false;
+    c->graph.have_groups = false;
     return HC_OK;
 }
 
@@ -192,6 +195,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     HC_HIP(hipSetDevice(c->device));
     hc_ctx::Graph& g = c->graph;
     g.valid = false;
+    g.have_groups = false;
     const uint32_t m = (uint32_t)n, V = (uint32_t)n_vertices;
     hipStream_t s = c->stream;
     const size_t m1 = m ? m : 1;
@@ -312,6 +316,169 @@ int hc_graph_fetch_edges(hc_ctx* c, uint64_t first, uint64_t count, hc_edge_rec*
     HC_HIP(hipSetDevice(c->device));
     HC_HIP(hipMemcpyAsync(dst, g.edges_out.as<hc_edge_rec>() + first, count * sizeof(hc_edge_rec), hipMemcpyDeviceToHost, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
+    return HC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// graph cleaning
+static void swap_scratch(hc_scratch& a, hc_scratch& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.cap, b.cap);
+    std::swap(a.host, b.host);
+}
+
+int hc_graph_size(hc_ctx* c, uint64_t* n_vertices, uint64_t* n_edges) {
+    if (!c || !n_vertices || !n_edges) return fail(HC_ERR_ARG, "hc_graph_size: null argument");
+    if (!c->graph.valid) return fail(HC_ERR_STATE, "hc_graph_size: no graph on the device");
+    *n_vertices = c->graph.n_vertices;
+    *n_edges = c->graph.n_edges;
+    return HC_OK;
+}
+
+int hc_graph_load(hc_ctx* c, const hc_edge_rec* edges, const uint64_t* out_off, const uint32_t* in_nodes, const uint64_t* in_off,
+                  uint64_t n_vertices, uint64_t n_edges, const uint8_t* inclusions) {
+    if (!c || !out_off || !in_off || (n_edges && (!edges || !in_nodes))) return fail(HC_ERR_ARG, "hc_graph_load: null argument");
+    if (n_edges >= (1ull << 31) || n_vertices >= (1ull << 31)) return fail(HC_ERR_ARG, "hc_graph_load: more than 2^31-1 edges or vertices");
+    // the kernels index by these ids: the offsets are checked here (O(V)), the records and in-lists on the device after the copy
+    const uint64_t V = n_vertices, E = n_edges;
+    if (out_off[0] != 0 || in_off[0] != 0 || out_off[V] != E || in_off[V] != E) return fail(HC_ERR_ARG, "hc_graph_load: offsets do not span the edges");
+    for (uint64_t v = 0; v < V; v++)
+        if (out_off[v + 1] < out_off[v] || in_off[v + 1] < in_off[v]) return fail(HC_ERR_ARG, "hc_graph_load: offsets decrease");
+    HC_HIP(hipSetDevice(c->device));
+    hc_ctx::Graph& g = c->graph;
+    g.valid = false;
+    g.have_groups = false;
+    int rc;
+    const size_t E1 = E ? E : 1;
+    if ((rc = g.edges_out.ensure(E1 * sizeof(hc_edge_rec))) || (rc = g.o_out.ensure(E1 * 4)) || (rc = g.in_nodes.ensure(E1 * 4)) ||
+        (rc = g.out_off.ensure((V + 1) * 8)) || (rc = g.in_off.ensure((V + 1) * 8)) || (rc = g.incl.ensure(V + 1)) ||
+        (rc = g.clean_temp.ensure(hc::trans::temp_bytes(E, V))))
+        return rc;
+    hipStream_t s = c->stream;
+    if (E) {
+        HC_HIP(hipMemcpyAsync(g.edges_out.p, edges, E * sizeof(hc_edge_rec), hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(g.in_nodes.p, in_nodes, E * 4, hipMemcpyHostToDevice, s));
+    }
+    HC_HIP(hipMemcpyAsync(g.out_off.p, out_off, (V + 1) * 8, hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemcpyAsync(g.in_off.p, in_off, (V + 1) * 8, hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemsetAsync(g.incl.p, 0, V + 1, s));
+    if (inclusions && V) HC_HIP(hipMemcpyAsync(g.incl.p, inclusions, V, hipMemcpyHostToDevice, s));
+    const hc::trans::Graph view{g.edges_out.as<hc_edge_rec>(), g.o_out.as<uint32_t>(), g.out_off.as<unsigned long long>(), g.in_nodes.as<uint32_t>(),
+                                g.in_off.as<unsigned long long>(), (uint32_t)V, (uint32_t)E};
+    bool consistent = false;
+    HC_HIP(hc::trans::check_graph(view, &consistent, g.clean_temp.p, g.clean_temp.cap, s));
+    if (!consistent)
+        return fail(HC_ERR_ARG, "hc_graph_load: an edge lies in the wrong list or leaves the graph, or adj_in and adj_out hold different pairs");
+    g.n_vertices = V;
+    g.n_edges = E;
+    g.n_tied = 0;
+    g.valid = true;
+    return HC_OK;
+}
+
+// the *_next buffers for a graph of (at most) E edges and V vertices, the scratch, and the views of both graphs
+static int clean_prepare(hc_ctx* c, hc::trans::Graph& in, hc::trans::Graph& out) {
+    hc_ctx::Graph& g = c->graph;
+    const uint64_t E = g.n_edges, V = g.n_vertices, E1 = E ? E : 1;
+    int rc;
+    if ((rc = g.edges_next.ensure(E1 * sizeof(hc_edge_rec))) || (rc = g.seq_next.ensure(E1 * 4)) || (rc = g.in_nodes_next.ensure(E1 * 4)) ||
+        (rc = g.out_off_next.ensure((V + 1) * 8)) || (rc = g.in_off_next.ensure((V + 1) * 8)) ||
+        (rc = g.clean_temp.ensure(hc::trans::temp_bytes(E, V))))
+        return rc;
+    in = hc::trans::Graph{g.edges_out.as<hc_edge_rec>(), g.o_out.as<uint32_t>(), g.out_off.as<unsigned long long>(), g.in_nodes.as<uint32_t>(),
+                          g.in_off.as<unsigned long long>(), (uint32_t)V, (uint32_t)E};
+    out = hc::trans::Graph{g.edges_next.as<hc_edge_rec>(), g.seq_next.as<uint32_t>(), g.out_off_next.as<unsigned long long>(),
+                           g.in_nodes_next.as<uint32_t>(), g.in_off_next.as<unsigned long long>(), (uint32_t)V, 0};
+    return HC_OK;
+}
+
+static void clean_commit(hc_ctx::Graph& g, const hc::trans::Graph& out) {
+    swap_scratch(g.edges_out, g.edges_next);
+    swap_scratch(g.o_out, g.seq_next);
+    swap_scratch(g.out_off, g.out_off_next);
+    swap_scratch(g.in_nodes, g.in_nodes_next);
+    swap_scratch(g.in_off, g.in_off_next);
+    g.n_edges = out.E;
+    g.n_tied = 0;  // the lists are in the reference's order now
+}
+
+int hc_graph_remove_inclusions(hc_ctx* c, hc_clean_counts* counts) {
+    if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_inclusions: null argument");
+    memset(counts, 0, sizeof *counts);
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_inclusions: no graph on the device");
+    if (g.n_tied) return fail(HC_ERR_STATE, "hc_graph_remove_inclusions: the device holds out-lists whose order only the host knows (hc_graph_resolve's tied lists): hc_graph_load the host's lists first");
+    HC_HIP(hipSetDevice(c->device));
+    hc::trans::Graph in, out;
+    int rc = clean_prepare(c, in, out);
+    if (rc) return rc;
+    const uint64_t E1 = g.n_edges ? g.n_edges : 1;
+    if ((rc = g.incl_vtx.ensure((g.n_vertices + 1) * 4)) || (rc = g.incl_off.ensure((g.n_vertices + 1) * 8)) ||
+        (rc = g.incl_edges.ensure(2 * E1 * sizeof(hc_edge_rec))))
+        return rc;
+    g.have_groups = false;
+    if (g.n_edges == 0) {  // nothing to remove; every marked vertex has an empty group
+        std::vector<uint8_t> bits(g.n_vertices);
+        std::vector<uint32_t> vtx;
+        if (g.n_vertices) HC_HIP(hipMemcpy(bits.data(), g.incl.p, g.n_vertices, hipMemcpyDeviceToHost));
+        for (uint64_t v = 0; v < g.n_vertices; v++)
+            if (bits[v]) vtx.push_back((uint32_t)v);
+        std::vector<uint64_t> off(vtx.size() + 1, 0);
+        if (!vtx.empty()) HC_HIP(hipMemcpy(g.incl_vtx.p, vtx.data(), vtx.size() * 4, hipMemcpyHostToDevice));
+        HC_HIP(hipMemcpy(g.incl_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+        g.n_groups = vtx.size();
+        g.n_group_edges = 0;
+        g.have_groups = true;
+        counts->edges_before = counts->edges_after = 0;
+        return HC_OK;
+    }
+    const hipError_t e = hc::trans::remove_inclusions(in, g.incl.as<uint8_t>(), out, g.incl_vtx.as<uint32_t>(), g.incl_off.as<unsigned long long>(),
+                                                      g.incl_edges.as<hc_edge_rec>(), &g.n_groups, &g.n_group_edges, counts, g.clean_temp.p,
+                                                      g.clean_temp.cap, c->stream);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string("hc_graph_remove_inclusions: ") + hipGetErrorString(e));
+    }
+    clean_commit(g, out);
+    g.have_groups = true;
+    return HC_OK;
+}
+
+int hc_graph_remove_transitive(hc_ctx* c, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts) {
+    if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_transitive: null argument");
+    memset(counts, 0, sizeof *counts);
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_transitive: no graph on the device");
+    if (g.n_tied) return fail(HC_ERR_STATE, "hc_graph_remove_transitive: the device holds out-lists whose order only the host knows (hc_graph_resolve's tied lists): hc_graph_load the host's lists first");
+    counts->edges_before = counts->edges_after = g.n_edges;
+    if (remove_trans == 0 || g.n_edges == 0) return HC_OK;  // :939-941; an empty graph stays as it is
+    HC_HIP(hipSetDevice(c->device));
+    hc::trans::Graph in, out;
+    int rc = clean_prepare(c, in, out);
+    if (rc) return rc;
+    const hipError_t e = hc::trans::remove_transitive(in, out, remove_trans, branch_reduction, counts, g.clean_temp.p, g.clean_temp.cap, c->stream);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string("hc_graph_remove_transitive: ") + hipGetErrorString(e));
+    }
+    clean_commit(g, out);
+    return HC_OK;
+}
+
+int hc_graph_fetch_inclusion_edges(hc_ctx* c, uint32_t* group_vertex, uint64_t* group_off, hc_edge_rec* edges, uint64_t cap, uint64_t* n_groups,
+                                   uint64_t* n_edges) {
+    if (!c || !n_groups || !n_edges) return fail(HC_ERR_ARG, "hc_graph_fetch_inclusion_edges: null argument");
+    hc_ctx::Graph& g = c->graph;
+    if (!g.have_groups) return fail(HC_ERR_STATE, "hc_graph_fetch_inclusion_edges: hc_graph_remove_inclusions has not run on this graph");
+    *n_groups = g.n_groups;
+    *n_edges = g.n_group_edges;
+    HC_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (group_vertex && g.n_groups) HC_HIP(hipMemcpyAsync(group_vertex, g.incl_vtx.p, g.n_groups * 4, hipMemcpyDeviceToHost, s));
+    if (group_off) HC_HIP(hipMemcpyAsync(group_off, g.incl_off.p, (g.n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+    const uint64_t k = std::min(cap, g.n_group_edges);
+    if (edges && k) HC_HIP(hipMemcpyAsync(edges, g.incl_edges.p, k * sizeof(hc_edge_rec), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipStreamSynchronize(s));
     return HC_OK;
 }
 

@@ -236,6 +236,11 @@ struct hc_ctx {
     struct Graph {
         hc_scratch adm, E, key0, key1, idx0, idx1, keep, incl, tied, counters, surv, k32a, k32b, k64a, k64b, tmp_idx, o_out, o_in,
             out_off, in_off, edges_out, in_nodes, vtx, temp, tied_list;
+        // graph cleaning (hc_graph_remove_inclusions / hc_graph_remove_transitive): the cleaned graph is written into
+        // the *_next buffers, which then trade places with the current ones; the inclusion groups stay for fetching
+        hc_scratch edges_next, seq_next, out_off_next, in_nodes_next, in_off_next, clean_temp, incl_vtx, incl_off, incl_edges;
+        uint64_t n_groups = 0, n_group_edges = 0;
+        bool have_groups = false;
         uint64_t n_vertices = 0, n_edges = 0, n_tied = 0;
         uint64_t n_appended = 0;  // records hc_graph_append has put into adm
         bool valid = false;

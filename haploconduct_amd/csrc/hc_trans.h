@@ -1,0 +1,42 @@
+// hc_trans.h — launch interface of hc_trans_kernels.hip (OverlapGraph::removeInclusions + removeTransitiveEdges on the
+// device).  The one host step of the device route, std::sort's order of an out-list by target, is host/TargetOrder.h's.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/hcedge.h"
+#include "host/TargetOrder.h"
+
+namespace hc {
+
+namespace trans {
+
+// A device graph in CSR form: adj_out records back to back in vertex order (E of them, list order) with seq (one per
+// record) and out_off (V + 1); adj_in as in_nodes with in_off (V + 1).
+struct Graph {
+    hc_edge_rec* edges;
+    uint32_t* seq;
+    unsigned long long* out_off;
+    uint32_t* in_nodes;
+    unsigned long long* in_off;
+    uint32_t V, E;
+};
+
+// Scratch of one call for E edges and V vertices.
+size_t temp_bytes(uint64_t E, uint64_t V);
+
+// hc_graph_load's checks on the device: every record lies in the list of its vertex1, every id < V, adj_in holds the
+// same (source, target) pairs as adj_out.  The offsets must already span [0, E] without decreasing (the caller checks).
+// Writes g.seq = 0, 1, ...
+hipError_t check_graph(const Graph& g, bool* consistent, void* temp, size_t temp_bytes, hipStream_t s);
+// removeTransitiveEdges from `in` into `out` (distinct buffers, room for in.E edges; out.E is set).  Synchronous on s:
+// the host takes part twice (the lists std::sort orders differently from a stable sort, and the branch choice).
+hipError_t remove_transitive(const Graph& in, Graph& out, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts, void* temp,
+                             size_t temp_bytes, hipStream_t s);
+// removeInclusions from `in` into `out`; the groups: group_vertex (room for V), group_off (V + 1), group_edges (2 E).
+hipError_t remove_inclusions(const Graph& in, const uint8_t* inclusions, Graph& out, uint32_t* group_vertex, unsigned long long* group_off,
+                             hc_edge_rec* group_edges, uint64_t* n_groups, uint64_t* n_group_edges, hc_clean_counts* counts, void* temp,
+                             size_t temp_bytes, hipStream_t s);
+
+}  // namespace trans
+}  // namespace hc

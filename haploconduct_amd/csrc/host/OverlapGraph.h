@@ -124,6 +124,11 @@ public:
     void sort_out_list(node_id_t v, const uint32_t* len_by_read);  // sortEdges' treatment of one out-list (:724-749)
     void rebuild_in_lists(unsigned n_threads);                     // adj_in from the out-lists, :751-762
     Edge removeEdge(node_id_t v, node_id_t w);                                                // :102-146
+    Edge* getEdgeInfo(node_id_t v, node_id_t w);                                              // :262-284, reverse not allowed
+    // src/GraphAlgos.cpp:20-48: the groups go to inclusion_edges
+    void removeInclusions(hc_clean_counts* counts = nullptr);
+    // src/GraphAlgos.cpp:938-1077 (with :746-833) for remove_trans / branch_reduction as given
+    void removeTransitiveEdges(unsigned remove_trans, bool branch_reduction, hc_clean_counts* counts = nullptr);
     double checkEdge(node_id_t v, node_id_t w, bool reverse_allowed) const;                   // :233-259
     // :608-719 (--add_duplicates; called at the end of construct_edges, EdgeCalculator.cpp:650-652): every edge once more
     // between the vertices of the reverse-complemented reads.  The mirrored edges carry no reverse offsets and no
@@ -149,6 +154,7 @@ public:
     std::vector<ArenaList<Edge>> adj_out;
     std::vector<ArenaList<node_id_t>> adj_in;
     std::vector<uint8_t> inclusions;                      // boost::dynamic_bitset in the reference
+    std::vector<std::vector<Edge>> inclusion_edges;       // removeInclusions' groups (for FNO1)
 
 private:
     void ensure_slots() const;  // after adopt_csr the index is built lazily

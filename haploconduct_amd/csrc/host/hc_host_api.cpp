@@ -437,6 +437,34 @@ int hc_host_graph_get(hc_host_graph* g, hc_edge_rec* out, uint64_t cap, uint64_t
     return HC_OK;
 }
 
+int hc_host_graph_remove_inclusions(hc_host_graph* g) {
+    if (!g) return set_last_error(HC_ERR_ARG, "hc_host_graph_remove_inclusions: null");
+    return guarded("removeInclusions", [&] { g->graph->removeInclusions(); });
+}
+
+int hc_host_graph_remove_transitive_edges(hc_host_graph* g, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts) {
+    if (!g) return set_last_error(HC_ERR_ARG, "hc_host_graph_remove_transitive_edges: null");
+    return guarded("removeTransitiveEdges", [&] { g->graph->removeTransitiveEdges(remove_trans, branch_reduction != 0, counts); });
+}
+
+int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t off_cap, hc_edge_rec* edges, uint64_t cap, uint64_t* n_groups,
+                                      uint64_t* n_out) {
+    if (!g || !n_groups || !n_out) return set_last_error(HC_ERR_ARG, "hc_host_graph_get_inclusion_edges: null");
+    const auto& groups = g->graph->inclusion_edges;
+    uint64_t n = 0;
+    for (size_t k = 0; k < groups.size(); k++) {
+        if (off && k < off_cap) off[k] = n;
+        for (const Edge& e : groups[k]) {
+            if (edges && n < cap) fill_edge_rec(e, edges[n]);
+            n++;
+        }
+    }
+    if (off && groups.size() < off_cap) off[groups.size()] = n;
+    *n_groups = groups.size();
+    *n_out = n;
+    return HC_OK;
+}
+
 int hc_host_graph_free(hc_host_graph* g) {
     delete g;
     return HC_OK;

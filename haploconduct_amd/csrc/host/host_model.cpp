@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <array>
+#include <climits>
+#include <set>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +24,7 @@
 #include "FastqStorage.h"
 #include "Overlap.h"
 #include "OverlapGraph.h"
+#include "TargetOrder.h"
 
 namespace hc {
 
@@ -1307,6 +1310,189 @@ void resolve_admitted_edges(OverlapGraph& g, const ProgramSettings& ps, Edge* ad
     lap("survivor list");
     g.bulk_add_edges(admitted, survivors, (unsigned)ps.n_threads);
     lap("bulk fill");
+}
+
+// ---- graph cleaning (src/GraphAlgos.cpp:20-48, 746-833, 938-1077) --------------------------------------------------
+
+Edge* OverlapGraph::getEdgeInfo(node_id_t v, node_id_t w) {  // src/OverlapGraph.cpp:262-284 with reverse_allowed = false
+    for (Edge& e : adj_out.at(v))
+        if (e.get_vertex(2) == w) return &e;
+    throw FatalError{HC_ERR_STATE, "getEdgeInfo: edge not found"};
+}
+
+void OverlapGraph::removeInclusions(hc_clean_counts* counts) {  // :20-48
+    const unsigned int before = edge_count;
+    std::set<std::pair<node_id_t, node_id_t>> edges_to_remove;
+    for (node_id_t v = 0; v < adj_out.size(); v++) {
+        if (!inclusions[v]) continue;
+        std::vector<Edge> group;
+        for (const Edge& e : adj_out[v]) {
+            edges_to_remove.insert(std::make_pair(v, e.get_vertex(2)));
+            group.push_back(e);
+        }
+        for (node_id_t x : adj_in[v]) {
+            edges_to_remove.insert(std::make_pair(x, v));
+            group.push_back(*getEdgeInfo(x, v));
+        }
+        inclusion_edges.push_back(std::move(group));
+    }
+    for (const auto& p : edges_to_remove) removeEdge(p.first, p.second);
+    if (counts) {
+        memset(counts, 0, sizeof *counts);
+        counts->edges_before = before;
+        counts->edges_after = edge_count;
+        counts->del_count = edges_to_remove.size();
+    }
+}
+
+namespace {
+// adjacency of a (sub)graph as sorted lists: out[u] targets ascending, in[w] sources ascending (repeats kept)
+struct SortedLists {
+    std::vector<uint64_t> out_off, in_off;
+    std::vector<uint32_t> out, in;
+};
+
+bool nonempty_intersect(const uint32_t* a, const uint32_t* ae, const uint32_t* b, const uint32_t* be) {  // :779-795
+    while (a != ae && b != be) {
+        if (*a == *b) return true;
+        if (*a < *b) a++;
+        else b++;
+    }
+    return false;
+}
+
+// findTransEdges (:746-777) with removeTrans = false: for every edge (in out-list order) whether out(u) and in(w) meet
+std::vector<uint8_t> find_trans_edges(const SortedLists& L) {
+    const size_t V = L.out_off.size() - 1;
+    std::vector<uint8_t> t(L.out.size(), 0);
+    for (size_t u = 0; u < V; u++)
+        for (uint64_t i = L.out_off[u]; i < L.out_off[u + 1]; i++) {
+            const uint32_t w = L.out[i];
+            t[i] = nonempty_intersect(L.out.data() + L.out_off[u], L.out.data() + L.out_off[u + 1], L.in.data() + L.in_off[w],
+                                      L.in.data() + L.in_off[w + 1]);
+        }
+    return t;
+}
+
+// the lists of the edges (src[i], tgt[i]), given in (source, target) order
+SortedLists lists_of(const std::vector<uint32_t>& src, const std::vector<uint32_t>& tgt, size_t V) {
+    SortedLists L;
+    L.out_off.assign(V + 1, 0);
+    L.in_off.assign(V + 1, 0);
+    for (size_t i = 0; i < src.size(); i++) L.out_off[src[i] + 1]++, L.in_off[tgt[i] + 1]++;
+    for (size_t v = 0; v < V; v++) L.out_off[v + 1] += L.out_off[v], L.in_off[v + 1] += L.in_off[v];
+    L.out = tgt;
+    L.in.resize(src.size());
+    std::vector<uint64_t> at(L.in_off.begin(), L.in_off.end() - 1);
+    for (size_t i = 0; i < src.size(); i++) L.in[at[tgt[i]]++] = src[i];  // sources ascending: the edges come in source order
+    return L;
+}
+}  // namespace
+
+void OverlapGraph::removeTransitiveEdges(unsigned remove_trans, bool branch_reduction, hc_clean_counts* counts) {  // :938-1077
+    if (counts) {
+        memset(counts, 0, sizeof *counts);
+        counts->edges_before = counts->edges_after = edge_count;
+    }
+    if (remove_trans == 0) return;
+    const size_t V = adj_out.size();
+    // sortAdjOut (:806-833): adj_out becomes its target-sorted form, by std::sort
+    uint64_t n_tied = 0;
+    std::vector<uint32_t> targets, perm;
+    std::vector<Edge> tmp;
+    for (size_t v = 0; v < V; v++) {
+        ArenaList<Edge>& Lv = adj_out[v];
+        const size_t n = Lv.size();
+        targets.resize(n);
+        perm.resize(n);
+        for (size_t k = 0; k < n; k++) targets[k] = (uint32_t)Lv[k].get_vertex(2);
+        target_sort_perm(targets.data(), n, perm.data());
+        tmp.assign(Lv.begin(), Lv.end());
+        bool repeated = false;
+        for (size_t k = 0; k < n; k++) {
+            Lv[k] = tmp[perm[k]];
+            if (k && targets[perm[k]] == targets[perm[k - 1]]) repeated = true;
+        }
+        if (repeated && n > 16) n_tied++;
+    }
+    // level 0: every edge in (source, target) order; sortAdjLists(adj_in) holds the same pairs as the out-lists
+    std::vector<uint32_t> src, tgt, pos;
+    for (size_t v = 0; v < V; v++)
+        for (const Edge& e : adj_out[v]) src.push_back((uint32_t)v), tgt.push_back((uint32_t)e.get_vertex(2));
+    const size_t E = src.size();
+    pos.resize(E);
+    for (size_t i = 0; i < E; i++) pos[i] = (uint32_t)i;
+    std::vector<uint32_t> lsrc = src, ltgt = tgt;
+    for (unsigned pass = 0; pass < remove_trans; pass++) {  // T_1, then T_2 on T_1, ... (:958-966)
+        const std::vector<uint8_t> t = find_trans_edges(lists_of(lsrc, ltgt, V));
+        std::vector<uint32_t> s2, t2, p2;
+        for (size_t i = 0; i < t.size(); i++)
+            if (t[i]) s2.push_back(lsrc[i]), t2.push_back(ltgt[i]), p2.push_back(pos[i]);
+        lsrc.swap(s2), ltgt.swap(t2), pos.swap(p2);
+    }
+    const uint64_t transitive_count = pos.size();
+    std::vector<uint8_t> in_t(E, 0);
+    for (uint32_t p : pos) in_t[p] = 1;
+    // first[i]: the position of the first edge of i's pair in the target-sorted out-list (getEdgeInfo's answer)
+    std::vector<uint64_t> off(V + 1, 0);
+    for (size_t v = 0; v < V; v++) off[v + 1] = off[v] + adj_out[v].size();
+    std::vector<uint64_t> first(E);
+    for (size_t i = 0; i < E; i++) first[i] = (i > off[src[i]] && tgt[i - 1] == tgt[i]) ? first[i - 1] : i;
+    auto len_at = [&](uint64_t i) { return adj_out[src[i]][i - off[src[i]]].get_len(0); };
+    // branch reduction (:968-993): (u, v) for every out-edge of u with len0 <= ovlen, (x, w) for every in-neighbour x of w whose
+    // first x -> w edge has len0 <= ovlen — per vertex, the largest ovlen of its transitive out- / in-edges decides
+    std::vector<uint8_t> in_d(E, 0);
+    if (remove_trans == 1 && branch_reduction) {
+        std::vector<int> max_out(V, INT_MIN), max_in(V, INT_MIN);
+        for (uint32_t p : pos) {
+            const int ov = len_at(first[p]);
+            max_out[src[p]] = std::max(max_out[src[p]], ov);
+            max_in[tgt[p]] = std::max(max_in[tgt[p]], ov);
+        }
+        std::vector<uint8_t> pair_d(E, 0);
+        for (size_t i = 0; i < E; i++)
+            if (len_at(i) <= max_out[src[i]] || len_at(first[i]) <= max_in[tgt[i]]) pair_d[first[i]] = 1;
+        for (size_t i = 0; i < E; i++) in_d[i] = pair_d[first[i]];
+    }
+    uint64_t del_count = 0;
+    const bool rebuild = 1.0 * transitive_count > 0.5 * edge_count;
+    if (rebuild) {  // :995-1054: new lists without T_k and without every edge of a pair in D; adj_in in vertex order
+        for (size_t v = 0; v < V; v++) {
+            ArenaList<Edge>& Lv = adj_out[v];
+            size_t k = 0;
+            for (uint64_t i = off[v]; i < off[v + 1]; i++) {
+                if (in_t[i]) continue;
+                if (in_d[i]) {
+                    del_count++;
+                    continue;
+                }
+                Lv[k++] = Lv[i - off[v]];
+            }
+            while (Lv.size() > k) Lv.erase(Lv.end() - 1);
+        }
+        for (size_t v = 0; v < V; v++) adj_in[v].clear();
+        for (size_t v = 0; v < V; v++)
+            for (const Edge& e : adj_out[v]) adj_in[e.get_vertex(2)].push_back((node_id_t)v);
+        edge_count = edge_count - (unsigned int)transitive_count - (unsigned int)del_count;
+        slots_valid = false;
+    } else {  // :1055-1077: removeEdge for every T_k entry, then once for every pair of D that still has an edge
+        for (size_t i = 0; i < pos.size(); i++) removeEdge(lsrc[i], ltgt[i]);
+        std::set<std::pair<uint32_t, uint32_t>> d;
+        for (size_t i = 0; i < E; i++)
+            if (in_d[i]) d.insert(std::make_pair(src[i], tgt[i]));
+        for (const auto& p : d)
+            if (checkEdge(p.first, p.second, false) >= 0) {
+                removeEdge(p.first, p.second);
+                del_count++;
+            }
+    }
+    if (counts) {
+        counts->edges_after = edge_count;
+        counts->transitive_count = transitive_count;
+        counts->del_count = del_count;
+        counts->rebuilt = rebuild ? 1 : 0;
+        counts->n_tied_lists = n_tied;
+    }
 }
 
 }  // namespace hc

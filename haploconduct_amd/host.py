@@ -87,6 +87,9 @@ _sig = {
     "hc_ec_get_in_lists": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "hc_host_graph_get": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp, C.POINTER(hc_ec_counters)]),
     "hc_host_graph_free": (C.c_int, [_vp]),
+    "hc_host_graph_remove_inclusions": (C.c_int, [_vp]),
+    "hc_host_graph_remove_transitive_edges": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(N.hc_clean_counts)]),
+    "hc_host_graph_get_inclusion_edges": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(N.lib, _name)
@@ -254,6 +257,27 @@ class HostGraph:
         nodes = np.zeros(max(n_edges, 1), np.uint64)
         N.check(N.lib.hc_host_graph_get_in_lists(self._h, off.ctypes.data, nodes.ctypes.data, n_edges), "hc_host_graph_get_in_lists")
         return off, nodes[:n_edges]
+
+    def remove_inclusions(self):
+        """OverlapGraph::removeInclusions (src/GraphAlgos.cpp:20-48); the groups: inclusion_edges()."""
+        N.check(N.lib.hc_host_graph_remove_inclusions(self._h), "hc_host_graph_remove_inclusions")
+
+    def remove_transitive_edges(self, remove_trans, branch_reduction=False):
+        """OverlapGraph::removeTransitiveEdges (src/GraphAlgos.cpp:938-1077); returns the hc_clean_counts as a dict."""
+        c = N.hc_clean_counts()
+        N.check(N.lib.hc_host_graph_remove_transitive_edges(self._h, remove_trans, 1 if branch_reduction else 0, C.byref(c)),
+                "hc_host_graph_remove_transitive_edges")
+        return c.as_dict()
+
+    def inclusion_edges(self):
+        """OverlapGraph::inclusion_edges (every removeInclusions call so far): (group offsets, records)."""
+        ng, n = C.c_uint64(), C.c_uint64()
+        N.check(N.lib.hc_host_graph_get_inclusion_edges(self._h, None, 0, None, 0, C.byref(ng), C.byref(n)), "hc_host_graph_get_inclusion_edges")
+        off = np.zeros(ng.value + 1, np.uint64)
+        out = np.zeros(n.value, dtype=EDGE_DTYPE)
+        N.check(N.lib.hc_host_graph_get_inclusion_edges(self._h, off.ctypes.data, off.size, out.ctypes.data if out.size else None, out.size,
+                                                        C.byref(ng), C.byref(n)), "hc_host_graph_get_inclusion_edges")
+        return off, out
 
     def get(self):
         n = C.c_uint64()

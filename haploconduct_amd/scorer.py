@@ -257,6 +257,59 @@ class EdgeScorer:
         res.update(edges=edges, out_off=out_off, in_nodes=in_nodes, in_off=in_off, seq=seq, inclusions=incl, tied_vertices=tied)
         return res
 
+    def graph_load(self, edges, out_off, in_nodes, in_off, inclusions=None):
+        """hc_graph_load: a caller's CSR graph (adj_out records, adj_in) onto the device in place of the resolved one."""
+        from .host import EDGE_DTYPE
+
+        e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+        oo, io = np.ascontiguousarray(out_off, np.uint64), np.ascontiguousarray(in_off, np.uint64)
+        inn = np.ascontiguousarray(in_nodes, np.uint32)
+        inc = None if inclusions is None else np.ascontiguousarray(inclusions, np.uint8)
+        N.check(N.lib.hc_graph_load(self._ctx, _ptr(e), _ptr(oo), _ptr(inn), _ptr(io), oo.size - 1, e.shape[0],
+                                    None if inc is None else _ptr(inc)), "hc_graph_load")
+
+    def graph_remove_inclusions(self):
+        """hc_graph_remove_inclusions: OverlapGraph::removeInclusions on the device graph; returns the counts."""
+        c = N.hc_clean_counts()
+        N.check(N.lib.hc_graph_remove_inclusions(self._ctx, C.byref(c)), "hc_graph_remove_inclusions")
+        return c.as_dict()
+
+    def graph_remove_transitive(self, remove_trans, branch_reduction=False):
+        """hc_graph_remove_transitive: OverlapGraph::removeTransitiveEdges on the device graph; returns the counts."""
+        c = N.hc_clean_counts()
+        N.check(N.lib.hc_graph_remove_transitive(self._ctx, remove_trans, 1 if branch_reduction else 0, C.byref(c)),
+                "hc_graph_remove_transitive")
+        return c.as_dict()
+
+    def graph_inclusion_edges(self):
+        """hc_graph_fetch_inclusion_edges: (group vertices, group offsets, records) of the last removeInclusions."""
+        from .host import EDGE_DTYPE
+
+        ng, ne = C.c_uint64(), C.c_uint64()
+        N.check(N.lib.hc_graph_fetch_inclusion_edges(self._ctx, None, None, None, 0, C.byref(ng), C.byref(ne)), "hc_graph_fetch_inclusion_edges")
+        gv, off = np.zeros(ng.value, np.uint32), np.zeros(ng.value + 1, np.uint64)
+        out = np.zeros(ne.value, EDGE_DTYPE)
+        N.check(N.lib.hc_graph_fetch_inclusion_edges(self._ctx, _ptr(gv) if gv.size else None, _ptr(off), _ptr(out) if out.size else None,
+                                                     ne.value, C.byref(ng), C.byref(ne)), "hc_graph_fetch_inclusion_edges")
+        return gv, off, out
+
+    def graph_fetch(self):
+        """hc_graph_fetch of the graph the device holds: edges, out_off, in_nodes, in_off, seq, inclusions."""
+        from .host import EDGE_DTYPE
+
+        V, E = self._graph_size()
+        edges = np.zeros(E, EDGE_DTYPE)
+        out_off, in_off = np.zeros(V + 1, np.uint64), np.zeros(V + 1, np.uint64)
+        in_nodes, seq, incl = np.zeros(E, np.uint32), np.zeros(E, np.uint32), np.zeros(V, np.uint8)
+        N.check(N.lib.hc_graph_fetch(self._ctx, _ptr(edges) if E else None, _ptr(out_off), _ptr(in_nodes) if E else None, _ptr(in_off),
+                                     _ptr(seq) if E else None, _ptr(incl) if V else None, None), "hc_graph_fetch")
+        return dict(edges=edges, out_off=out_off, in_nodes=in_nodes, in_off=in_off, seq=seq, inclusions=incl)
+
+    def _graph_size(self):
+        V, E = C.c_uint64(), C.c_uint64()
+        N.check(N.lib.hc_graph_size(self._ctx, C.byref(V), C.byref(E)), "hc_graph_size")
+        return int(V.value), int(E.value)
+
     def score_batch_compact(self, overlaps):
         """hc_score_batch_compact: (indices, records) of the non-DROP candidates only."""
         ov = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)

@@ -541,6 +541,42 @@ int hc_graph_fetch(hc_ctx* ctx, hc_edge_rec* edges, uint64_t* out_off, uint32_t*
  * threads turn the pieces that have arrived into the graph's lists. */
 int hc_graph_fetch_edges(hc_ctx* ctx, uint64_t first, uint64_t count, hc_edge_rec* dst);
 
+/* ---- graph cleaning on the device: OverlapGraph::removeInclusions + removeTransitiveEdges -----------------------
+ * (src/GraphAlgos.cpp:20-48, 746-833, 938-1077) on the graph the context holds: the one hc_graph_resolve left, or one a
+ * caller put there with hc_graph_load.  A graph hc_graph_resolve left with tied lists (counts.n_tied_lists > 0: their order
+ * is std::sort's, which only the host restores) is refused with HC_ERR_STATE: hc_graph_load the host's lists instead.  Afterwards hc_graph_fetch / hc_graph_fetch_edges return the cleaned graph: adj_out
+ * in the reference's list order (target order, std::sort's order in lists with repeated targets), adj_in as the branch the
+ * reference took leaves it; seq follows the records.  hc_graph_fetch reports no tied lists afterwards (their order is settled).
+ * These calls clean what they are given: whether the reference would have re-labelled the graph first
+ * (vertexLabellingHeuristic) is the caller's question. */
+typedef struct hc_clean_counts {
+    uint64_t edges_before, edges_after; /* OverlapGraph::edge_count before and after the call                       */
+    uint64_t transitive_count;          /* |T_k|, the edges of the last findTransEdges pass                          */
+    uint64_t del_count;                 /* branch-reduction deletions; removeInclusions: pairs removed                */
+    uint64_t rebuilt;                   /* 1: the rebuild branch (transitive_count > 0.5 edge_count), 0: removeEdge   */
+    uint64_t n_tied_lists;              /* out-lists of more than 16 entries with a repeated target: their order is
+                                           std::sort's, re-sorted on the host over the same input order              */
+} hc_clean_counts;
+/* A caller's graph onto the device (replacing the resolved one): edges = adj_out back to back in vertex order,
+ * out_off / in_off: n_vertices + 1 offsets, in_nodes: adj_in, inclusions: n_vertices bytes or NULL (none).  Every vertex id
+ * < n_vertices < 2^31, n_edges < 2^31, every record in the list of its vertex1, adj_in holding the same (source, target)
+ * pairs as adj_out: the offsets are checked on the host, the rest on the device after the copy (HC_ERR_ARG, no graph
+ * left).  Repeated pairs are allowed, any number of copies.  seq becomes 0, 1, ... */
+int hc_graph_load(hc_ctx* ctx, const hc_edge_rec* edges, const uint64_t* out_off, const uint32_t* in_nodes, const uint64_t* in_off,
+                  uint64_t n_vertices, uint64_t n_edges, const uint8_t* inclusions);
+/* Vertices and edges of the graph the context holds (HC_ERR_STATE when there is none). */
+int hc_graph_size(hc_ctx* ctx, uint64_t* n_vertices, uint64_t* n_edges);
+/* removeInclusions: one group per vertex marked in inclusions (ascending): its out-edges in list order, then for every
+ * in-neighbour x in list order the first x -> v edge; then every such pair loses its first edge.  counts: edges before /
+ * after, del_count = pairs removed.  The groups stay on the device for hc_graph_fetch_inclusion_edges. */
+int hc_graph_remove_inclusions(hc_ctx* ctx, hc_clean_counts* counts);
+/* removeTransitiveEdges with program_settings.remove_trans / branch_reduction as given (remove_trans 0: nothing happens). */
+int hc_graph_remove_transitive(hc_ctx* ctx, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts);
+/* OverlapGraph::inclusion_edges of the last hc_graph_remove_inclusions: group_vertex (n_groups ids), group_off (n_groups + 1),
+ * edges (room for cap records).  Any output may be NULL; *n_groups / *n_edges are always set. */
+int hc_graph_fetch_inclusion_edges(hc_ctx* ctx, uint32_t* group_vertex, uint64_t* group_off, hc_edge_rec* edges, uint64_t cap,
+                                   uint64_t* n_groups, uint64_t* n_edges);
+
 /* PCI bus id of a device ("0000:c1:00.0"), for callers that place the host threads feeding it on its NUMA node
  * (/sys/bus/pci/devices/<id>/numa_node); the stage does (HC_NUMA=0 turns that off). */
 int hc_device_bus_id(int32_t device, char* bus_id, uint32_t cap);

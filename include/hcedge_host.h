@@ -196,6 +196,17 @@ int hc_host_graph_get(hc_host_graph* g, hc_edge_rec* out, uint64_t cap, uint64_t
 /* OverlapGraph::sortEdges on the bare graph; len_by_read[r] = Read::get_len() of read r (n_reads = n_vertices). */
 int hc_host_graph_sort_edges(hc_host_graph* g, const uint32_t* len_by_read, uint64_t n_reads);
 int hc_host_graph_get_in_lists(hc_host_graph* g, uint64_t* in_off, uint64_t* in_nodes, uint64_t cap);
+/* OverlapGraph::removeInclusions (src/GraphAlgos.cpp:20-48) on the bare graph; the groups: hc_host_graph_get_inclusion_edges. */
+int hc_host_graph_remove_inclusions(hc_host_graph* g);
+/* OverlapGraph::removeTransitiveEdges (src/GraphAlgos.cpp:938-1077) with remove_trans / branch_reduction as given;
+ * counts (hc_clean_counts, include/hcedge.h) may be NULL. */
+int hc_host_graph_remove_transitive_edges(hc_host_graph* g, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts);
+/* OverlapGraph::inclusion_edges: group k holds records [off[k], off[k + 1]).  Like the reference's member, the groups of
+ * every removeInclusions call so far, in call order.  off: room for off_cap entries (n_groups + 1 are written when there
+ * is room), edges: room for cap records; *n_groups and *n_out (records) are always set, so a first call with NULL
+ * buffers sizes them. */
+int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t off_cap, hc_edge_rec* edges, uint64_t cap, uint64_t* n_groups,
+                                      uint64_t* n_out);
 int hc_host_graph_free(hc_host_graph* g);
 
 #ifdef __cplusplus
