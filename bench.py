@@ -42,6 +42,11 @@ N > 1 adds "ranks": per rank kernel_ms, step_ms, gather_ms (the exchange alone: 
 `n_ranks_seen` = the world size RCCL reported (the run fails if it is not N); the other scaling mode under its name ("weak": every rank
 its own set), so one driver pass yields both curves; "gather_modes": both forms of the exchange.
 "summary" (last key): the line's figures once more, compact.
+
+Everything above but the contract fields, "config" and the summary needs --full (off by default): "roofline", "parity", "stage_*",
+"cpu_baseline", "also", and at N > 1 the other scaling mode and the per-rank kernel times.  A plain run sets up, warms up, times the
+steps, writes --dump-outputs and prints the line; it builds the headline's candidate records on the device (paired_candidates_device).
+At N > 1 a plain run still times every form of the exchange it is given (--gather): `value` is the fastest of them.
 """
 import argparse
 import ctypes
@@ -216,14 +221,61 @@ def cached_candidates(key, make):
     return cand
 
 
-def build_workload(workload, rank, keep=False):
+def paired_candidates_device(meta, n_candidates, seed, min_len=75, max_window=100000):
+    """synth.paired_candidates(meta, n_candidates, min_len, seed, max_window) of untrimmed pairs as the hc_cand_rec records
+    EdgeScorer.pack_cands makes of it, bit for bit, in an int32 [n, 4] device tensor.  The window walk and the seeded draw are the host's;
+    the sorts, gathers and packing run on the device: on the host, the stable argsort of 10^8 keys and the record assembly took most of a
+    minute.  Every pair of reads is met once, at one distance in start order, so the sfo keys are unique and any sort orders them as the
+    host's does.  tests/test_gpu_bench_records.py and tests/test_gpu_c3.py keep it equal to the host's records."""
+    import torch
+
+    s, e, flipped, rl = meta["s"], meta["e"], meta["flipped"], meta["read_len"]
+    order = np.argsort(s, kind="stable").astype(np.int32)
+    ss, ee = s[order].astype(np.int32), e[order].astype(np.int32)
+    maxd = rl - min_len
+    out_i, out_j, out_p1, out_d2 = [], [], [], []
+    for k in range(1, min(ss.size, max_window)):
+        ds = ss[k:] - ss[:-k]
+        m = ds <= maxd
+        if not m.any():
+            break
+        d2 = ee[k:] - ee[:-k]
+        m &= np.abs(d2) <= maxd
+        idx = np.nonzero(m)[0]
+        out_i.append(order[idx])
+        out_j.append(order[idx + k])
+        out_p1.append(ds[idx].astype(np.int16))
+        out_d2.append(d2[idx].astype(np.int16))
+    dev = torch.device("cuda")
+    i, j, p1, d2 = (torch.from_numpy(np.concatenate(x)).to(dev).int() for x in (out_i, out_j, out_p1, out_d2))
+    del out_i, out_j, out_p1, out_d2
+    if i.numel() < n_candidates:
+        raise ValueError(f"only {i.numel()} candidates exist, {n_candidates} requested: lower genome_len")
+    if i.numel() > n_candidates:
+        pick = np.random.default_rng(seed).choice(i.numel(), n_candidates, replace=False)
+        keep = torch.zeros(i.numel(), dtype=torch.bool, device=dev)
+        keep[torch.from_numpy(pick).to(dev)] = True
+        del pick
+        i, j, p1, d2 = i[keep], j[keep], p1[keep], d2[keep]  # in index order, as the host's sorted pick
+        del keep
+    o = torch.argsort((torch.minimum(i, j).long() << 32) | torch.maximum(i, j).long(), stable=True)
+    i, j, p1, d2 = i[o], j[o], p1[o], d2[o]
+    del o
+    fl = torch.from_numpy(flipped).to(dev)
+    # hc_pack_cands: pos1 | ori1 << 28 | ori2 << 29 | ord code << 30 ('1' -> 1, '2' -> 2); |pos| <= read_len - min_len needs no clamp
+    bits = p1 | torch.where(fl[i.long()], 0, 1 << 28) | torch.where(fl[j.long()], 0, 1 << 29) | torch.where(d2 >= 0, 1 << 30, -(1 << 31))
+    return torch.stack([i, j, bits.int(), d2.abs()], dim=1)
+
+
+def build_workload(workload, rank, keep=False, on_device=False):
     """BASELINE.json configs; candidates in sfo2overlaps order.  keep: remember the (one) latest workload built, so that
-    a second leg over the same candidates does not generate them again."""
+    a second leg over the same candidates does not generate them again.  on_device: the candidates as the hc_cand_rec records a step
+    reads, in an int32 [n, 4] device tensor, instead of host hc_overlap_rec records."""
     if keep:
-        if (workload, rank) not in _WORKLOADS:
+        if (workload, rank, on_device) not in _WORKLOADS:
             _WORKLOADS.clear()
-            _WORKLOADS[(workload, rank)] = build_workload(workload, rank)
-        return _WORKLOADS[(workload, rank)]
+            _WORKLOADS[(workload, rank, on_device)] = build_workload(workload, rank, on_device=on_device)
+        return _WORKLOADS[(workload, rank, on_device)]
     from haploconduct_amd import synth
     import haploconduct_amd as hc
 
@@ -256,9 +308,12 @@ def build_workload(workload, rank, keep=False):
                 quals = (np.arange(1, nq + 1) + 33).astype(np.uint8)
                 qdesc = f"{nq} quality values, uniform i.i.d."
         reads, meta = synth.make_paired_dataset(n_pairs, glen, seed=1, quals=quals, qual_p=qual_p)
-        cand = cached_candidates(("paired", n_pairs, glen, n_cand, 2 + rank), lambda: synth.paired_candidates(meta, n_candidates=n_cand, seed=2 + rank))
+        if on_device:
+            cand = paired_candidates_device(meta, n_cand, seed=2 + rank)
+        else:
+            cand = cached_candidates(("paired", n_pairs, glen, n_cand, 2 + rank), lambda: synth.paired_candidates(meta, n_candidates=n_cand, seed=2 + rank))
         desc = f"{workload}: {n_pairs} synthetic 2x150 bp read pairs, {qdesc}, {n_cand} p-p candidates per GPU"
-        cfg = {"read_pairs": n_pairs, "genome_len": glen, "quality_alphabet": int(np.unique(reads.quals).size)}
+        cfg = {"read_pairs": n_pairs, "genome_len": glen, "quality_alphabet": int(np.count_nonzero(np.bincount(reads.quals, minlength=256)))}
     elif workload == "c4":
         # POLYTE diploid 20x per haplotype, 2x250 bp, every read a single (polyte.py:283-288), both orientations,
         # edge_threshold 1 / merge_contigs 0 (polyte.py:617-626), 35 distinct quality values as in polyte/example
@@ -317,7 +372,11 @@ def build_workload(workload, rank, keep=False):
         cfg = {"reads": n_reads, "genome_len": glen}
     else:
         raise SystemExit(f"unknown workload {workload}")
-    cfg = dict(cfg, workload=desc, candidates_per_gpu=int(cand.size))
+    if on_device and not pw:
+        import torch
+
+        cand = torch.from_numpy(hc.EdgeScorer.pack_cands(cand).view(np.int32).reshape(-1, 4)).cuda()
+    cfg = dict(cfg, workload=desc, candidates_per_gpu=len(cand))
     return reads, cand, cfg, hc.Settings(**st)
 
 
@@ -593,7 +652,8 @@ def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, 
     # exchange is gated on the scoring kernel having taken its CUs): the scoring kernel otherwise holds a workgroup on EVERY CU for its whole
     # duration and a collective's kernels cannot share a CU with one (profiles/r05_coresident.json)
     reserve_cus = max(0, args.reserve_cus) if with_gather else 0
-    reads, cand, cfg, settings = build_workload(workload, 0 if strong else rank, keep=world > 1)
+    on_device = not args.full and order == "sfo"  # only --full needs the host's records (parity, stage, baselines)
+    reads, cand, cfg, settings = build_workload(workload, 0 if strong else rank, keep=world > 1, on_device=on_device)
     cfg = dict(cfg)
     if world > 1 and dist.get_world_size() != world:  # the collective library must have seen every rank: never report N ranks on fewer
         raise SystemExit(f"bench.py: --gpus {world} but the process group has {dist.get_world_size()} ranks")
@@ -604,25 +664,29 @@ def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, 
         cand = cand[np.argsort(cand["read1"], kind="stable")]
     elif order == "shuffled":
         cand = cand[np.random.default_rng(5).permutation(cand.size)]
-    n_job = int(cand.size) * (1 if strong else world)  # candidates one step scores over all ranks
+    n_job = len(cand) * (1 if strong else world)  # candidates one step scores over all ranks
     if strong:  # the one candidate set split over the ranks: contiguous, order-preserving shards
-        lo, hi = parallel.shard_range(int(cand.size), rank, world)
+        lo, hi = parallel.shard_range(len(cand), rank, world)
         cand, base_index = cand[lo:hi], lo
     else:
-        base_index = rank * int(cand.size)
-    n = int(cand.size)
+        base_index = rank * len(cand)
+    n = len(cand)
     sc = hc.EdgeScorer(settings)
     sc.set_reads(reads)
-    cd = sc.pack_cands(cand)  # hc_cand_rec: the 16 bytes per candidate the stage sends to the device
-    d_in = torch.from_numpy(cd.view(np.uint8).reshape(-1)).cuda()
+    # hc_cand_rec: the 16 bytes per candidate the stage sends to the device
+    d_in = cand.view(torch.uint8).reshape(-1) if on_device else torch.from_numpy(sc.pack_cands(cand).view(np.uint8).reshape(-1)).cuda()
     d_out = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
-    positions, subs = sc.count_positions_device(d_in.data_ptr(), n, REC_COMPACT)
-    # parity, untimed half: one launch into a buffer of its own, reduced to a digest on the device
-    d_ref = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
-    sc.score_cands_device(d_in.data_ptr(), n, d_ref.data_ptr())
-    sc.synchronize()
-    digest_untimed = device_digest(torch, d_ref, n)
-    del d_ref
+    if args.full:
+        positions, subs = sc.count_positions_device(d_in.data_ptr(), n, REC_COMPACT)
+        # parity, untimed half: one launch into a buffer of its own, reduced to a digest on the device
+        d_ref = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
+        sc.score_cands_device(d_in.data_ptr(), n, d_ref.data_ptr())
+        sc.synchronize()
+        digest_untimed = device_digest(torch, d_ref, n)
+        del d_ref
+    else:  # the same untimed first launch, so that what a first launch sets up is not in the warm-up or, with --warmup 0, the timed steps
+        sc.score_cands_device(d_in.data_ptr(), n, d_out.data_ptr())
+        sc.synchronize()
 
     # N > 1: every rank scores its shard against a replicated read store; per step, the non-dropped
     # records of every rank are collected on every rank.  The scoring kernel itself appends them (tagged with their
@@ -722,25 +786,30 @@ def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, 
         dt = float(t.item())
     if dump_dir and rank == 0:  # outside the timed region, before anything else launches into d_out
         dump_outputs(torch, d_out, n, dump_dir)
-    # parity, timed half: the digest of what the last timed step left, and stretches of it against the CPU oracle
-    parity = parity_record(torch, sc, reads, settings, cand, d_out, n, device_digest(torch, d_out, n), digest_untimed)
-    # kernel-only: hipEvents on the stream the kernel is launched on
-    # (the parity leg above left the device idle for seconds — CPU oracle — and its clocks down: a few untimed launches first, as the timed
-    # steps have their warm-up; round 5's figure carried the ramp: kernel_ms above ms_per_step)
-    sc.time_kernel(d_in.data_ptr(), n, d_out.data_ptr(), max(2, min(args.warmup, 5)), REC_COMPACT)
-    kern_ms = sc.time_kernel(d_in.data_ptr(), n, d_out.data_ptr(), max(10, min(args.steps, 200)), REC_COMPACT)
-    kinfo = sc.kernel_info(n)  # the form a launch of this size takes
-    symbytes = 2 if "encoding=u16" in kinfo else 1
+    kern_ms = None
+    if args.full:
+        # parity, timed half: the digest of what the last timed step left, and stretches of it against the CPU oracle
+        parity = parity_record(torch, sc, reads, settings, cand, d_out, n, device_digest(torch, d_out, n), digest_untimed)
+        # kernel-only: hipEvents on the stream the kernel is launched on
+        # (the parity leg above left the device idle for seconds — CPU oracle — and its clocks down: a few untimed launches first, as the timed
+        # steps have their warm-up; round 5's figure carried the ramp: kernel_ms above ms_per_step)
+        sc.time_kernel(d_in.data_ptr(), n, d_out.data_ptr(), max(2, min(args.warmup, 5)), REC_COMPACT)
+        kern_ms = sc.time_kernel(d_in.data_ptr(), n, d_out.data_ptr(), max(10, min(args.steps, 200)), REC_COMPACT)
+        kinfo = sc.kernel_info(n)  # the form a launch of this size takes
+        symbytes = 2 if "encoding=u16" in kinfo else 1
     per_rank = None
     if dist:  # what every rank saw, gathered outside the timed region
-        mine = torch.tensor([kern_ms, dt_local / args.steps * 1e3, gather_wait_ms / max(args.steps, 1), float(dist.get_world_size()), float(n), gather_ms],
-                            device=coll, dtype=torch.float64)
+        mine = torch.tensor([kern_ms or 0.0, dt_local / args.steps * 1e3, gather_wait_ms / max(args.steps, 1), float(dist.get_world_size()), float(n),
+                             gather_ms], device=coll, dtype=torch.float64)
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(everyone, mine)
         per_rank = [{"rank": r, "kernel_ms": float(v[0]), "step_ms": float(v[1]), "gather_ms": float(v[5]), "gather_wait_ms_per_step": float(v[2]),
                      "n_ranks_seen": int(v[3]), "candidates": int(v[4])} for r, v in enumerate(everyone)]
         if len(per_rank) != world or any(p["n_ranks_seen"] != world for p in per_rank):
             raise SystemExit(f"bench.py: {world} ranks asked for, the collective library reports {[p['n_ranks_seen'] for p in per_rank]}")
+        if not args.full:
+            for p in per_rank:
+                del p["kernel_ms"]
     rec = {
         "value": n_job * args.steps / dt,
         "ms_per_step": dt / args.steps * 1e3,
@@ -753,18 +822,21 @@ def run_workload(workload, order, scaling, args, torch, dist, rank, local_rank, 
                                     if gather else ""),
                        **({"gather": gather_mode, "gather_row_bytes": 24 if narrow else 32, "reserve_cus": reserve_cus,
                            "reserve_cus_tried_ms_per_step": {str(k): v for k, v in reserve_tried.items()} if reserve_tried else None} if gather else {}),
-                       edge_threshold=settings.edge_threshold, mean_positions_per_candidate=positions / max(n, 1)),
-        "roofline": roofline_record(workload, order, n, positions, kern_ms, kinfo, symbytes),
-        "parity": parity,
+                       edge_threshold=settings.edge_threshold),
     }
+    if args.full:
+        rec["config"]["mean_positions_per_candidate"] = positions / max(n, 1)
+        rec["roofline"] = roofline_record(workload, order, n, positions, kern_ms, kinfo, symbytes)
+        rec["parity"] = parity
     if per_rank:
-        # overlap: the share of the all-gather's time hidden behind the scoring kernel = 1 - (step - kernel) / gather alone is not
-        # observable without a second run; what is: a step costs step_ms against a kernel of kernel_ms, the difference is what the
-        # collection adds on the critical path
         rec["ranks"] = {"n_ranks_seen": per_rank[0]["n_ranks_seen"], "gather": gather_mode if gather else None, "per_rank": per_rank,
                         "gather_ms_max": max(p["gather_ms"] for p in per_rank),
-                        "gather_ms_is": "the step's collective(s) alone, events on the side stream, mean over the timed steps (it runs beside the next step's kernel)",
-                        "collection_on_critical_path_ms": max(0.0, rec["ms_per_step"] - max(p["kernel_ms"] for p in per_rank))}
+                        "gather_ms_is": "the step's collective(s) alone, events on the side stream, mean over the timed steps (it runs beside the next step's kernel)"}
+        if args.full:
+            # overlap: the share of the all-gather's time hidden behind the scoring kernel = 1 - (step - kernel) / gather alone is not
+            # observable without a second run; what is: a step costs step_ms against a kernel of kernel_ms, the difference is what the
+            # collection adds on the critical path
+            rec["ranks"]["collection_on_critical_path_ms"] = max(0.0, rec["ms_per_step"] - max(p["kernel_ms"] for p in per_rank))
     sc.close()
     del d_in, d_out
     torch.cuda.empty_cache()
@@ -937,10 +1009,11 @@ def summary_record(out, args):
     def g(x, nd=5):  # compact: the driver's record keeps 2 000 characters of tail
         return float(f"{x:.{nd}g}") if isinstance(x, float) else x
 
-    sm = {"value": g(out["value"]), "ms_per_step": g(out["ms_per_step"]), "n_gpus": out["n_gpus"], "scaling": out["scaling"], "workload": args.workload,
-          "kernel_ms": g(r.get("kernel_ms")), "roofline_frac": g(r.get("frac"), 4), "roofline_bound": r.get("bound"),
-          "roofline_frac_8d_note": "8(d) bytes give %.2f of peak (not a bound: fused symbol byte + L1/L2 reuse); counter traffic gives frac" % (r.get("frac_8d") or 0.0),
-          "parity_checked_records": out.get("parity_checked_records"), "edges": out.get("edges")}
+    sm = {"value": g(out["value"]), "ms_per_step": g(out["ms_per_step"]), "n_gpus": out["n_gpus"], "scaling": out["scaling"], "workload": args.workload}
+    if args.full:
+        sm.update({"kernel_ms": g(r.get("kernel_ms")), "roofline_frac": g(r.get("frac"), 4), "roofline_bound": r.get("bound"),
+                   "roofline_frac_8d_note": "8(d) bytes give %.2f of peak (not a bound: fused symbol byte + L1/L2 reuse); counter traffic gives frac" % (r.get("frac_8d") or 0.0),
+                   "parity_checked_records": out.get("parity_checked_records"), "edges": out.get("edges")})
     busy = r.get("busy") or {}
     for k in ("valu", "lds", "ta", "hbm", "lds_bank_conflict_share", "valu_instructions_per_candidate"):
         if k in busy:
@@ -972,8 +1045,9 @@ def summary_record(out, args):
     if out.get("ranks"):
         sm["gather"] = out["ranks"].get("gather")
         sm["gather_ms_max"] = out["ranks"].get("gather_ms_max")
-        sm["collection_on_critical_path_ms"] = out["ranks"]["collection_on_critical_path_ms"]
-        sm["kernel_ms_per_rank"] = [round(p["kernel_ms"], 4) for p in out["ranks"]["per_rank"]]
+        if args.full:
+            sm["collection_on_critical_path_ms"] = out["ranks"]["collection_on_critical_path_ms"]
+            sm["kernel_ms_per_rank"] = [round(p["kernel_ms"], 4) for p in out["ranks"]["per_rank"]]
     for k in ("strong", "weak"):
         if k in out:
             sm[k] = {"value": out[k]["value"], "ms_per_step": out[k]["ms_per_step"]}
@@ -989,26 +1063,29 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c3")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: in-run parity, kernel time and roofline, the stage, the CPU "
+                         "baselines, the --also workloads and, at N > 1, the other scaling mode; a run without it does only what `value` needs")
     ap.add_argument("--also", default="c2,c3q25,c3q35,c3q35r,c3q60,c3q70",
-                    help="further workloads (comma-separated) measured on one GPU and reported under \"also\" ('none' = skip): config 2, and config 3 with "
+                    help="--full: further workloads (comma-separated) measured on one GPU and reported under \"also\" ('none' = skip): config 2, and config 3 with "
                          "25 / 35 / 60 / 70 distinct quality values (the LG = 5 kernel, the two wide 8-bit encodings and the 16-bit-symbol kernel at the headline's "
                          "size; c3q35r: the 35 values drawn from the histogram of the reference's POLYTE example reads instead of uniformly)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="N > 1: strong (default) = the workload's ONE candidate set is split over the ranks (BASELINE configs[2]); "
                          "weak = every rank scores its own candidate set of the workload's size")
-    ap.add_argument("--one-mode", action="store_true", help="N > 1: measure only --scaling's mode (default: both, the other one under its name)")
+    ap.add_argument("--one-mode", action="store_true", help="N > 1 with --full: measure only --scaling's mode (default: both, the other one under its name)")
     ap.add_argument("--gather", default="all", choices=["ring", "direct", "root", "both", "all"],
                     help="N > 1, the per-step exchange: ring = one all-gather of the fixed-capacity payload; direct = all-gather-v (counts, then "
                          "grouped per-peer send / recv); both (default) = ring first, then the headline's mode again with direct behind a watchdog")
     ap.add_argument("--reserve-cus", type=int, default=-1,
                     help="N > 1: CUs the scoring launches leave free for the exchange's kernels (0 = none, the exchange is not gated either; "
                          "-1 = decided by trying 0, 16 and 32 during set-up)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the result records of the headline workload's last timed step (rank 0's) to DIR/<name>.npy as float64: "
                          f"x1, x2, mm, n, cls and the record positions (index); above {DUMP_SAMPLE} records a fixed, seeded sample of them")
     ap.add_argument("--dump-rows", default=None, help="N > 1 (or HC_BENCH_FORCE_GATHER=1): rank 0 writes the rows collected in the last step to this .npy file")
-    ap.add_argument("--no-stage", action="store_true", help="skip the stage end-to-end measurement")
+    ap.add_argument("--no-stage", action="store_true", help="--full: skip the stage end-to-end measurement")
     ap.add_argument("--stage-threads", type=int, default=0, help="--threads of the stage (0 = min(32, hardware threads))")
     ap.add_argument("--order", default="sfo", choices=["sfo", "grouped", "shuffled"],
                     help="candidate order inside the batch: sfo = sorted by (min id, max id) as scripts/sfo2overlaps.py:53 "
@@ -1068,8 +1145,8 @@ def main():
     def leg_record(rec, mode_name):
         return {"value": rec["value"], "unit": "candidate overlaps/s", "ms_per_step": rec["ms_per_step"], "scaling": mode_name,
                 "gather": rec["config"].get("gather"), "gather_row_bytes": rec["config"].get("gather_row_bytes"), "candidates_per_step": rec["config"]["candidates_per_step"],
-                "candidates_per_gpu": rec["config"]["candidates_per_gpu"], "kernel_ms": rec["roofline"]["kernel_ms"], "ranks": rec.get("ranks"),
-                "parity": rec["parity"]}
+                "candidates_per_gpu": rec["config"]["candidates_per_gpu"], "kernel_ms": rec.get("roofline", {}).get("kernel_ms"), "ranks": rec.get("ranks"),
+                "parity": rec.get("parity")}
 
     def headline(rec):
         h = {
@@ -1087,11 +1164,10 @@ def main():
             "data": "synthetic",
             "config": dict(rec["config"], **({"test_run": f"backend {backend}, every rank on one device: NOT a multi-GPU measurement"}
                                              if (backend != "nccl" or one_device) else {})),
-            "roofline": rec["roofline"],
-            "parity": rec["parity"],
-            "parity_checked_records": rec["parity"]["parity_checked_records"],
-            "edges": rec["parity"]["edges"],
         }
+        if args.full:
+            h.update(roofline=rec["roofline"], parity=rec["parity"], parity_checked_records=rec["parity"]["parity_checked_records"],
+                     edges=rec["parity"]["edges"])
         if "ranks" in rec:
             h["ranks"] = rec["ranks"]
         return h
@@ -1100,7 +1176,7 @@ def main():
         out = headline(main_rec)
     if dist:
         dist.barrier()
-    if world > 1 and not args.one_mode:
+    if world > 1 and args.full and not args.one_mode:
         # the other scaling mode in the same line, so that one driver pass over N = 1, 2, 4, 8 yields both curves.  The HEADLINE (round 5) is
         # "strong": the ONE candidate set of the workload (BASELINE configs[2]: 1e8 candidates, 1 -> 8 GPUs) split over the ranks — what the
         # north star's "scaling at 8 GPUs" is quoted on; "weak" = every rank its own set.  Same steps, collection, barriers, max-over-ranks clock.
@@ -1149,9 +1225,9 @@ def main():
                 out = dict(headline(best_rec), **extras)
             out["gather_modes"] = legs
             out["gather_modes_note"] = (f"`value` is the fastest of the forms of the per-step exchange ({out['config'].get('gather')}), each a full leg of "
-                                        f"{args.steps} timed steps with its own warm-up, barriers and in-run parity")
+                                        f"{args.steps} timed steps with its own warm-up and barriers" + (" and in-run parity" if args.full else ""))
         dist.barrier()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_stage:
             threads = args.stage_threads or min(32, os.cpu_count() or 1)
             out["stage_end_to_end"] = stage_end_to_end(reads, cand, settings, threads)

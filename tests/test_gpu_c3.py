@@ -25,6 +25,15 @@ def c3():
     return reads, cand, st
 
 
+def test_c3_records_a_plain_bench_run_builds_on_the_device(c3):
+    """bench.paired_candidates_device at the headline's size: the 10^8 records a plain bench.py run scores are pack_cands of the host's."""
+    import bench
+
+    reads, cand, st = c3
+    _, d_cand, _, _ = bench.build_workload("c3", 0, on_device=True)
+    assert d_cand.cpu().numpy().tobytes() == hc.EdgeScorer.pack_cands(cand).tobytes()
+
+
 def test_full_size_c3_properties_and_every_record_against_the_oracle(oracle, c3):
     reads, cand, st = c3
     rng = np.random.default_rng(31)

@@ -50,7 +50,7 @@ def test_ranks_over_rccl_collect_what_one_device_computes(tmp_path, scaling, gat
     rows_file = str(tmp_path / "rows.npy")
     env, over_rccl = _ranks_env(world)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full",
            "--workload", "c2", "--scaling", scaling, "--one-mode", "--gather", gather, "--no-stage", "--no-cpu-baseline", "--also", "none",
            "--dump-rows", rows_file]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -115,7 +115,7 @@ def test_one_pass_yields_both_curves():
     """The driver's command line at N = 2 over RCCL (see _check_default_line; one GPU: both ranks on it over gloo, see _ranks_env)."""
     env, over_rccl = _ranks_env(2)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--workload", "c2", "--no-stage", "--no-cpu-baseline", "--also", "none"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -165,24 +165,26 @@ def test_n_rank_bench_path_on_one_gpu_over_gloo(tmp_path, world):
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1"]
     tail = ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--workload", "c2", "--no-stage", "--no-cpu-baseline", "--also", "none"]
     # (1) the driver's command line: both curves in one line
-    r = subprocess.run(base + ["--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + tail, cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=1200)
+    r = subprocess.run(base + ["--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + tail + ["--full"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert "test_run" in line["config"]
     _check_default_line(line, world)
-    # (2) the strong split's gathered rows are the one-device result, by either form of the exchange
+    # (2) the strong split's gathered rows are the one-device result, by either form of the exchange, and in a plain run (no --full: the
+    # candidate records built on the device)
     rows = {}
-    for gather, row_bytes in (("ring", "24"), ("direct", "24"), ("root", "24"), ("root", "32")):  # (32: the rows as the kernels write them)
-        rows_file = str(tmp_path / f"rows_{gather}_{row_bytes}.npy")
-        r = subprocess.run(base + ["--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + tail +
+    for gather, row_bytes, full in (("ring", "24", True), ("direct", "24", True), ("root", "24", True), ("root", "32", True),  # (32: the rows as the kernels write them)
+                                    ("ring", "24", False)):
+        rows_file = str(tmp_path / f"rows_{gather}_{row_bytes}_{full}.npy")
+        r = subprocess.run(base + ["--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + tail + (["--full"] if full else []) +
                            ["--scaling", "strong", "--one-mode", "--gather", gather, "--dump-rows", rows_file], cwd=ROOT,
                            env=dict(env, HC_BENCH_ROW_BYTES=row_bytes), capture_output=True, text=True, timeout=1200)
         assert r.returncode == 0, r.stderr[-3000:]
         assert json.loads(r.stdout.strip().splitlines()[-1])["config"]["gather_row_bytes"] == int(row_bytes)
-        rows[(gather, row_bytes)] = np.load(rows_file)
-    assert all(np.array_equal(rows[("ring", "24")], v) for v in rows.values()), "every form and row width collects the same set"
-    rows = rows[("ring", "24")]
+        rows[(gather, row_bytes, full)] = np.load(rows_file)
+    assert all(np.array_equal(rows[("ring", "24", True)], v) for v in rows.values()), "every form, row width and run collects the same set"
+    rows = rows[("ring", "24", True)]
     import bench
     import haploconduct_amd as hc
     from haploconduct_amd.records import result_cls
@@ -210,7 +212,7 @@ def test_every_launch_form_through_the_n_rank_path_over_gloo(tmp_path, workload,
 
     env = dict(os.environ, HC_BENCH_BACKEND="gloo", HC_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1"]
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--no-stage", "--no-cpu-baseline", "--also", "none",
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--workload", workload, "--no-stage", "--no-cpu-baseline", "--also", "none",
             "--scaling", "strong", "--one-mode"]
     got = {}
     for gather in ("ring", "root"):

@@ -11,6 +11,6 @@ OBJS=$(ls build/*.o build/host/*.o | grep -v hc_kernels.hip.o)
 for A in $MASKS; do
   /opt/rocm/bin/hipcc $FLAGS -DHC_ABLATE=$A -x hip -c -o build/hc_kernels.hip.o hc_kernels.hip 2>$R/gpurun_out/ablate_cc_$A.err || { echo "mask $A: compile failed"; continue; }
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libhcedge.so build/hc_kernels.hip.o $OBJS
-  (cd $R && HC_BENCH_ABLATION=1 HC_WORKLOAD_CACHE=/tmp/hcw timeout 600 python bench.py --workload $W --also none --no-stage --no-cpu-baseline --steps 10 2>$R/gpurun_out/ablate_$A.err | \
+  (cd $R && HC_BENCH_ABLATION=1 HC_WORKLOAD_CACHE=/tmp/hcw timeout 600 python bench.py --full --workload $W --also none --no-stage --no-cpu-baseline --steps 10 2>/tmp/ablate_$A.err | \
     python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$W HC_ABLATE=$A kernel_ms', round(d['roofline']['kernel_ms'],4))")
 done
