@@ -71,8 +71,24 @@ class hc_clean_counts(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class hc_sr_settings(C.Structure):  # include/hcsr.h
+    _fields_ = [("min_qual", C.c_double), ("min_clique_size", C.c_uint32), ("error_correction", C.c_uint32), ("subreads_needed", C.c_uint32),
+                ("n_threads", C.c_uint32)]
+
+
+class hc_sr_stats(C.Structure):
+    _fields_ = [("n_columns", C.c_uint64), ("n_host_columns", C.c_uint64), ("ms_device", C.c_double), ("ms_host_finish", C.c_double)]
+
+
 _vp = C.c_void_p
+_u64p = C.POINTER(C.c_uint64)
+_sr_tail = [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]
 _sig = {
+    "hc_sr_consensus": (C.c_int, [_vp] + _sr_tail),
+    "hc_host_sr_consensus": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32] + _sr_tail),
+    "hc_host_sr_column": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_double, _vp]),
+    "hc_host_sr_table": (C.c_int, [C.c_double, C.c_uint32, _vp]),
+    "hc_host_sr_edge_layouts": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp, _u64p]),
     "hc_version": (C.c_char_p, []),
     "hc_strerror": (C.c_char_p, [C.c_int]),
     "hc_last_error": (C.c_char_p, []),

@@ -1,0 +1,94 @@
+"""Super-read consensus (include/hcsr.h): SRBuilder::consensus / consensus_pos (reference src/SRBuilder.cpp:289-535)
+for a batch of layouts.  Record views, the result type and the plumbing shared by EdgeScorer.sr_consensus (device)
+and host.sr_consensus (the host mirror)."""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native as N
+
+# hc_sr_member, 12 bytes; hc_sr_layout, 16 bytes
+SR_MEMBER_DTYPE = np.dtype([("read", "<u4"), ("pos", "<i4"), ("seq", "u1"), ("rev", "u1"), ("pad", "u1", (2,))], align=False)
+assert SR_MEMBER_DTYPE.itemsize == 12
+SR_LAYOUT_DTYPE = np.dtype([("first_member", "<u8"), ("n_members", "<u4"), ("total_len", "<i4")], align=False)
+assert SR_LAYOUT_DTYPE.itemsize == 16
+
+SR_OK, SR_NO_SUPPORT, SR_MEMBER_SHORT, SR_UNCOVERED, SR_NAN, SR_BAD_LAYOUT, SR_BAD_SYMBOL = range(7)
+SR_TABLE_BYTES = 25 * 128 * 128 + 5 * 128
+
+
+@dataclass
+class SrResult:
+    ret: np.ndarray        # int32 per layout: what consensus() returns
+    status: np.ndarray     # uint32 per layout: SR_*
+    out_off: np.ndarray    # uint64, n_layouts + 1
+    cons_seq: np.ndarray   # uint8, packed
+    cons_qual: np.ndarray  # uint8, packed
+    n_columns: int
+    n_host_columns: int    # device call: columns the host threads finished from the device's sums
+    ms_device: float
+    ms_host_finish: float
+
+    def seq(self, i):
+        a, b = int(self.out_off[i]), int(self.out_off[i + 1])
+        return self.cons_seq[a:b].tobytes(), self.cons_qual[a:b].tobytes()
+
+
+def make_settings(min_qual=0.99, min_clique_size=2, error_correction=False, subreads_needed=False, n_threads=1):
+    return N.hc_sr_settings(float(min_qual), int(min_clique_size), int(bool(error_correction)), int(bool(subreads_needed)), int(n_threads))
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def run(call, layouts, members, settings):
+    """call(layouts_ptr, n_layouts, members_ptr, n_members, settings_ref, ret, status, out_off, seq, qual, cap, n_bytes_ref, stats_ref) -> status"""
+    layouts = np.ascontiguousarray(layouts, dtype=SR_LAYOUT_DTYPE)
+    members = np.ascontiguousarray(members, dtype=SR_MEMBER_DTYPE)
+    n = layouts.size
+    ret = np.zeros(n, np.int32)
+    status = np.zeros(n, np.uint32)
+    out_off = np.zeros(n + 1, np.uint64)
+    cap = int(np.maximum(layouts["total_len"], 0).astype(np.int64).sum())
+    seq = np.zeros(cap, np.uint8)
+    qual = np.zeros(cap, np.uint8)
+    n_bytes = C.c_uint64(0)
+    stats = N.hc_sr_stats()
+    N.check(call(_ptr(layouts), n, _ptr(members), members.size, C.byref(settings), ret.ctypes.data if n else None,
+                 status.ctypes.data if n else None, out_off.ctypes.data, _ptr(seq), _ptr(qual), cap, C.byref(n_bytes), C.byref(stats)),
+            "sr_consensus")
+    nb = int(n_bytes.value)
+    return SrResult(ret, status, out_off, seq[:nb], qual[:nb], int(stats.n_columns), int(stats.n_host_columns), float(stats.ms_device),
+                    float(stats.ms_host_finish))
+
+
+def edge_layouts(edges, reads):
+    """Layouts of edge merges between single-end reads, as sort_vertices type 's' builds them (src/SRBuilder.cpp:33-285).
+    edges: hc_edge_rec records (records.EDGE_DTYPE); returns (layouts, members).  A paired read is refused (HcError)."""
+    from .host import EDGE_DTYPE
+
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    first = reads.read_first_seq.astype(np.int64)
+    paired = np.ascontiguousarray((first[1:] - first[:-1]) == 2, dtype=np.uint8)
+    lens = np.ascontiguousarray((reads.seq_off[1:] - reads.seq_off[:-1])[first[:-1]], dtype=np.uint32)
+    layouts = np.zeros(edges.size, SR_LAYOUT_DTYPE)
+    members = np.zeros(2 * edges.size, SR_MEMBER_DTYPE)
+    bad = C.c_uint64(0)
+    N.check(N.lib.hc_host_sr_edge_layouts(_ptr(edges), edges.size, _ptr(lens), _ptr(paired), reads.n_reads, _ptr(layouts), _ptr(members),
+                                          C.byref(bad)), "sr edge_layouts")
+    return layouts, members
+
+
+def column(nucleotides, qualities, min_qual=0.99):
+    """consensus_pos for one column given as byte strings: (nucleotide, quality byte), or None where it returns 0."""
+    out = (C.c_uint8 * 2)()
+    ok = N.lib.hc_host_sr_column(bytes(nucleotides), bytes(qualities), len(nucleotides), float(min_qual), out)
+    return (out[0], out[1]) if ok else None
+
+
+def table(min_qual, n_q):
+    t = np.zeros(SR_TABLE_BYTES, np.uint8)
+    N.check(N.lib.hc_host_sr_table(float(min_qual), int(n_q), t.ctypes.data), "hc_host_sr_table")
+    return t

@@ -368,6 +368,11 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
             }
         }
     }
+    // the inverse of qmap, by quality index as the symbols carry it (the consensus tables are addressed by it: hc_api_sr.cpp)
+    memset(c->sr_qbyte, 255, sizeof c->sr_qbyte);
+    for (int b = 33; b <= 127; b++)
+        if (qmap[b] < 128) c->sr_qbyte[qmap[b]] = (uint8_t)(b - 33);
+    c->sr.tables_valid = false;
     if (phred.empty()) phred.push_back(0);
     const uint32_t K = (uint32_t)phred.size();
     const uint32_t symbytes = hc::sym_bytes_for(K);

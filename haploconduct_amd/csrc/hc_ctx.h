@@ -250,6 +250,14 @@ struct hc_ctx {
         hipEvent_t stage_free[2] = {nullptr, nullptr};
         int stage_turn = 0;
     } graph;
+    // super-read consensus (hc_api_sr.cpp).  hc_set_reads keeps the inverse of its quality map: sr_qbyte[i] = quality byte - 33 of the
+    // store's quality index i (255: the index is not a quality value).  The tables are rebuilt when the store or min_qual changes.
+    uint8_t sr_qbyte[128];
+    struct Sr {
+        hc_scratch layouts, members, mem, info, len, off, temp, seq, qual, late, host_cols, counter, terms, qbyte, table;
+        bool tables_valid = false;
+        double table_min_qual = 0;
+    } sr;
 };
 
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,

@@ -1,0 +1,47 @@
+// hc_sr.h — what the super-read consensus kernels (hc_sr_kernels.hip) and their glue (hc_api_sr.cpp) share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/hcsr.h"
+#include "hc_device.h"
+
+namespace hc {
+
+constexpr uint32_t kSrQIdx = 128;                 // quality indices of a store symbol the tables are addressed by (K + 2 <= 97, wide labels < 64)
+constexpr uint32_t kSrTable1 = 25u * 128u * 128u;  // hcsr.h: where the one-member entries of the table start
+constexpr uint32_t kSrLateBadSymbol = 1u, kSrLateNaN = 2u;  // what a column reports about its layout
+constexpr double kSrSafeLead = 9.79;               // host/SrConsensus.h: kSafeLead, kSafeFloor
+constexpr double kSrSafeFloor = -300.0;
+
+struct SrMember {  // a member resolved against the store
+    uint64_t off;  // first symbol of the oriented sequence
+    uint32_t len;
+    int32_t pos;
+};
+static_assert(sizeof(SrMember) == 16, "SrMember is 16 bytes");
+
+struct SrLayoutInfo {
+    int32_t ret;      // what consensus() returns
+    uint32_t status;  // HC_SR_*
+    uint32_t len;     // columns written
+    int32_t trim;     // trim_pos: the first column
+};
+
+struct SrHostColumn {  // a column the host finishes (:348-396) from the device's sums
+    uint64_t out;      // its place in the packed buffers
+    uint32_t n;        // nucleotides.length()
+    uint32_t layout;
+    double s[4];       // by base code A, C, G, T
+};
+static_assert(sizeof(SrHostColumn) == 48, "SrHostColumn is 48 bytes");
+
+hipError_t sr_launch_layouts(const StoreView& st, const hc_sr_layout* layouts, uint64_t n_layouts, const hc_sr_member* members, uint64_t n_members,
+                             uint32_t minimum_support, uint32_t error_correction, SrMember* mem, SrLayoutInfo* info, uint64_t* out_len,
+                             hipStream_t s);
+hipError_t sr_launch_columns(const StoreView& st, uint32_t n_cu, const hc_sr_layout* layouts, uint64_t n_layouts, const SrMember* mem,
+                             const SrLayoutInfo* info, const uint64_t* out_off, const double* terms, const uint8_t* qbyte, const uint8_t* table,
+                             uint32_t safe_region, uint8_t* cons_seq, uint8_t* cons_qual, uint32_t* late, SrHostColumn* host_cols,
+                             uint64_t host_cap, unsigned long long* host_count, hipStream_t s);
+
+}  // namespace hc

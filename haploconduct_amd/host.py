@@ -407,3 +407,23 @@ class EdgeCalculatorStage:
             self.close()
         except Exception:
             pass
+
+
+def sr_consensus(reads, layouts, members, min_qual=0.99, min_clique_size=2, error_correction=False, subreads_needed=False, n_threads=1):
+    """hc_host_sr_consensus: the host mirror of EdgeScorer.sr_consensus on a ReadSet (SRBuilder::consensus, src/SRBuilder.cpp:289-535)."""
+    from . import consensus as SR
+
+    st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
+
+    def p(a):
+        return a.ctypes.data if a.size else None
+
+    return SR.run(lambda *a: N.lib.hc_host_sr_consensus(p(reads.bases), p(reads.quals), p(reads.seq_off), p(reads.read_first_seq), reads.n_reads, *a),
+                  layouts, members, st)
+
+
+def sr_edge_layouts(edges, reads):
+    """hc_host_sr_edge_layouts: layouts of edge merges between single-end reads (sort_vertices type 's', src/SRBuilder.cpp:33-285)."""
+    from . import consensus as SR
+
+    return SR.edge_layouts(edges, reads)

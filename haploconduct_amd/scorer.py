@@ -49,6 +49,15 @@ class EdgeScorer:
             "hc_set_reads",
         )
 
+    # -- super-read consensus (include/hcsr.h) --------------------------------
+    def sr_consensus(self, layouts, members, min_qual=0.99, min_clique_size=2, error_correction=False, subreads_needed=False, n_threads=16):
+        """hc_sr_consensus: SRBuilder::consensus (src/SRBuilder.cpp:413-535) for every layout, on the device against the store of
+        set_reads.  layouts / members: consensus.SR_LAYOUT_DTYPE / SR_MEMBER_DTYPE records.  Returns a consensus.SrResult."""
+        from . import consensus as SR
+
+        st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
+        return SR.run(lambda *a: N.lib.hc_sr_consensus(self._ctx, *a), layouts, members, st)
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

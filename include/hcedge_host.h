@@ -209,6 +209,9 @@ int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t 
                                       uint64_t* n_out);
 int hc_host_graph_free(hc_host_graph* g);
 
+/* Super-read consensus on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts): include/hcsr.h,
+ * which includes this header's records. */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,112 @@
+/*
+ * hcsr.h — C ABI of the super-read consensus in libhcedge.so: SRBuilder::consensus and consensus_pos
+ * (reference src/SRBuilder.cpp:289-535) for a batch of layouts, on the device against the store of hc_set_reads, and
+ * the host mirror of the same contract on plain base / quality arrays.  Plain C, as hcedge.h and hcfno.h.
+ * Citations: reference file:line.
+ *
+ * A LAYOUT is what sort_vertices (src/SRBuilder.cpp:33-285) hands to consensus: total_len and the members in list order
+ * (positions ascending, the first is 0).  A MEMBER names a stored sequence instead of carrying strings.
+ */
+#ifndef HCSR_H_
+#define HCSR_H_
+
+#include "hcedge.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One entry of pos_list / seq_list / qual_list. */
+typedef struct hc_sr_member {
+    uint32_t read; /* index of the read in the store (hc_set_reads order)                                      */
+    int32_t pos;   /* its entry of pos_list                                                                    */
+    uint8_t seq;   /* Read::get_seq(0 | 1 | 2): 0 = the sequence of a single-end read, 1 / 2 = mate of a pair   */
+    uint8_t rev;   /* 0: get_seq / get_phred; 1: get_rev_comp / get_rev_phred                                  */
+    uint8_t pad[2];
+} hc_sr_member; /* 12 bytes */
+
+typedef struct hc_sr_layout {
+    uint64_t first_member; /* members [first_member, first_member + n_members) of the call's member array */
+    uint32_t n_members;
+    int32_t total_len;
+} hc_sr_layout; /* 16 bytes */
+
+typedef struct hc_sr_settings {
+    double min_qual;           /* SRBuilder::minQual, src/SRBuilder.h:89 (0.99 there)                        */
+    uint32_t min_clique_size;  /* program_settings.min_clique_size, :426                                    */
+    uint32_t error_correction; /* consensus(..., error_correction)                                          */
+    uint32_t subreads_needed;  /* consensus(..., subreads_needed): minimumSupport = 2, :422-424             */
+    uint32_t n_threads;        /* host threads (the mirror's layouts; the device call's host-finished columns); 0 = 1 */
+} hc_sr_settings; /* 24 bytes */
+
+/* Per-layout status: which of the reference's exits a layout took.  cons_seq / cons_qual are empty for all but HC_SR_OK
+ * (an HC_SR_OK layout may be empty too: nothing left after the trim). */
+enum {
+    HC_SR_OK = 0,           /* return trim_pos, :535                                                              */
+    HC_SR_NO_SUPPORT = 1,   /* "Not enough support for super-read.", return -1, :441-446                          */
+    HC_SR_MEMBER_SHORT = 2, /* a member shorter than its trimmed start, return 0, :490-494                        */
+    HC_SR_UNCOVERED = 3,    /* a column no member covers, return 0, :507-510                                      */
+    HC_SR_NAN = 4,          /* "p_incorrect NaN", return trim_pos, :367-370, :528-532                             */
+    HC_SR_BAD_LAYOUT = 5,   /* refused: no member, member / read index out of range, `seq` that the read does not
+                               have, rev > 1, first position not 0, positions not ascending, total_len shorter than
+                               a member's end.  Return value 0.  Nothing of the store is read for it.             */
+    HC_SR_BAD_SYMBOL = 6    /* a column met a base outside ACGTN or a quality byte outside [33,127] (the
+                               reference asserts, :307,340).  Return value 0.                                    */
+};
+
+typedef struct hc_sr_stats {
+    uint64_t n_columns;      /* consensus positions written                                                         */
+    uint64_t n_host_columns; /* of them finished by host threads from the device's four sums (device call only)   */
+    double ms_device;        /* device call only: the kernels, by events on the context's stream                  */
+    double ms_host_finish;   /* device call only: the host threads' share                                         */
+} hc_sr_stats;
+
+/* SRBuilder::consensus (src/SRBuilder.cpp:413-535) with consensus_pos (:296-409) for every layout, on the device.
+ * Needs hc_set_reads.  Per layout l: ret[l] = the return value, status[l] = HC_SR_*, and cons_seq / cons_qual hold
+ * its bytes at [out_off[l], out_off[l + 1]) — one packed buffer each, out_off has n_layouts + 1 entries.
+ * cap = bytes cons_seq and cons_qual each have room for; the sum of the layouts' positive total_len always suffices.
+ * *n_bytes = bytes needed; when cap is smaller (or cons_seq / cons_qual are NULL), ret / status / out_off are still
+ * filled, nothing is written to the two buffers and HC_ERR_ARG is returned: asking first with cap = 0 and calling again
+ * is the count-then-fetch form.  stats may be NULL.
+ * Numerics (DESIGN.md "Super-read consensus"): the device adds host-built log10 terms in member order, takes columns
+ * of one and two members from a host-built table and decides a deeper column only where the outcome follows from the
+ * four sums by comparisons; every other column is finished by host threads with the reference's expressions.  The
+ * result is the reference's, byte for byte. */
+int hc_sr_consensus(hc_ctx* ctx, const hc_sr_layout* layouts, uint64_t n_layouts, const hc_sr_member* members, uint64_t n_members,
+                    const hc_sr_settings* settings, int32_t* ret, uint32_t* status, uint64_t* out_off, uint8_t* cons_seq,
+                    uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats);
+
+/* The same contract on the host, on the arrays hc_set_reads takes (no device, no context): a restatement of
+ * :296-535 that walks every layout as the reference does.  What the CPU tests run and what the device is compared with. */
+int hc_host_sr_consensus(const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off, const uint32_t* read_first_seq,
+                         uint32_t n_reads, const hc_sr_layout* layouts, uint64_t n_layouts, const hc_sr_member* members,
+                         uint64_t n_members, const hc_sr_settings* settings, int32_t* ret, uint32_t* status, uint64_t* out_off,
+                         uint8_t* cons_seq, uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats);
+
+/* consensus_pos (:296-409) for ONE column given as strings, by direct evaluation: out[0] = the nucleotide, out[1] = the
+ * quality byte.  Returns 1, or 0 where consensus_pos returns 0 (NaN). */
+int hc_host_sr_column(const uint8_t* nucleotides, const uint8_t* qualities, uint32_t n, double min_qual, uint8_t* out);
+
+/* The table the device takes columns of one and two members from (built once per call and min_qual on the host by the
+ * reference's expressions): entry ((b1 * 5 + b2) * 128 + q1) * 128 + q2 for bases b = 0..4 (A, C, G, T, N) and quality
+ * bytes q + 33 of the two members in list order, and, for one member, entry 25 * 128 * 128 + b1 * 128 + q1.
+ * (an N member has q = 0 whatever its quality byte: it takes no part).  An entry is the Phred value 0..93, 255 for the 'N' / '$' column, 254 for NaN.  (The nucleotide follows from the exact
+ * sums by comparison, :390-393.)  Only q < n_q is filled.  table has HC_SR_TABLE_BYTES bytes. */
+#define HC_SR_TABLE_BYTES (25u * 128u * 128u + 5u * 128u)
+int hc_host_sr_table(double min_qual, uint32_t n_q, uint8_t* table);
+
+/* Layouts of the simplest real case: merging along an edge between two SINGLE-END reads, as sort_vertices type 's' does
+ * for the two vertices of the edge (:33-285): the base is the member with the smaller vertex, the other member's
+ * new_pos = pos1 when the base is read 1 of the edge, -pos1 otherwise (:143-148), inserted before the base when
+ * new_pos <= 0 (:213-221), positions shifted so that the first is 0 (:247-250), total_len = base length + the two
+ * extensions (:236-243).  rev = the vertex is the reverse one (OverlapGraph::getOrientation false).
+ * seq_len_by_read[r] = length of single-end read r, paired[r] != 0 marks a paired read (may be NULL: none is).
+ * Writes layouts[i] (first_member = 2 i) and members[2 i], members[2 i + 1].  An edge that names a paired read, a read
+ * index >= n_reads or read1 == read2 is refused: HC_ERR_BAD_OVERLAP, *first_bad = its index (paired members are not built). */
+int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const uint32_t* seq_len_by_read, const uint8_t* paired,
+                            uint32_t n_reads, hc_sr_layout* layouts, hc_sr_member* members, uint64_t* first_bad);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
