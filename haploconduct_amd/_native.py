@@ -71,6 +71,25 @@ class hc_clean_counts(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class hc_read_geom(C.Structure):
+    _fields_ = [("len1", C.c_uint32), ("len2", C.c_uint32), ("paired", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class hc_tip_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("edges_before", "edges_after", "out_tip_count", "tip_count", "n_removed", "n_tip_reads")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class hc_branch_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("edges_before", "edges_after", "n_removed", "transitive_kept", "n_out_branch", "n_in_branch",
+                                          "n_components", "n_tied_lists", "cc_rounds")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class hc_sr_settings(C.Structure):  # include/hcsr.h
     _fields_ = [("min_qual", C.c_double), ("min_clique_size", C.c_uint32), ("error_correction", C.c_uint32), ("subreads_needed", C.c_uint32),
                 ("n_threads", C.c_uint32)]
@@ -136,6 +155,10 @@ _sig = {
     "hc_graph_remove_inclusions": (C.c_int, [_vp, C.POINTER(hc_clean_counts)]),
     "hc_graph_remove_transitive": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(hc_clean_counts)]),
     "hc_graph_fetch_inclusion_edges": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hc_graph_remove_tips": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(hc_tip_counts)]),
+    "hc_graph_remove_branches": (C.c_int, [_vp, C.POINTER(hc_branch_counts)]),
+    "hc_graph_fetch_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "hc_graph_fetch_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
     "hc_reset": (C.c_int, [_vp, _vp]),
     "hc_set_comm_reserve": (C.c_int, [_vp, C.c_uint32]),
     "hc_comm_gate_device": (C.c_int, [_vp, _vp, C.c_uint32]),

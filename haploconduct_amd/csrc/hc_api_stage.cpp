@@ -196,6 +196,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     hc_ctx::Graph& g = c->graph;
     g.valid = false;
     g.have_groups = false;
+    g.n_branching = g.n_tip_reads = 0;
     const uint32_t m = (uint32_t)n, V = (uint32_t)n_vertices;
     hipStream_t s = c->stream;
     const size_t m1 = m ? m : 1;
@@ -348,6 +349,7 @@ int hc_graph_load(hc_ctx* c, const hc_edge_rec* edges, const uint64_t* out_off, 
     hc_ctx::Graph& g = c->graph;
     g.valid = false;
     g.have_groups = false;
+    g.n_branching = g.n_tip_reads = 0;
     int rc;
     const size_t E1 = E ? E : 1;
     if ((rc = g.edges_out.ensure(E1 * sizeof(hc_edge_rec))) || (rc = g.o_out.ensure(E1 * 4)) || (rc = g.in_nodes.ensure(E1 * 4)) ||
@@ -479,6 +481,129 @@ int hc_graph_fetch_inclusion_edges(hc_ctx* c, uint32_t* group_vertex, uint64_t* 
     const uint64_t k = std::min(cap, g.n_group_edges);
     if (edges && k) HC_HIP(hipMemcpyAsync(edges, g.incl_edges.p, k * sizeof(hc_edge_rec), hipMemcpyDeviceToHost, s));
     HC_HIP(hipStreamSynchronize(s));
+    return HC_OK;
+}
+
+// room for `want` bytes in a grow-only buffer whose first `have` bytes stay
+static int grow_keeping(hc_scratch& b, size_t have, size_t want, hipStream_t s) {
+    if (want <= b.cap) return HC_OK;
+    hc_scratch bigger;
+    const int rc = bigger.ensure(std::max(want, 2 * b.cap));
+    if (rc) return rc;
+    if (have) {
+        HC_HIP(hipMemcpyAsync(bigger.p, b.p, have, hipMemcpyDeviceToDevice, s));
+        HC_HIP(hipStreamSynchronize(s));
+    }
+    swap_scratch(b, bigger);
+    return HC_OK;
+}
+
+static const char* const kTiedRefusal =
+    ": the device holds out-lists whose order only the host knows (hc_graph_resolve's tied lists): hc_graph_load the host's lists first";
+
+// the second half of both calls: branching_edges grows by the removed records, the cleaned graph takes the current one's place
+static int commit_removed(hc_ctx* c, const char* who, const hc::trans::Graph& in, hc::trans::Graph& out, bool target_ordered, uint64_t n_removed) {
+    hc_ctx::Graph& g = c->graph;
+    int rc = grow_keeping(g.branching, g.n_branching * sizeof(hc_edge_rec), (g.n_branching + n_removed + 1) * sizeof(hc_edge_rec), c->stream);
+    if (rc) return rc;
+    const hipError_t e = hc::trans::commit_removed(in, out, target_ordered, g.branching.as<hc_edge_rec>() + g.n_branching, n_removed, g.clean_temp.p,
+                                                   g.clean_temp.cap, c->stream);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    g.n_branching += n_removed;
+    clean_commit(g, out);
+    return HC_OK;
+}
+
+int hc_graph_remove_tips(hc_ctx* c, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts) {
+    if (!c || !counts || (n_reads && !reads)) return fail(HC_ERR_ARG, "hc_graph_remove_tips: null argument");
+    memset(counts, 0, sizeof *counts);
+    if (n_reads >= (1ull << 31)) return fail(HC_ERR_ARG, "hc_graph_remove_tips: more than 2^31-1 reads");
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_tips: no graph on the device");
+    if (g.n_tied) return fail(HC_ERR_STATE, std::string("hc_graph_remove_tips") + kTiedRefusal);
+    counts->edges_before = counts->edges_after = g.n_edges;
+    HC_HIP(hipSetDevice(c->device));
+    if (g.n_edges == 0) return HC_OK;  // no list of more than one entry: no tips
+    hipStream_t s = c->stream;
+    hc::trans::Graph in, out;
+    int rc = clean_prepare(c, in, out);
+    if (rc) return rc;
+    // the tip flags of earlier calls stay; reads beyond them start at 0
+    const uint64_t had = g.n_tip_reads, flags = std::max(had, n_reads);
+    if ((rc = grow_keeping(g.tip_reads, had, flags + 1, s)) || (rc = g.read_geom.ensure((n_reads + 1) * sizeof(hc_read_geom)))) return rc;
+    // a refused call (read index out of range) must leave the flags as they were: it sets none, and the zeroed tail is not counted yet
+    if (flags > had) HC_HIP(hipMemsetAsync(g.tip_reads.as<uint8_t>() + had, 0, flags - had, s));
+    if (n_reads) HC_HIP(hipMemcpyAsync(g.read_geom.p, reads, n_reads * sizeof(hc_read_geom), hipMemcpyHostToDevice, s));
+    bool in_range = false;
+    const hipError_t e = hc::trans::find_tips(in, max_tip_len, g.read_geom.as<hc_read_geom>(), n_reads, g.tip_reads.as<uint8_t>(), flags, counts, &in_range,
+                                              g.clean_temp.p, g.clean_temp.cap, s);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string("hc_graph_remove_tips: ") + hipGetErrorString(e));
+    }
+    if (!in_range) {
+        memset(counts, 0, sizeof *counts);
+        return fail(HC_ERR_ARG, "hc_graph_remove_tips: a record's read1 / read2 is not below n_reads");
+    }
+    g.n_tip_reads = flags;
+    if ((rc = commit_removed(c, "hc_graph_remove_tips", in, out, false, counts->n_removed))) return rc;
+    counts->edges_after = g.n_edges;
+    return HC_OK;
+}
+
+int hc_graph_remove_branches(hc_ctx* c, hc_branch_counts* counts) {
+    if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_branches: null argument");
+    memset(counts, 0, sizeof *counts);
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_branches: no graph on the device");
+    if (g.n_tied) return fail(HC_ERR_STATE, std::string("hc_graph_remove_branches") + kTiedRefusal);
+    counts->edges_before = counts->edges_after = g.n_edges;
+    if (g.n_edges == 0) {  // every vertex is its own component
+        counts->n_components = g.n_vertices;
+        return HC_OK;
+    }
+    HC_HIP(hipSetDevice(c->device));
+    hc::trans::Graph in, out;
+    int rc = clean_prepare(c, in, out);
+    if (rc) return rc;
+    const hipError_t e = hc::trans::find_branches(in, counts, g.clean_temp.p, g.clean_temp.cap, c->stream);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string("hc_graph_remove_branches: ") + hipGetErrorString(e));
+    }
+    if ((rc = commit_removed(c, "hc_graph_remove_branches", in, out, true, counts->n_removed))) return rc;
+    counts->edges_after = g.n_edges;
+    return HC_OK;
+}
+
+int hc_graph_fetch_branching_edges(hc_ctx* c, hc_edge_rec* edges, uint64_t cap, uint64_t* n_edges) {
+    if (!c || !n_edges) return fail(HC_ERR_ARG, "hc_graph_fetch_branching_edges: null argument");
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_fetch_branching_edges: no graph on the device");
+    *n_edges = g.n_branching;
+    const uint64_t k = std::min(cap, g.n_branching);
+    if (edges && k) {
+        HC_HIP(hipSetDevice(c->device));
+        HC_HIP(hipMemcpyAsync(edges, g.branching.p, k * sizeof(hc_edge_rec), hipMemcpyDeviceToHost, c->stream));
+        HC_HIP(hipStreamSynchronize(c->stream));
+    }
+    return HC_OK;
+}
+
+int hc_graph_fetch_tip_reads(hc_ctx* c, uint8_t* is_tip, uint64_t n_reads) {
+    if (!c || (n_reads && !is_tip)) return fail(HC_ERR_ARG, "hc_graph_fetch_tip_reads: null argument");
+    hc_ctx::Graph& g = c->graph;
+    if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_fetch_tip_reads: no graph on the device");
+    const uint64_t k = std::min(n_reads, g.n_tip_reads);
+    if (n_reads > k) memset(is_tip + k, 0, n_reads - k);
+    if (k) {
+        HC_HIP(hipSetDevice(c->device));
+        HC_HIP(hipMemcpyAsync(is_tip, g.tip_reads.p, k, hipMemcpyDeviceToHost, c->stream));
+        HC_HIP(hipStreamSynchronize(c->stream));
+    }
     return HC_OK;
 }
 

@@ -241,6 +241,10 @@ struct hc_ctx {
         hc_scratch edges_next, seq_next, out_off_next, in_nodes_next, in_off_next, clean_temp, incl_vtx, incl_off, incl_edges;
         uint64_t n_groups = 0, n_group_edges = 0;
         bool have_groups = false;
+        // hc_graph_remove_tips / hc_graph_remove_branches: OverlapGraph::branching_edges (n_branching records) and the per-read
+        // tip flags (n_tip_reads bytes), both until the next hc_graph_load / hc_graph_resolve; the read table of one call
+        hc_scratch branching, tip_reads, read_geom;
+        uint64_t n_branching = 0, n_tip_reads = 0;
         uint64_t n_vertices = 0, n_edges = 0, n_tied = 0;
         uint64_t n_appended = 0;  // records hc_graph_append has put into adm
         bool valid = false;

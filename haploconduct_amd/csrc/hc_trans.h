@@ -37,6 +37,17 @@ hipError_t remove_transitive(const Graph& in, Graph& out, uint32_t remove_trans,
 hipError_t remove_inclusions(const Graph& in, const uint8_t* inclusions, Graph& out, uint32_t* group_vertex, unsigned long long* group_off,
                              hc_edge_rec* group_edges, uint64_t* n_groups, uint64_t* n_group_edges, hc_clean_counts* counts, void* temp,
                              size_t temp_bytes, hipStream_t s);
+// removeTips / removeBranches in two steps, because the caller sizes branching_edges between them.  find_* leaves in the
+// scratch which records and in-entries stay and the list of removed records in removal order, and fills the counts but
+// edges_after; commit_removed (same graph, same scratch, nothing in between) appends the n_removed records to `removed`
+// and writes the cleaned graph into `out` (target_ordered: find_branches' lists, in sortAdjOut's order).  in.E > 0.
+// find_tips: tip = the per-read flags (n_flags >= n_reads bytes, set where a read becomes a tip); *reads_in_range false: a record
+// names a read >= n_reads and nothing else was done.
+hipError_t find_tips(const Graph& in, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, uint8_t* tip, uint64_t n_flags, hc_tip_counts* counts,
+                     bool* reads_in_range, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t find_branches(const Graph& in, hc_branch_counts* counts, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t commit_removed(const Graph& in, Graph& out, bool target_ordered, hc_edge_rec* removed, uint64_t n_removed, void* temp, size_t temp_bytes,
+                          hipStream_t s);
 
 }  // namespace trans
 }  // namespace hc

@@ -1,5 +1,6 @@
 // hc_trans_kernels.hip — OverlapGraph::removeInclusions and removeTransitiveEdges (src/GraphAlgos.cpp:20-48, 746-833,
-// 938-1077) on the device graph, for gfx950.
+// 938-1077), removeTips (:543-637) and removeBranches (:835-936; described where their kernels start) on the device graph,
+// for gfx950.
 //
 // removeTransitiveEdges:
 //   target order        every out-list stably sorted by target (radix sort of (source, target), positions as values);
@@ -28,6 +29,7 @@
 #include "../../include/hcedge.h"
 #include "hc_prims.h"
 #include "hc_trans.h"
+#include "host/ExtLen.h"
 
 namespace hc {
 namespace trans {
@@ -534,6 +536,296 @@ hipError_t emit(const Graph& in, Graph& out, const uint8_t* keep, const uint32_t
     return hipSuccess;
 }
 
+// sortAdjOut (:806-833): stable target order (target_order), then std::sort's order in the lists where the two can differ;
+// w.tied must be zero on entry
+hipError_t std_sort_target_order(const Graph& g, const Work& w, uint64_t* n_tied_out, hipStream_t s) {
+    // sortAdjOut: stable target order, then std::sort's order in the lists where the two can differ
+    TRY(target_order(g, w, s));
+    uint64_t n_tied = 0;
+    const uint32_t E = g.E, V = g.V;
+    if (E && V) {
+        hipLaunchKernelGGL(k_tied, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, g.out_off, E, w.tied);
+        TRY(hipGetLastError());
+        TRY(prims::select_flagged(w.prims, w.prims_bytes, w.tied, V, w.tied_list, w.counters + 6, s));
+        unsigned long long t = 0;
+        TRY(hipMemcpyAsync(&t, w.counters + 6, sizeof t, hipMemcpyDeviceToHost, s));
+        TRY(hipStreamSynchronize(s));
+        n_tied = t;
+    }
+    if (n_tied) {
+        // the listed lists' targets packed back to back (one copy down), std::sort's permutation of each on the host,
+        // the permutations unpacked into perm (one copy up); everything on s
+        std::vector<uint32_t> tied(n_tied);
+        std::vector<unsigned long long> off(V + 1);
+        TRY(hipMemcpyAsync(tied.data(), w.tied_list, n_tied * 4, hipMemcpyDeviceToHost, s));
+        TRY(hipMemcpyAsync(off.data(), g.out_off, ((size_t)V + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        TRY(hipStreamSynchronize(s));
+        std::vector<uint32_t> pack_off(n_tied + 1, 0);  // every listed list has more than 16 entries: n_tied + 1 <= E
+        for (uint64_t t = 0; t < n_tied; t++) pack_off[t + 1] = pack_off[t] + (uint32_t)(off[tied[t] + 1] - off[tied[t]]);
+        const uint32_t packed = pack_off[n_tied];
+        uint32_t* d_pack = w.lsrc[1];      // scratch of the later passes, free here: packed <= E
+        uint32_t* d_pack_off = w.ltgt[1];
+        TRY(hipMemcpyAsync(d_pack_off, pack_off.data(), (n_tied + 1) * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_pack_lists, dim3((unsigned)std::min<uint64_t>(n_tied, 1u << 16)), dim3(kBlock), 0, s, w.tied_list, (uint32_t)n_tied,
+                           g.out_off, d_pack_off, w.tgt_orig, d_pack);
+        TRY(hipGetLastError());
+        std::vector<uint32_t> targets(packed), perm(packed);
+        TRY(hipMemcpyAsync(targets.data(), d_pack, (size_t)packed * 4, hipMemcpyDeviceToHost, s));
+        TRY(hipStreamSynchronize(s));
+        for (uint64_t t = 0; t < n_tied; t++) target_sort_perm(targets.data() + pack_off[t], pack_off[t + 1] - pack_off[t], perm.data() + pack_off[t]);
+        TRY(hipMemcpyAsync(d_pack, perm.data(), (size_t)packed * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_unpack_perm, dim3((unsigned)std::min<uint64_t>(n_tied, 1u << 16)), dim3(kBlock), 0, s, w.tied_list, (uint32_t)n_tied,
+                           g.out_off, d_pack_off, d_pack, w.perm);
+        TRY(hipGetLastError());
+        TRY(hipStreamSynchronize(s));  // the host vectors leave scope
+    }
+    *n_tied_out = n_tied;
+    return hipSuccess;
+}
+
+// ---- removeTips (:543-637) and removeBranches (:835-936) -----------------------------------------------------------
+//   per-list sums       one lane per list of fewer than 64 entries, the whole wave for a longer one (a 6 000-entry hub is
+//                       94 wave steps, not one lane's loop); no atomics: "has an edge that leads on" and the reduced
+//                       graph's degrees are sums over a list
+//   tips                one pass over the out entries in stable target order and one over the sorted in-entries, which
+//                       finds the first x -> i record by binary search of the target-ordered list; a removed pair is
+//                       marked at the first entry of its run (marking twice is marking once: the std::set), the marks
+//                       are the removal order (ascending (v, w)), the first record of the run is the first in list order
+//   branches            std::sort's target order, k_intersect on every edge, degrees of the reduced graph with
+//                       multiplicity, survivors (outdeg_red(u) == 1 && indeg_red(w) == 1) united in one lock-free
+//                       union-find pass (the larger root hooks under the smaller by atomicCAS, so parent[x] <= x always
+//                       and a cycle's last edge finds both ends under one root), labels by one compress pass
+
+__global__ void k_check_reads(const hc_edge_rec* __restrict__ E, uint32_t n, uint64_t n_reads, unsigned long long* __restrict__ bad) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (n + stride - 1) / stride * stride;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride)
+        wave_count(i < n && (E[i].read1 >= n_reads || E[i].read2 >= n_reads), bad);
+}
+
+__global__ void k_count_nonzero(const uint8_t* __restrict__ a, uint32_t n, unsigned long long* __restrict__ count) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (n + stride - 1) / stride * stride;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride) wave_count(i < n && a[i] != 0, count);
+}
+
+// out[v] = sum of f(k) over k in [off[v], off[v + 1]).  A wave takes 64 lists: lanes walk the short ones, the wave walks
+// each list of 64 or more entries together.
+template <class F>
+__global__ void __launch_bounds__(kBlock) k_list_sum(const unsigned long long* __restrict__ off, uint32_t V, F f, uint32_t* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t chunk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); (uint64_t)chunk * 64 < V; chunk += n_waves) {
+        const uint32_t v = chunk * 64 + lane;
+        const bool valid = v < V;
+        const uint32_t a = valid ? (uint32_t)off[v] : 0u, b = valid ? (uint32_t)off[v + 1] : 0u;
+        uint32_t sum = 0;
+        if (b - a < 64)
+            for (uint32_t k = a; k < b; k++) sum += f(k);
+        unsigned long long longs = __ballot(b - a >= 64);
+        while (longs) {
+            const int j = __ffsll((long long)longs) - 1;
+            longs &= longs - 1;
+            const uint32_t aj = __shfl(a, j), bj = __shfl(b, j);
+            uint32_t part = 0;
+            for (uint32_t k = aj + lane; k < bj; k += 64) part += f(k);
+            for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+            if ((int)lane == j) sum = part;
+        }
+        if (valid) out[v] = sum;
+    }
+}
+
+struct LeadsOn {  // the entry's neighbour has a non-empty list of the same kind: the edge is no dead end
+    const uint32_t* nb;
+    const unsigned long long* off;
+    __device__ uint32_t operator()(uint32_t k) const {
+        const uint32_t t = nb[k];
+        return off[t + 1] > off[t] ? 1u : 0u;
+    }
+};
+
+struct KeptOut {  // target-ordered out entry k is an edge of the reduced graph
+    const uint8_t* transitive;
+    __device__ uint32_t operator()(uint32_t k) const { return transitive[k] ? 0u : 1u; }
+};
+
+// the first entry of (x, y)'s run in x's target-ordered out-list, or 0xffffffff
+__device__ __forceinline__ uint32_t find_pair(const unsigned long long* out_off, const uint32_t* tgt, uint32_t x, uint32_t y) {
+    const uint64_t o0 = out_off[x], o1 = out_off[x + 1];
+    const uint32_t f = (uint32_t)o0 + lower_bound_u32(tgt + o0, (uint32_t)(o1 - o0), y);
+    return f < o1 && tgt[f] == y ? f : 0xffffffffu;  // hc_graph_load checks that adj_in and adj_out hold the same pairs
+}
+
+struct KeptIn {  // sorted in-entry j (key = target << 32 | source) is an edge of the reduced graph
+    const uint64_t* key;
+    const unsigned long long* out_off;
+    const uint32_t* tgt;
+    const uint8_t* transitive;
+    __device__ uint32_t operator()(uint32_t j) const {
+        const uint64_t k = key[j];
+        const uint32_t f = find_pair(out_off, tgt, (uint32_t)k, (uint32_t)(k >> 32));
+        return f != 0xffffffffu && !transitive[f] ? 1u : 0u;
+    }
+};
+
+// removeTips' first loop (:551-586) over the out entries in stable target order
+__global__ void k_tips_out(const hc_edge_rec* __restrict__ E, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ src,
+                           const uint32_t* __restrict__ tgt, const uint32_t* __restrict__ first, uint32_t n,
+                           const unsigned long long* __restrict__ out_off, const uint32_t* __restrict__ leads, const hc_read_geom* __restrict__ reads,
+                           uint32_t max_tip_len, uint8_t* __restrict__ pair_mark, uint8_t* __restrict__ tip, unsigned long long* __restrict__ tips) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (n + stride - 1) / stride * stride;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < end; p += stride) {
+        bool is_tip = false;
+        if (p < n) {
+            const uint32_t u = src[p], t = tgt[p];
+            if (out_off[u + 1] - out_off[u] > 1 && out_off[t + 1] == out_off[t]) {
+                const hc_edge_rec& e = E[perm[p]];
+                const unsigned int ext = edge_ext_len(e, reads[e.read1], reads[e.read2], true);
+                is_tip = ext < max_tip_len || ext == 0;
+                if (ext == 0 || (is_tip && leads[u] != 0)) {  // an inclusion tip always goes, another one unless all are tips
+                    pair_mark[first[p]] = 1;
+                    tip[e.read2] = 1;
+                }
+            }
+        }
+        wave_count(is_tip, tips);
+    }
+}
+
+// ... and its second loop (:591-626) over the in-entries sorted by (target, source): the edge is the first x -> i record
+__global__ void k_tips_in(const uint64_t* __restrict__ key, uint32_t n, const unsigned long long* __restrict__ in_off,
+                          const unsigned long long* __restrict__ out_off, const uint32_t* __restrict__ tgt, const uint32_t* __restrict__ perm,
+                          const hc_edge_rec* __restrict__ E, const uint32_t* __restrict__ leads, const hc_read_geom* __restrict__ reads,
+                          uint32_t max_tip_len, uint8_t* __restrict__ pair_mark, uint8_t* __restrict__ tip, unsigned long long* __restrict__ tips) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (n + stride - 1) / stride * stride;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < end; j += stride) {
+        bool is_tip = false;
+        if (j < n) {
+            const uint64_t k = key[j];
+            const uint32_t x = (uint32_t)k, i = (uint32_t)(k >> 32);
+            if (in_off[i + 1] - in_off[i] > 1 && in_off[x + 1] == in_off[x]) {
+                const uint32_t f = find_pair(out_off, tgt, x, i);
+                if (f != 0xffffffffu) {
+                    const hc_edge_rec& e = E[perm[f]];
+                    const unsigned int ext = edge_ext_len(e, reads[e.read1], reads[e.read2], false);
+                    is_tip = ext < max_tip_len || ext == 0;
+                    if (ext == 0 || (is_tip && leads[i] != 0)) {
+                        pair_mark[f] = 1;
+                        tip[e.read1] = 1;
+                    }
+                }
+            }
+        }
+        wave_count(is_tip, tips);
+    }
+}
+
+// removeEdge for every marked pair: the first record of its run leaves adj_out (keep is in list positions) ...
+__global__ void k_tips_keep_out(const uint8_t* __restrict__ pair_mark, const uint32_t* __restrict__ perm, uint32_t n, uint8_t* __restrict__ keep) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) keep[perm[p]] = pair_mark[p] ? 0 : 1;
+}
+
+// ... and the first x of adj_in[i] (the sort is stable: the first of equal keys is the first in list order)
+__global__ void k_tips_keep_in(const uint64_t* __restrict__ key, const uint32_t* __restrict__ in_pos, uint32_t n,
+                               const unsigned long long* __restrict__ out_off, const uint32_t* __restrict__ tgt, const uint8_t* __restrict__ pair_mark,
+                               uint8_t* __restrict__ in_keep) {
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        const uint64_t k = key[j];
+        bool del = false;
+        if (j == 0 || key[j - 1] != k) {
+            const uint32_t f = find_pair(out_off, tgt, (uint32_t)k, (uint32_t)(k >> 32));
+            del = f != 0xffffffffu && pair_mark[f] != 0;
+        }
+        in_keep[in_pos[j]] = del ? 0 : 1;
+    }
+}
+
+__global__ void k_gather_removed(const uint32_t* __restrict__ idx, uint32_t n, const uint32_t* __restrict__ perm, const hc_edge_rec* __restrict__ E,
+                                 hc_edge_rec* __restrict__ dst) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = E[perm[idx[i]]];
+}
+
+// union-find over the vertices; parent[x] <= x throughout (the larger root hooks under the smaller)
+__device__ __forceinline__ uint32_t uf_load(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+__device__ __forceinline__ uint32_t uf_root(uint32_t* parent, uint32_t v) {  // with path halving
+    uint32_t curr = uf_load(parent + v);
+    if (curr != v) {
+        uint32_t prev = v, next;
+        while (curr > (next = uf_load(parent + curr))) {
+            __atomic_store_n(parent + prev, next, __ATOMIC_RELAXED);
+            prev = curr;
+            curr = next;
+        }
+    }
+    return curr;
+}
+
+__global__ void k_cc_init(uint32_t* __restrict__ parent, uint32_t V) {
+    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) parent[v] = v;
+}
+
+// every surviving edge of the reduced graph unites its ends.  A failed atomicCAS returns a smaller id to go on from, so
+// every retry descends and the loop ends; the edge that closes a cycle finds one root on both sides and does nothing.
+__global__ void k_cc_hook(const uint32_t* __restrict__ src, const uint32_t* __restrict__ tgt, const uint8_t* __restrict__ transitive, uint32_t n,
+                          const uint32_t* __restrict__ dout, const uint32_t* __restrict__ din, uint32_t* parent) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        const uint32_t u = src[p], w = tgt[p];
+        if (transitive[p] || dout[u] != 1 || din[w] != 1) continue;
+        uint32_t a = uf_root(parent, u), b = uf_root(parent, w);
+        while (a != b) {
+            if (a < b) {
+                const uint32_t t = a;
+                a = b;
+                b = t;
+            }
+            const uint32_t old = atomicCAS(parent + a, a, b);  // a > b: hook a under b if a is still a root
+            if (old == a) break;
+            a = old;
+        }
+    }
+}
+
+__global__ void k_cc_labels(const uint32_t* __restrict__ parent, uint32_t V, uint32_t* __restrict__ label, unsigned long long* __restrict__ n_roots) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (V + stride - 1) / stride * stride;
+    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < end; v += stride) {
+        bool root = false;
+        if (v < V) {
+            uint32_t r = v, nx;
+            while ((nx = parent[r]) != r) r = nx;
+            label[v] = r;
+            root = r == v;
+        }
+        wave_count(root, n_roots);
+    }
+}
+
+__global__ void k_branch_stats(const uint32_t* __restrict__ dout, const uint32_t* __restrict__ din, uint32_t V, unsigned long long* __restrict__ n_out,
+                               unsigned long long* __restrict__ n_in) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t end = (V + stride - 1) / stride * stride;
+    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < end; v += stride) {
+        wave_count(v < V && dout[v] > 1, n_out);
+        wave_count(v < V && din[v] > 1, n_in);
+    }
+}
+
+// :918-931: every record between two components leaves (target-ordered positions), and every such entry of adj_in
+__global__ void k_branch_keep(const uint32_t* __restrict__ src, const uint32_t* __restrict__ tgt, const uint32_t* __restrict__ in_owner,
+                              const uint32_t* __restrict__ in_nodes, const uint32_t* __restrict__ label, uint32_t n, uint8_t* __restrict__ keep,
+                              uint8_t* __restrict__ del, uint8_t* __restrict__ in_keep) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        const bool same = label[src[p]] == label[tgt[p]];
+        keep[p] = same ? 1 : 0;
+        del[p] = same ? 0 : 1;
+        in_keep[p] = label[in_nodes[p]] == label[in_owner[p]] ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 hipError_t check_graph(const Graph& g, bool* consistent, void* temp, size_t temp_bytes_, hipStream_t s) {
@@ -575,45 +867,8 @@ hipError_t remove_transitive(const Graph& g, Graph& out, uint32_t remove_trans, 
     const uint32_t E = g.E, V = g.V;
     TRY(hipMemsetAsync(w.counters, 0, 8 * sizeof(unsigned long long), s));
     TRY(hipMemsetAsync(w.tied, 0, (size_t)V + 1, s));
-    // sortAdjOut: stable target order, then std::sort's order in the lists where the two can differ
-    TRY(target_order(g, w, s));
     uint64_t n_tied = 0;
-    if (E && V) {
-        hipLaunchKernelGGL(k_tied, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, g.out_off, E, w.tied);
-        TRY(hipGetLastError());
-        TRY(prims::select_flagged(w.prims, w.prims_bytes, w.tied, V, w.tied_list, w.counters + 6, s));
-        unsigned long long t = 0;
-        TRY(hipMemcpyAsync(&t, w.counters + 6, sizeof t, hipMemcpyDeviceToHost, s));
-        TRY(hipStreamSynchronize(s));
-        n_tied = t;
-    }
-    if (n_tied) {
-        // the listed lists' targets packed back to back (one copy down), std::sort's permutation of each on the host,
-        // the permutations unpacked into perm (one copy up); everything on s
-        std::vector<uint32_t> tied(n_tied);
-        std::vector<unsigned long long> off(V + 1);
-        TRY(hipMemcpyAsync(tied.data(), w.tied_list, n_tied * 4, hipMemcpyDeviceToHost, s));
-        TRY(hipMemcpyAsync(off.data(), g.out_off, ((size_t)V + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        TRY(hipStreamSynchronize(s));
-        std::vector<uint32_t> pack_off(n_tied + 1, 0);  // every listed list has more than 16 entries: n_tied + 1 <= E
-        for (uint64_t t = 0; t < n_tied; t++) pack_off[t + 1] = pack_off[t] + (uint32_t)(off[tied[t] + 1] - off[tied[t]]);
-        const uint32_t packed = pack_off[n_tied];
-        uint32_t* d_pack = w.lsrc[1];      // scratch of the later passes, free here: packed <= E
-        uint32_t* d_pack_off = w.ltgt[1];
-        TRY(hipMemcpyAsync(d_pack_off, pack_off.data(), (n_tied + 1) * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_pack_lists, dim3((unsigned)std::min<uint64_t>(n_tied, 1u << 16)), dim3(kBlock), 0, s, w.tied_list, (uint32_t)n_tied,
-                           g.out_off, d_pack_off, w.tgt_orig, d_pack);
-        TRY(hipGetLastError());
-        std::vector<uint32_t> targets(packed), perm(packed);
-        TRY(hipMemcpyAsync(targets.data(), d_pack, (size_t)packed * 4, hipMemcpyDeviceToHost, s));
-        TRY(hipStreamSynchronize(s));
-        for (uint64_t t = 0; t < n_tied; t++) target_sort_perm(targets.data() + pack_off[t], pack_off[t + 1] - pack_off[t], perm.data() + pack_off[t]);
-        TRY(hipMemcpyAsync(d_pack, perm.data(), (size_t)packed * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_unpack_perm, dim3((unsigned)std::min<uint64_t>(n_tied, 1u << 16)), dim3(kBlock), 0, s, w.tied_list, (uint32_t)n_tied,
-                           g.out_off, d_pack_off, d_pack, w.perm);
-        TRY(hipGetLastError());
-        TRY(hipStreamSynchronize(s));  // the host vectors leave scope
-    }
+    TRY(std_sort_target_order(g, w, &n_tied, s));
     // sortAdjLists(adj_in) and the transitive passes (:954-966); level 0 = every edge in target order
     TRY(sort_in_entries(g, w, s));
     TRY(hipMemsetAsync(w.in_t, 0, E ? E : 1, s));
@@ -733,6 +988,107 @@ hipError_t remove_inclusions(const Graph& g, const uint8_t* incl, Graph& out, ui
     counts->rebuilt = 0;
     counts->n_tied_lists = 0;
     if ((uint64_t)E - h[0] != out.E) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+hipError_t find_tips(const Graph& g, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, uint8_t* tip, uint64_t n_flags, hc_tip_counts* counts,
+                     bool* reads_in_range, void* temp, size_t temp_bytes_, hipStream_t s) {
+    Carve c{(char*)(((uintptr_t)temp + 255) & ~(uintptr_t)255)};
+    const Work w = layout(c, g.E, g.V);
+    if (c.used + 256 > temp_bytes_ || !g.E) return hipErrorInvalidValue;
+    const uint32_t E = g.E, V = g.V;
+    TRY(hipMemsetAsync(w.counters, 0, 8 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_check_reads, grid_for(E), dim3(kBlock), 0, s, g.edges, E, n_reads, w.counters + 2);
+    TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    TRY(hipMemcpyAsync(&bad, w.counters + 2, sizeof bad, hipMemcpyDeviceToHost, s));
+    TRY(hipStreamSynchronize(s));
+    *reads_in_range = bad == 0;
+    if (bad) return hipSuccess;
+    TRY(target_order(g, w, s));  // stable: the first entry of a target's run is the first in list order
+    TRY(sort_in_entries(g, w, s));
+    TRY(hipMemsetAsync(w.pair_d, 0, E, s));
+    uint32_t* leads_out = (uint32_t*)w.max_out;
+    uint32_t* leads_in = (uint32_t*)w.max_in;
+    const dim3 vgrid = grid_for(((uint64_t)V + 63) / 64 * 64);  // 64 lists per wave
+    hipLaunchKernelGGL(k_first, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, g.out_off, E, w.first);
+    hipLaunchKernelGGL(k_list_sum<LeadsOn>, vgrid, dim3(kBlock), 0, s, g.out_off, V, LeadsOn{w.tgt_orig, g.out_off}, leads_out);
+    hipLaunchKernelGGL(k_list_sum<LeadsOn>, vgrid, dim3(kBlock), 0, s, g.in_off, V, LeadsOn{g.in_nodes, g.in_off}, leads_in);
+    hipLaunchKernelGGL(k_tips_out, grid_for(E), dim3(kBlock), 0, s, g.edges, w.perm, w.src, w.tgt, w.first, E, g.out_off, leads_out, reads,
+                       max_tip_len, w.pair_d, tip, w.counters + 0);
+    hipLaunchKernelGGL(k_tips_in, grid_for(E), dim3(kBlock), 0, s, w.key_b, E, g.in_off, g.out_off, w.tgt, w.perm, g.edges, leads_in, reads,
+                       max_tip_len, w.pair_d, tip, w.counters + 1);
+    hipLaunchKernelGGL(k_tips_keep_out, grid_for(E), dim3(kBlock), 0, s, w.pair_d, w.perm, E, w.keep);
+    hipLaunchKernelGGL(k_tips_keep_in, grid_for(E), dim3(kBlock), 0, s, w.key_b, w.in_pos, E, g.out_off, w.tgt, w.pair_d, w.in_keep);
+    hipLaunchKernelGGL(k_count_nonzero, grid_for(n_flags), dim3(kBlock), 0, s, tip, (uint32_t)n_flags, w.counters + 7);
+    TRY(hipGetLastError());
+    TRY(prims::select_flagged(w.prims, w.prims_bytes, w.pair_d, E, w.lpos[1], w.counters + 3, s));  // ascending (v, w)
+    unsigned long long h[8];
+    TRY(hipMemcpyAsync(h, w.counters, sizeof h, hipMemcpyDeviceToHost, s));
+    TRY(hipStreamSynchronize(s));
+    counts->edges_before = E;
+    counts->out_tip_count = h[0];
+    counts->tip_count = h[0] + h[1];
+    counts->n_removed = h[3];
+    counts->n_tip_reads = h[7];
+    return hipSuccess;
+}
+
+hipError_t find_branches(const Graph& g, hc_branch_counts* counts, void* temp, size_t temp_bytes_, hipStream_t s) {
+    Carve c{(char*)(((uintptr_t)temp + 255) & ~(uintptr_t)255)};
+    const Work w = layout(c, g.E, g.V);
+    if (c.used + 256 > temp_bytes_ || !g.E) return hipErrorInvalidValue;
+    const uint32_t E = g.E, V = g.V;
+    TRY(hipMemsetAsync(w.counters, 0, 8 * sizeof(unsigned long long), s));
+    TRY(hipMemsetAsync(w.tied, 0, (size_t)V + 1, s));
+    uint64_t n_tied = 0;
+    TRY(std_sort_target_order(g, w, &n_tied, s));  // sortAdjOut; sortAdjLists(adj_in) next
+    TRY(sort_in_entries(g, w, s));
+    hipLaunchKernelGGL(k_low32, grid_for(E), dim3(kBlock), 0, s, w.key_b, E, w.lin_src);
+    // findTransEdges(..., removeTrans = true) (:847): the reduced graph is what the intersection test does not flag
+    hipLaunchKernelGGL(k_intersect, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, E, g.out_off, w.tgt, g.in_off, w.lin_src, w.flags);
+    TRY(hipGetLastError());
+    uint32_t* dout = (uint32_t*)w.max_out;
+    uint32_t* din = (uint32_t*)w.max_in;
+    uint32_t* parent = w.tied_list;     // free once the target order stands
+    uint32_t* label = (uint32_t*)w.hist;
+    const dim3 vgrid = grid_for(((uint64_t)V + 63) / 64 * 64);
+    hipLaunchKernelGGL(k_list_sum<KeptOut>, vgrid, dim3(kBlock), 0, s, g.out_off, V, KeptOut{w.flags}, dout);
+    hipLaunchKernelGGL(k_list_sum<KeptIn>, vgrid, dim3(kBlock), 0, s, g.in_off, V, KeptIn{w.key_b, g.out_off, w.tgt, w.flags}, din);
+    hipLaunchKernelGGL(k_count_nonzero, grid_for(E), dim3(kBlock), 0, s, w.flags, E, w.counters + 0);
+    hipLaunchKernelGGL(k_branch_stats, grid_for(V), dim3(kBlock), 0, s, dout, din, V, w.counters + 1, w.counters + 2);
+    // components of the surviving edges over all V vertices: one hooking pass, one compress pass
+    hipLaunchKernelGGL(k_cc_init, grid_for(V), dim3(kBlock), 0, s, parent, V);
+    hipLaunchKernelGGL(k_cc_hook, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, w.flags, E, dout, din, parent);
+    hipLaunchKernelGGL(k_cc_labels, grid_for(V), dim3(kBlock), 0, s, parent, V, label, w.counters + 7);
+    hipLaunchKernelGGL(k_branch_keep, grid_for(E), dim3(kBlock), 0, s, w.src, w.tgt, w.in_owner, g.in_nodes, label, E, w.keep, w.in_d, w.in_keep);
+    TRY(hipGetLastError());
+    TRY(prims::select_flagged(w.prims, w.prims_bytes, w.in_d, E, w.lpos[1], w.counters + 3, s));  // vertex ascending, list order
+    unsigned long long h[8];
+    TRY(hipMemcpyAsync(h, w.counters, sizeof h, hipMemcpyDeviceToHost, s));
+    TRY(hipStreamSynchronize(s));
+    counts->edges_before = E;
+    counts->transitive_kept = E - h[0];
+    counts->n_out_branch = h[1];
+    counts->n_in_branch = h[2];
+    counts->n_removed = h[3];
+    counts->n_components = h[7];
+    counts->n_tied_lists = n_tied;
+    counts->cc_rounds = 0;
+    return hipSuccess;
+}
+
+hipError_t commit_removed(const Graph& g, Graph& out, bool target_ordered, hc_edge_rec* removed, uint64_t n_removed, void* temp, size_t temp_bytes_,
+                          hipStream_t s) {
+    Carve c{(char*)(((uintptr_t)temp + 255) & ~(uintptr_t)255)};
+    const Work w = layout(c, g.E, g.V);
+    if (c.used + 256 > temp_bytes_ || n_removed > g.E) return hipErrorInvalidValue;
+    if (n_removed) {
+        hipLaunchKernelGGL(k_gather_removed, grid_for(n_removed), dim3(kBlock), 0, s, w.lpos[1], (uint32_t)n_removed, w.perm, g.edges, removed);
+        TRY(hipGetLastError());
+    }
+    TRY(emit(g, out, w.keep, target_ordered ? w.perm : nullptr, w.in_keep, w, s));
+    if ((uint64_t)g.E - n_removed != out.E) return hipErrorInvalidValue;
     return hipSuccess;
 }
 

@@ -129,6 +129,11 @@ public:
     void removeInclusions(hc_clean_counts* counts = nullptr);
     // src/GraphAlgos.cpp:938-1077 (with :746-833) for remove_trans / branch_reduction as given
     void removeTransitiveEdges(unsigned remove_trans, bool branch_reduction, hc_clean_counts* counts = nullptr);
+    // src/GraphAlgos.cpp:543-637 with max_tip_len as given.  reads[r]: pairedness and sequence lengths of m_read_vec[r], which
+    // Edge::ext_len (src/Edge.h:220-275) reads through the edge's read pointers; the tip flags (Read::set_tip) go to tip_reads
+    void removeTips(unsigned int max_tip_len, const hc_read_geom* reads, size_t n_reads, hc_tip_counts* counts = nullptr);
+    // src/GraphAlgos.cpp:835-936 (with :714-743, :746-833); adj_out is left in target order, as sortAdjOut leaves it
+    void removeBranches(hc_branch_counts* counts = nullptr);
     double checkEdge(node_id_t v, node_id_t w, bool reverse_allowed) const;                   // :233-259
     // :608-719 (--add_duplicates; called at the end of construct_edges, EdgeCalculator.cpp:650-652): every edge once more
     // between the vertices of the reverse-complemented reads.  The mirrored edges carry no reverse offsets and no
@@ -155,8 +160,11 @@ public:
     std::vector<ArenaList<node_id_t>> adj_in;
     std::vector<uint8_t> inclusions;                      // boost::dynamic_bitset in the reference
     std::vector<std::vector<Edge>> inclusion_edges;       // removeInclusions' groups (for FNO1)
+    std::vector<Edge> branching_edges;                    // what removeTips / removeBranches removed, in removal order (for FNO)
+    std::vector<uint8_t> tip_reads;                       // Read::is_tip() by read index (Read::m_is_tip in the reference)
 
 private:
+    uint64_t sortAdjOut();      // src/GraphAlgos.cpp:806-833
     void ensure_slots() const;  // after adopt_csr the index is built lazily
     mutable EdgeSlotIndex slots;  // kept in step with adj_out by addEdge / removeEdgeWithOri
     mutable bool slots_valid = true;

@@ -465,6 +465,31 @@ int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t 
     return HC_OK;
 }
 
+int hc_host_graph_remove_tips(hc_host_graph* g, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts) {
+    if (!g || (n_reads && !reads)) return set_last_error(HC_ERR_ARG, "hc_host_graph_remove_tips: null");
+    return guarded("removeTips", [&] { g->graph->removeTips(max_tip_len, reads, n_reads, counts); });
+}
+
+int hc_host_graph_remove_branches(hc_host_graph* g, hc_branch_counts* counts) {
+    if (!g) return set_last_error(HC_ERR_ARG, "hc_host_graph_remove_branches: null");
+    return guarded("removeBranches", [&] { g->graph->removeBranches(counts); });
+}
+
+int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint64_t cap, uint64_t* n_out) {
+    if (!g || !n_out) return set_last_error(HC_ERR_ARG, "hc_host_graph_get_branching_edges: null");
+    const auto& b = g->graph->branching_edges;
+    for (size_t k = 0; k < b.size() && k < cap && edges; k++) fill_edge_rec(b[k], edges[k]);
+    *n_out = b.size();
+    return HC_OK;
+}
+
+int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads) {
+    if (!g || (n_reads && !is_tip)) return set_last_error(HC_ERR_ARG, "hc_host_graph_get_tip_reads: null");
+    const auto& t = g->graph->tip_reads;
+    for (uint64_t r = 0; r < n_reads; r++) is_tip[r] = r < t.size() ? t[r] : 0;
+    return HC_OK;
+}
+
 int hc_host_graph_free(hc_host_graph* g) {
     delete g;
     return HC_OK;

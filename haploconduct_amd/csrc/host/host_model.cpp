@@ -16,10 +16,12 @@
 #include <fstream>
 #include <sstream>
 #include <functional>
+#include <list>
 #include <thread>
 
 #include "../../../include/hcedge.h"
 #include "Edge.h"
+#include "ExtLen.h"
 #include "EdgeCalculator.h"
 #include "FastqStorage.h"
 #include "Overlap.h"
@@ -1389,14 +1391,10 @@ SortedLists lists_of(const std::vector<uint32_t>& src, const std::vector<uint32_
 }
 }  // namespace
 
-void OverlapGraph::removeTransitiveEdges(unsigned remove_trans, bool branch_reduction, hc_clean_counts* counts) {  // :938-1077
-    if (counts) {
-        memset(counts, 0, sizeof *counts);
-        counts->edges_before = counts->edges_after = edge_count;
-    }
-    if (remove_trans == 0) return;
+// sortAdjOut (:806-833): adj_out becomes its target-sorted form, by std::sort; returns the number of lists of more than 16
+// entries that repeat a target (where std::sort's order can differ from a stable sort's)
+uint64_t OverlapGraph::sortAdjOut() {
     const size_t V = adj_out.size();
-    // sortAdjOut (:806-833): adj_out becomes its target-sorted form, by std::sort
     uint64_t n_tied = 0;
     std::vector<uint32_t> targets, perm;
     std::vector<Edge> tmp;
@@ -1415,6 +1413,17 @@ void OverlapGraph::removeTransitiveEdges(unsigned remove_trans, bool branch_redu
         }
         if (repeated && n > 16) n_tied++;
     }
+    return n_tied;
+}
+
+void OverlapGraph::removeTransitiveEdges(unsigned remove_trans, bool branch_reduction, hc_clean_counts* counts) {  // :938-1077
+    if (counts) {
+        memset(counts, 0, sizeof *counts);
+        counts->edges_before = counts->edges_after = edge_count;
+    }
+    if (remove_trans == 0) return;
+    const size_t V = adj_out.size();
+    const uint64_t n_tied = sortAdjOut();
     // level 0: every edge in (source, target) order; sortAdjLists(adj_in) holds the same pairs as the out-lists
     std::vector<uint32_t> src, tgt, pos;
     for (size_t v = 0; v < V; v++)
@@ -1491,6 +1500,162 @@ void OverlapGraph::removeTransitiveEdges(unsigned remove_trans, bool branch_redu
         counts->transitive_count = transitive_count;
         counts->del_count = del_count;
         counts->rebuilt = rebuild ? 1 : 0;
+        counts->n_tied_lists = n_tied;
+    }
+}
+
+// ---- removeTips (:543-637) and removeBranches (:835-936) ------------------------------------------------------------
+
+void OverlapGraph::removeTips(unsigned int max_tip_len, const hc_read_geom* reads, size_t n_reads, hc_tip_counts* counts) {
+    for (const auto& list : adj_out)
+        for (const Edge& e : list)
+            if (e.get_read(1)->get_index() >= n_reads || e.get_read(2)->get_index() >= n_reads)
+                throw FatalError{HC_ERR_ARG, "removeTips: a read index is not below n_reads"};
+    if (tip_reads.size() < n_reads) tip_reads.resize(n_reads, 0);
+    auto ext_len = [&](const Edge& e, bool forward) {  // Edge::ext_len (src/Edge.h:220-275) on the read table
+        hc_edge_rec r;
+        memset(&r, 0, sizeof r);
+        r.pos1 = e.get_pos(1), r.pos2 = e.get_pos(2);
+        r.ori2 = e.get_ori(2), r.ord = (uint8_t)e.get_ord();
+        r.len0 = e.get_len(0), r.len1 = e.get_len(1), r.len2 = e.get_len(2);
+        return edge_ext_len(r, reads[e.get_read(1)->get_index()], reads[e.get_read(2)->get_index()], forward);
+    };
+    const unsigned int before = edge_count;
+    unsigned int tip_count = 0;
+    std::set<std::pair<node_id_t, node_id_t>> edges_to_remove;
+    for (node_id_t i = 0; i < adj_out.size(); i++) {  // outgoing tips
+        if (adj_out[i].size() <= 1) continue;
+        bool alltips = true;
+        std::vector<std::pair<node_id_t, node_id_t>> local_tips;
+        std::vector<size_t> local_tip_reads;
+        for (const Edge& e : adj_out[i]) {
+            const node_id_t v1 = e.get_vertex(2);
+            if (adj_out.at(v1).empty()) {
+                const unsigned int ext = ext_len(e, true);
+                if (ext == 0) {  // inclusion edge: always a tip
+                    tip_count++;
+                    edges_to_remove.insert(std::make_pair(i, v1));
+                    tip_reads[e.get_read(2)->get_index()] = 1;
+                } else if (ext < max_tip_len) {
+                    tip_count++;
+                    local_tips.push_back(std::make_pair(i, v1));
+                    local_tip_reads.push_back(e.get_read(2)->get_index());
+                }
+            } else {
+                alltips = false;
+            }
+        }
+        if (!alltips) {
+            edges_to_remove.insert(local_tips.begin(), local_tips.end());
+            for (size_t r : local_tip_reads) tip_reads[r] = 1;
+        }
+    }
+    const unsigned int out_tip_count = tip_count;
+    for (node_id_t i = 0; i < adj_in.size(); i++) {  // incoming tips
+        if (adj_in[i].size() <= 1) continue;
+        bool alltips = true;
+        std::vector<std::pair<node_id_t, node_id_t>> local_tips;
+        std::vector<size_t> local_tip_reads;
+        for (node_id_t v1 : adj_in[i]) {
+            if (adj_in.at(v1).empty()) {
+                const Edge* e = getEdgeInfo(v1, i);
+                const unsigned int ext = ext_len(*e, false);
+                if (ext == 0) {
+                    tip_count++;
+                    edges_to_remove.insert(std::make_pair(v1, i));
+                    tip_reads[e->get_read(1)->get_index()] = 1;
+                } else if (ext < max_tip_len) {
+                    tip_count++;
+                    local_tips.push_back(std::make_pair(v1, i));
+                    local_tip_reads.push_back(e->get_read(1)->get_index());
+                }
+            } else {
+                alltips = false;
+            }
+        }
+        if (!alltips) {
+            edges_to_remove.insert(local_tips.begin(), local_tips.end());
+            for (size_t r : local_tip_reads) tip_reads[r] = 1;
+        }
+    }
+    for (const auto& p : edges_to_remove) branching_edges.push_back(removeEdge(p.first, p.second));
+    if (counts) {
+        memset(counts, 0, sizeof *counts);
+        counts->edges_before = before;
+        counts->edges_after = edge_count;
+        counts->out_tip_count = out_tip_count;
+        counts->tip_count = tip_count;
+        counts->n_removed = edges_to_remove.size();
+        for (uint8_t t : tip_reads) counts->n_tip_reads += t != 0;
+    }
+}
+
+void OverlapGraph::removeBranches(hc_branch_counts* counts) {
+    const size_t V = adj_out.size();
+    const unsigned int before = edge_count;
+    const uint64_t n_tied = sortAdjOut();  // adj_out stays in target order (:831)
+    std::vector<uint32_t> src, tgt;
+    for (size_t v = 0; v < V; v++)
+        for (const Edge& e : adj_out[v]) src.push_back((uint32_t)v), tgt.push_back((uint32_t)e.get_vertex(2));
+    // findTransEdges(..., removeTrans = true) (:847): the lists of the edges that are not transitive, repeats kept
+    const std::vector<uint8_t> t = find_trans_edges(lists_of(src, tgt, V));
+    std::vector<std::vector<node_id_t>> new_adj_in(V), new_adj_out(V);
+    uint64_t kept = 0;
+    for (size_t i = 0; i < t.size(); i++)
+        if (!t[i]) {
+            new_adj_out[src[i]].push_back(tgt[i]);
+            new_adj_in[tgt[i]].push_back(src[i]);
+            kept++;
+        }
+    // findBranchfreeGraph (:714-743) and the two clear() loops (:855-862), neither list updated for the other
+    uint64_t n_out_branch = 0, n_in_branch = 0;
+    std::vector<uint8_t> remove_out(V, 0), remove_in(V, 0);
+    for (size_t v = 0; v < V; v++) {
+        if (new_adj_out[v].size() > 1) remove_out[v] = 1, n_out_branch++;
+        if (new_adj_in[v].size() > 1) remove_in[v] = 1, n_in_branch++;
+    }
+    for (size_t v = 0; v < V; v++) {
+        if (remove_in[v]) new_adj_in[v].clear();
+        if (remove_out[v]) new_adj_out[v].clear();
+    }
+    // connected components of the branch-free graph (:865-912)
+    std::vector<unsigned int> component(V, 0);
+    std::vector<uint8_t> visited(V, 0);
+    unsigned int current_component = 0;
+    for (node_id_t i = 0; i < V; i++) {
+        if (visited[i]) continue;
+        std::list<node_id_t> stack;
+        stack.push_back(i);
+        visited[i] = 1;
+        while (!stack.empty()) {
+            const node_id_t node = stack.front();
+            stack.pop_front();
+            component[node] = current_component;
+            for (node_id_t out_nb : new_adj_out[node]) {
+                if (std::count(new_adj_in[out_nb].begin(), new_adj_in[out_nb].end(), node) == 0) continue;
+                if (!visited[out_nb]) stack.push_back(out_nb), visited[out_nb] = 1;
+            }
+            for (node_id_t in_nb : new_adj_in[node]) {
+                if (std::count(new_adj_out[in_nb].begin(), new_adj_out[in_nb].end(), node) == 0) continue;
+                if (!visited[in_nb]) stack.push_back(in_nb), visited[in_nb] = 1;
+            }
+        }
+        current_component++;
+    }
+    // every edge between two components leaves (:917-931)
+    std::vector<std::pair<node_id_t, node_id_t>> edges_to_remove;
+    for (size_t i = 0; i < src.size(); i++)
+        if (component[src[i]] != component[tgt[i]]) edges_to_remove.push_back(std::make_pair(src[i], tgt[i]));
+    for (const auto& p : edges_to_remove) branching_edges.push_back(removeEdge(p.first, p.second));
+    if (counts) {
+        memset(counts, 0, sizeof *counts);
+        counts->edges_before = before;
+        counts->edges_after = edge_count;
+        counts->n_removed = edges_to_remove.size();
+        counts->transitive_kept = kept;
+        counts->n_out_branch = n_out_branch;
+        counts->n_in_branch = n_in_branch;
+        counts->n_components = current_component;
         counts->n_tied_lists = n_tied;
     }
 }

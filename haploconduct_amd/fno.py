@@ -220,3 +220,12 @@ def edges_from_records(recs, add_duplicates_reads=None):
     e["ori1"], e["ori2"] = recs["ori1"], recs["ori2"]
     e["ord"] = recs["ord"]
     return e
+
+
+def edges_from_graph(recs):
+    """Graph records (host.EDGE_DTYPE: hc_graph_fetch, hc_graph_fetch_branching_edges, HostGraph.get / branching_edges) ->
+    FNO_EDGE_DTYPE, field by field: what Fno1Input takes as graph_edges and branching_edges."""
+    e = np.zeros(len(recs), FNO_EDGE_DTYPE)
+    for f in ("v1", "v2", "score", "pos1", "pos2", "len1", "len2", "perc", "ord", "ori1", "ori2"):
+        e[f] = recs[f]
+    return e

@@ -14,6 +14,9 @@ EDGE_DTYPE = np.dtype(
      ("ori1", "u1"), ("ori2", "u1"), ("ord", "u1"), ("pad", "u1"), ("read1", "<u4"), ("read2", "<u4"), ("_p2", "<u4"),
      ("v1", "<u8"), ("v2", "<u8"), ("perc", "<i4"), ("len0", "<i4"), ("len1", "<i4"), ("len2", "<i4")], align=False)
 assert EDGE_DTYPE.itemsize == 80
+# hc_read_geom (include/hcedge.h): what Edge::ext_len reads of a read, by read index
+READ_GEOM_DTYPE = np.dtype([("len1", "<u4"), ("len2", "<u4"), ("paired", "u1"), ("pad", "u1", (3,))], align=False)
+assert READ_GEOM_DTYPE.itemsize == 12
 
 
 class hc_ec_paths(C.Structure):
@@ -90,6 +93,10 @@ _sig = {
     "hc_host_graph_remove_inclusions": (C.c_int, [_vp]),
     "hc_host_graph_remove_transitive_edges": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(N.hc_clean_counts)]),
     "hc_host_graph_get_inclusion_edges": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hc_host_graph_remove_tips": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(N.hc_tip_counts)]),
+    "hc_host_graph_remove_branches": (C.c_int, [_vp, C.POINTER(N.hc_branch_counts)]),
+    "hc_host_graph_get_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "hc_host_graph_get_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(N.lib, _name)
@@ -278,6 +285,35 @@ class HostGraph:
         N.check(N.lib.hc_host_graph_get_inclusion_edges(self._h, off.ctypes.data, off.size, out.ctypes.data if out.size else None, out.size,
                                                         C.byref(ng), C.byref(n)), "hc_host_graph_get_inclusion_edges")
         return off, out
+
+    def remove_tips(self, max_tip_len, read_geom):
+        """OverlapGraph::removeTips (src/GraphAlgos.cpp:543-637); read_geom (READ_GEOM_DTYPE) by read index.  Returns hc_tip_counts as a dict."""
+        rg = np.ascontiguousarray(read_geom, dtype=READ_GEOM_DTYPE)
+        c = N.hc_tip_counts()
+        N.check(N.lib.hc_host_graph_remove_tips(self._h, max_tip_len, rg.ctypes.data if rg.size else None, rg.shape[0], C.byref(c)),
+                "hc_host_graph_remove_tips")
+        return c.as_dict()
+
+    def remove_branches(self):
+        """OverlapGraph::removeBranches (src/GraphAlgos.cpp:835-936); returns hc_branch_counts as a dict."""
+        c = N.hc_branch_counts()
+        N.check(N.lib.hc_host_graph_remove_branches(self._h, C.byref(c)), "hc_host_graph_remove_branches")
+        return c.as_dict()
+
+    def branching_edges(self):
+        """OverlapGraph::branching_edges: what removeTips / removeBranches removed so far, in removal order."""
+        n = C.c_uint64()
+        N.check(N.lib.hc_host_graph_get_branching_edges(self._h, None, 0, C.byref(n)), "hc_host_graph_get_branching_edges")
+        out = np.zeros(n.value, dtype=EDGE_DTYPE)
+        if out.size:
+            N.check(N.lib.hc_host_graph_get_branching_edges(self._h, out.ctypes.data, out.size, C.byref(n)), "hc_host_graph_get_branching_edges")
+        return out
+
+    def tip_reads(self, n_reads):
+        """Read::is_tip() of reads [0, n_reads) as bytes."""
+        out = np.zeros(n_reads, np.uint8)
+        N.check(N.lib.hc_host_graph_get_tip_reads(self._h, out.ctypes.data if n_reads else None, n_reads), "hc_host_graph_get_tip_reads")
+        return out
 
     def get(self):
         n = C.c_uint64()

@@ -302,6 +302,39 @@ class EdgeScorer:
                                                      ne.value, C.byref(ng), C.byref(ne)), "hc_graph_fetch_inclusion_edges")
         return gv, off, out
 
+    def graph_remove_tips(self, max_tip_len, read_geom):
+        """hc_graph_remove_tips: OverlapGraph::removeTips on the device graph; read_geom (READ_GEOM_DTYPE) is indexed by
+        the records' read1 / read2.  Returns the counts."""
+        from .host import READ_GEOM_DTYPE
+
+        rg = np.ascontiguousarray(read_geom, dtype=READ_GEOM_DTYPE)
+        c = N.hc_tip_counts()
+        N.check(N.lib.hc_graph_remove_tips(self._ctx, max_tip_len, _ptr(rg) if rg.size else None, rg.shape[0], C.byref(c)), "hc_graph_remove_tips")
+        return c.as_dict()
+
+    def graph_remove_branches(self):
+        """hc_graph_remove_branches: OverlapGraph::removeBranches on the device graph; returns the counts."""
+        c = N.hc_branch_counts()
+        N.check(N.lib.hc_graph_remove_branches(self._ctx, C.byref(c)), "hc_graph_remove_branches")
+        return c.as_dict()
+
+    def graph_branching_edges(self):
+        """hc_graph_fetch_branching_edges: what removeTips / removeBranches removed so far, in removal order (EDGE_DTYPE)."""
+        from .host import EDGE_DTYPE
+
+        n = C.c_uint64()
+        N.check(N.lib.hc_graph_fetch_branching_edges(self._ctx, None, 0, C.byref(n)), "hc_graph_fetch_branching_edges")
+        out = np.zeros(n.value, EDGE_DTYPE)
+        if out.size:
+            N.check(N.lib.hc_graph_fetch_branching_edges(self._ctx, _ptr(out), out.size, C.byref(n)), "hc_graph_fetch_branching_edges")
+        return out
+
+    def graph_tip_reads(self, n_reads):
+        """hc_graph_fetch_tip_reads: Read::is_tip() of reads [0, n_reads) as bytes."""
+        out = np.zeros(n_reads, np.uint8)
+        N.check(N.lib.hc_graph_fetch_tip_reads(self._ctx, _ptr(out) if n_reads else None, n_reads), "hc_graph_fetch_tip_reads")
+        return out
+
     def graph_fetch(self):
         """hc_graph_fetch of the graph the device holds: edges, out_off, in_nodes, in_off, seq, inclusions."""
         from .host import EDGE_DTYPE

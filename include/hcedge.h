@@ -577,6 +577,48 @@ int hc_graph_remove_transitive(hc_ctx* ctx, uint32_t remove_trans, uint32_t bran
 int hc_graph_fetch_inclusion_edges(hc_ctx* ctx, uint32_t* group_vertex, uint64_t* group_off, hc_edge_rec* edges, uint64_t cap,
                                    uint64_t* n_groups, uint64_t* n_edges);
 
+/* ---- removeTips + removeBranches on the device graph ---------------------------------------------------------------
+ * OverlapGraph::removeTips (src/GraphAlgos.cpp:543-637) and OverlapGraph::removeBranches (:835-936), the two steps between
+ * removeTransitiveEdges and the second sortEdges of an iteration (src/ViralQuasispecies.cpp:297-350).  Both run on the graph
+ * the context holds, refuse what the two calls above refuse, and append the records they remove, in the reference's removal
+ * order, to OverlapGraph::branching_edges (:635, :930), which stays on the device until the next hc_graph_load /
+ * hc_graph_resolve and is what hc_fno1_run takes as branching_edges.  The four cleaning calls compose in any order. */
+typedef struct hc_read_geom {
+    uint32_t len1, len2; /* m_seq1.size(), m_seq2.size() (src/Read.h:30)   */
+    uint8_t paired, pad[3]; /* Read::is_paired() (:114)                    */
+} hc_read_geom;
+typedef struct hc_tip_counts {
+    uint64_t edges_before, edges_after;
+    uint64_t out_tip_count; /* tip_count after the first loop  (:588)         */
+    uint64_t tip_count;     /* after the second               (:628)          */
+    uint64_t n_removed;     /* |edges_to_remove| (a std::set of pairs)        */
+    uint64_t n_tip_reads;   /* reads with Read::is_tip() afterwards           */
+} hc_tip_counts;
+typedef struct hc_branch_counts {
+    uint64_t edges_before, edges_after, n_removed;
+    uint64_t transitive_kept;           /* findTransEdges' "edges kept" (:773)               */
+    uint64_t n_out_branch, n_in_branch; /* remove_out.size(), remove_in.size() (:740-741)    */
+    uint64_t n_components;              /* current_component (:914)                          */
+    uint64_t n_tied_lists;              /* as hc_clean_counts.n_tied_lists                   */
+    uint64_t cc_rounds;                 /* launches of the component-labelling loop (0: the
+                                           labelling is one union-find pass and one compress pass) */
+} hc_branch_counts;
+/* removeTips with program_settings.max_tip_len as given.  reads[r] is the geometry of m_read_vec[r] (Edge::ext_len,
+ * src/Edge.h:220-275, reads the pairedness and sequence lengths of the edge's read1 / read2, which hc_edge_rec.read1 /
+ * read2 index — not the vertices: an --add_duplicates graph has two vertices per read).  Both loops read the graph as it
+ * is on entry; every pair of edges_to_remove then loses its first record in adj_out and its first entry in adj_in, in
+ * ascending (v, w) order; what remains keeps its order.  The tip flags (Read::set_tip) are per read and stay until the next
+ * hc_graph_load / hc_graph_resolve.  A record whose read1 / read2 is >= n_reads: HC_ERR_ARG, the graph untouched. */
+int hc_graph_remove_tips(hc_ctx* ctx, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts);
+/* removeBranches: adj_out is left in target order (sortAdjOut's side effect, std::sort's order where a list repeats a
+ * target), adj_in keeps its order; every record i -> j whose ends lie in different components of the branch-free reduced
+ * graph leaves, vertex ascending, in list order, with every copy of a repeated pair. */
+int hc_graph_remove_branches(hc_ctx* ctx, hc_branch_counts* counts);
+/* OverlapGraph::branching_edges so far: room for cap records; *n_edges is always set (a first call with cap 0 sizes it). */
+int hc_graph_fetch_branching_edges(hc_ctx* ctx, hc_edge_rec* edges, uint64_t cap, uint64_t* n_edges);
+/* Read::is_tip() of reads [0, n_reads): one byte each (reads no hc_graph_remove_tips call has seen: 0). */
+int hc_graph_fetch_tip_reads(hc_ctx* ctx, uint8_t* is_tip, uint64_t n_reads);
+
 /* PCI bus id of a device ("0000:c1:00.0"), for callers that place the host threads feeding it on its NUMA node
  * (/sys/bus/pci/devices/<id>/numa_node); the stage does (HC_NUMA=0 turns that off). */
 int hc_device_bus_id(int32_t device, char* bus_id, uint32_t cap);

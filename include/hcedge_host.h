@@ -207,6 +207,13 @@ int hc_host_graph_remove_transitive_edges(hc_host_graph* g, uint32_t remove_tran
  * buffers sizes them. */
 int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t off_cap, hc_edge_rec* edges, uint64_t cap, uint64_t* n_groups,
                                       uint64_t* n_out);
+/* OverlapGraph::removeTips (src/GraphAlgos.cpp:543-637) and OverlapGraph::removeBranches (:835-936) on the bare graph, with the
+ * contract of hc_graph_remove_tips / hc_graph_remove_branches (include/hcedge.h); counts may be NULL.  cc_rounds stays 0. */
+int hc_host_graph_remove_tips(hc_host_graph* g, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts);
+int hc_host_graph_remove_branches(hc_host_graph* g, hc_branch_counts* counts);
+/* OverlapGraph::branching_edges so far (room for cap records; *n_out is always set) and Read::is_tip() of reads [0, n_reads). */
+int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint64_t cap, uint64_t* n_out);
+int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads);
 int hc_host_graph_free(hc_host_graph* g);
 
 /* Super-read consensus on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts): include/hcsr.h,
