@@ -436,43 +436,105 @@ __host__ __device__ inline uint32_t coop_stage_base(uint32_t lut_bytes, uint32_t
     return (lut_bytes == 65536u && wg == kWideDmaLanes) ? 65536u : (lut_bytes + 128u + 1023u) & ~1023u;
 }
 
+// What the stage and the multi-GPU collection need of a batch, produced by the scoring kernel itself: every record that
+// is not dropped is appended, tagged with base_index + its position in the batch, to `rows`; *count is the number of
+// appended rows (it may exceed cap: overflow, nothing is written beyond cap).  One atomic per workgroup and iteration
+// (same-address atomics serialise in L2: one per wave cost 0.1 ms per 2 M candidates); the rows arrive in no
+// particular order (they carry their index).  `rows` may be page-locked host memory mapped into the device's address
+// space (the stage: the few per cent of records that survive land where the host reads them, with no copy in
+// between); the counter always lives in device memory.
+struct RowSink {
+    hc_gather_row* rows;  // nullptr: no collection
+    unsigned long long* count;
+    uint64_t cap;
+    uint64_t base_index;
+    // the device parser's stage: the parsed line of every appended row travels with it (lines_out[pos] = lines_in[i])
+    const hc_line_rec* lines_in;
+    hc_line_rec* lines_out;
+    // Segment mode (the cooperative kernel's plain launches; hc_score_pack_device): every workgroup appends into a segment of its
+    // own — seg_rows rows at seg_buf + blockIdx.x * seg_rows, its place taken from a counter in LDS, so the waves neither meet at a
+    // barrier nor share a global atomic — and leaves its count in seg_count[blockIdx.x]; sink_compact_kernel then moves the
+    // segments into `rows` back to back and writes *count.  nullptr: rows are appended directly (one global atomic per workgroup
+    // and iteration behind two barriers, or one per wave in the bucketed launch).
+    // A row that finds its workgroup's segment full is not lost (round 4, ADVICE: one workgroup's share of the kept rows is not bounded
+    // by any multiple of the mean — bucketed launches pull pieces at their own pace, and a file may keep all its rows in one stretch):
+    // it goes to the SPILL area behind the segments (spill_cap rows, its place from one global counter per wave — the slow path, taken
+    // by skewed launches only), and sink_compact_kernel appends the spilled rows behind the segments' rows.  *count is then exactly
+    // the number of kept rows, above cap only when there were more kept rows than cap.
+    hc_gather_row* seg_buf;
+    uint32_t* seg_count;
+    uint32_t seg_rows;
+    uint32_t spill_cap;
+    hc_gather_row* spill_buf;
+    uint32_t* spill_count;  // zero when the launch starts (sink_compact_kernel re-arms the counter of the launch after the next)
+    // hc_comm_gate_device (the multi-GPU step): every workgroup of a cooperative launch adds one here when it starts, so that a gate
+    // kernel on the exchange's stream can hold the collective back until this launch's workgroups sit on their CUs.  nullptr: not counted.
+    unsigned long long* started;
+};
+
+// The arguments travel as ONE block (CoopArgs, launch_score fills it): the kernel-argument segment then has the struct's layout, and what
+// an iteration uses once — the class bands, merge_contigs, the row sink — is read from it with scalar loads WHERE it is used
+// (coop_args_here) instead of sitting in scalar registers across the whole loop.  Held live, the three by-value structs and the ticket and
+// locality state exceeded the scalar register file: 65 of them were spilled to vector-register lanes, which cost the blocks a candidate
+// passes ~40 v_readlane per 64 candidates.
+struct CoopArgs {
+    StoreView st;
+    ScoreParams prm;
+    const double* lut_g;
+    const void* in;
+    uint64_t n;
+    hc_result_rec* out;
+    const uint32_t* perm;
+    RowSink sink;
+    uint32_t* queue;  // not read (the bucketing's queue counter served round 3's global workgroup queue)
+};
+typedef const __attribute__((address_space(4))) CoopArgs* coop_args_ptr;
+// The kernel's argument block, as a pointer the compiler takes HERE: loads through it are scalar loads that cannot be hoisted out of the loop.
+__device__ __forceinline__ coop_args_ptr coop_args_here() {
+    coop_args_ptr p = (coop_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 // What a sub-overlap's walk leaves behind -> its result (x = (1/n) S, mismatches, n), or the exact re-scan when the sum came
 // out NaN (an invalid symbol inside the window, or next to it in the last chunk).
 // inv_n: StoreView::inv_n — 1.0 / n for every n a sub-overlap of this read set can count (built on the host: the same IEEE quotient the
 // device's division gives, :137; round 5: the division was ~15 VALU instructions per sub-overlap)
 template <typename SymT>
-__device__ __forceinline__ void finish_sub(const SymT* __restrict__ sym, uint32_t offA, uint32_t offB, uint32_t L, uint32_t fatal, uint32_t Kp, double S,
-                                           uint32_t skipped, uint32_t cm, bool packed, const double* __restrict__ inv_n, SubScore& out) {
-    out.x = -__builtin_inf();
-    out.mm = 1;
-    out.n = 1;
-    out.err = fatal;
-    if (L == 0) return;
+__device__ __forceinline__ void finish_sub(uint32_t offA, uint32_t offB, uint32_t L, uint32_t fatal, uint32_t Kp, double S,
+                                           uint32_t skipped, uint32_t cm, bool packed, SubScore& out) {
+    // Straight-line: every lane computes the common result and selects it (a lane without a sub-overlap has L = 0, S = 0.0 and cn = 0);
+    // early returns inside divergent branches left a merge block of register copies behind each of them.
     if (packed) {
         skipped >>= 2;
         cm >>= 2;
     }
-    if (S != S) {
-        const SubScore e = score_sub_slow<SymT>((const SymT*)((const char*)sym + offA), (const SymT*)((const char*)sym + offB), L, Kp);
-        out.x = e.x;
-        out.mm = e.mm;
-        out.n = e.n;
-        out.err |= e.err;
-        return;
-    }
-    if (S == __builtin_inf()) return;
     const uint32_t cn = 16u * ((L + 15u) >> 4) - skipped;
-    if (cn == 0) return;
-    out.x = inv_n[cn] * S;  // cn <= L + 15 <= the longest sequence + 15 < the table's length
-    out.mm = cm;
-    out.n = cn;
+    const bool rescan = L != 0u && S != S;
+    const bool ok = L != 0u && cn != 0u && S < __builtin_inf();  // (false for a NaN sum as well)
+    const double* __restrict__ inv_n = coop_args_here()->st.inv_n;  // (read where it is used: score_kernel_coop)
+    const double x = inv_n[ok ? cn : 0u] * S;  // cn <= L + 15 <= the longest sequence + 15 < the table's length; [0]: a slot nobody uses
+    out.x = ok ? x : -__builtin_inf();
+    out.mm = ok ? cm : 1u;
+    out.n = ok ? cn : 1u;
+    out.err = fatal;
+    if (__ballot(rescan) != 0ull) {  // wave-level: rare
+        if (rescan) {
+            const char* sym = (const char*)coop_args_here()->st.sym;
+            const SubScore e = score_sub_slow<SymT>((const SymT*)(sym + offA), (const SymT*)(sym + offB), L, Kp);
+            out.x = e.x;
+            out.mm = e.mm;
+            out.n = e.n;
+            out.err |= e.err;
+        }
+    }
 }
 
 // One sub-overlap of each of the wave's 64 candidates.  Called by all 64 lanes; a lane without one passes L = 0.
 // offA / offB: byte offsets of the window starts in the store; L: positions (sub_positions()).
 template <typename SymT, int LG, int DEPTH = 1>
-__device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint32_t oob, const SymT* __restrict__ sym, uint32_t stage, uint32_t offA,
-                                               uint32_t offB, uint32_t L, uint32_t fatal, uint32_t Kp, const double* __restrict__ inv_n, SubScore& out) {
+__device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint32_t oob, uint32_t stage, uint32_t offA, uint32_t offB, uint32_t L,
+                                               uint32_t fatal, uint32_t Kp, SubScore& out) {
     using T = Tr<SymT>;
     constexpr uint32_t kSymB = sizeof(SymT);
     constexpr int kChunks = 4 / kSymB;            // 16-symbol chunks per 64-byte row
@@ -575,7 +637,7 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        finish_sub<SymT>(sym, offA, offB, L, fatal, Kp, S == S ? S : 0.0, skipped, cm, kPacked, inv_n, out);
+        finish_sub<SymT>(offA, offB, L, fatal, Kp, S == S ? S : 0.0, skipped, cm, kPacked, out);
         return;
 #endif
         if (__ballot(Lb != 0u) != 0ull) {  // wave-uniform
@@ -629,7 +691,7 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
                 if (!more) break;
             }
         }
-        finish_sub<SymT>(sym, offA, offB, L, fatal, Kp, S, skipped, cm, kPacked, inv_n, out);
+        finish_sub<SymT>(offA, offB, L, fatal, Kp, S, skipped, cm, kPacked, out);
         return;
     }
     // DEPTH register sets of pieces in flight: set s holds the pieces of the step it is consumed in and is refilled, right
@@ -716,7 +778,7 @@ __device__ __forceinline__ void score_sub_coop(__amdgpu_buffer_rsrc_t rsrc, uint
             step(nA[DEPTH - 1], nB[DEPTH - 1], at + 64u);
         }
     }
-    finish_sub<SymT>(sym, offA, offB, L, fatal, Kp, S, skipped, cm, kPacked, inv_n, out);
+    finish_sub<SymT>(offA, offB, L, fatal, Kp, S, skipped, cm, kPacked, out);
 }
 
 // Result records are written once and read by nobody on the device: streamed past the caches, so they do not push the
@@ -740,44 +802,59 @@ __device__ __forceinline__ void store_result(hc_result_rec* __restrict__ out, ui
 // exp(x) > T  in x-space: 1 pass, 0 fail, 2 ambiguous
 __device__ __forceinline__ uint32_t band_test(double x, const Band& b) { return x > b.hi ? 1u : (x <= b.lo ? 0u : 2u); }
 
+// What the class of a candidate depends on besides its sub-overlaps' results (ScoreParams' share of it; the cooperative kernel reads it
+// from its argument block where it is used, score_kernel_coop)
+struct ClassParams {
+    Band edge, ov;
+    double merge_contigs;
+    uint32_t flags;
+};
+__device__ __forceinline__ ClassParams class_params(const ScoreParams& prm) { return ClassParams{prm.edge, prm.ov, prm.merge_contigs, prm.flags}; }
+
+// A value the compiler has to take HERE: what is computed from it stays inside the branch it is taken in.  (The fp64 divisions below sit in
+// branches that hardly ever run; the compiler used to if-convert them into the common path, ~30 VALU instructions per candidate.)
+__device__ __forceinline__ uint32_t taken_here(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // The tail of compute_overlap + the 3-way class of process_overlaps for one candidate whose sub-overlap
 // results are known: mismatch_rate = max of the two (:254), class in x-space (:404-413), result record.
+// ns <= 0 (no sub-overlap was scored: s1 = { -inf, 1, 1 }, s2 = { NaN, 0, 1 }): a malformed record is an error, a "skip" record (a line
+// dropped before scoring) a dropped result.
 template <bool STREAM = true>
-__device__ __forceinline__ hc_result_rec classify_and_store(const ScoreParams& prm, int ns, const SubScore& s1, const SubScore& s2,
+__device__ __forceinline__ hc_result_rec classify_and_store(const ClassParams& prm, int ns, const SubScore& s1, const SubScore& s2,
                                                             uint64_t i, hc_result_rec* __restrict__ out) {
     hc_result_rec res;
     // mismatch_rate = float(mismatch_count)/total_len (:132); std::max over the two (:254): the sub-overlap with the larger
     // rate supplies (mm, n).  Which one that is needs no division: for mm < 2^24 (exact as a float) and n < 2^26 two
     // different fractions mm/n <= 1 lie more than 2^-52 apart — two ulps at least — so their correctly rounded quotients
     // compare as the fractions do, i.e. as the cross products; equal fractions give equal quotients.
-    uint32_t mm = s1.mm, nn = s1.n;
-    if (ns == 2) {
-        bool second;
-        if ((s1.mm | s2.mm) < (1u << 24) && (s1.n | s2.n) < (1u << 26)) second = (uint64_t)s1.mm * s2.n < (uint64_t)s2.mm * s1.n;
-        else second = (double)(float)s1.mm / (double)s1.n < (double)(float)s2.mm / (double)s2.n;
-        if (second) {
-            mm = s2.mm;
-            nn = s2.n;
-        }
+    const bool two = ns == 2;
+    bool second = two && (uint64_t)s1.mm * s2.n < (uint64_t)s2.mm * s1.n;
+    const bool large = two && !((s1.mm | s2.mm) < (1u << 24) && (s1.n | s2.n) < (1u << 26));
+    if (__ballot(large) != 0ull) {  // wave-level: counts of a sequence longer than 2^24 symbols only
+        const uint32_t m1 = taken_here(s1.mm);
+        if (large) second = (double)(float)m1 / (double)s1.n < (double)(float)s2.mm / (double)s2.n;
     }
+    const uint32_t mm = second ? s2.mm : s1.mm, nn = second ? s2.n : s1.n;
     // :404-413 in x-space; flags bit0 / bit1: threshold < 0, every score (0 included) passes
     const bool e_all = prm.flags & 1u, o_all = prm.flags & 2u;
     uint32_t e = e_all ? 1u : band_test(s1.x, prm.edge);
     uint32_t o = o_all ? 1u : band_test(s1.x, prm.ov);
-    if (ns == 2) {
-        const uint32_t e2 = e_all ? 1u : band_test(s2.x, prm.edge), o2 = o_all ? 1u : band_test(s2.x, prm.ov);
+    {
+        const uint32_t e2 = (e_all || !two) ? 1u : band_test(s2.x, prm.edge), o2 = (o_all || !two) ? 1u : band_test(s2.x, prm.ov);
         e = (e == 0 || e2 == 0) ? 0u : ((e == 1 && e2 == 1) ? 1u : 2u);
         o = (o == 0 || o2 == 0) ? 0u : ((o == 1 && o2 == 1) ? 1u : 2u);
     }
-    uint32_t cls;
-    if (s1.err | s2.err) cls = HC_CLS_ERROR;
-    else if (e == 1) cls = HC_CLS_EDGE;
-    else if (e == 2) cls = HC_CLS_AMBIG;
     // mismatch_rate <= --merge_contigs; against the default 0 that is "no mismatch" (the rate is never negative)
-    else if (prm.merge_contigs == 0.0 ? mm == 0u : (double)(float)mm / (double)nn <= prm.merge_contigs) cls = HC_CLS_EDGE_MC;
-    else if (o == 1) cls = HC_CLS_NONEDGE;
-    else if (o == 2) cls = HC_CLS_AMBIG;
-    else cls = HC_CLS_DROP;
+    bool mc = mm == 0u;
+    if (prm.merge_contigs != 0.0) mc = (double)(float)taken_here(mm) / (double)nn <= prm.merge_contigs;  // kernel-argument-uniform branch
+    uint32_t cls = o == 1 ? HC_CLS_NONEDGE : (o == 2 ? HC_CLS_AMBIG : HC_CLS_DROP);
+    cls = mc ? HC_CLS_EDGE_MC : cls;
+    cls = e == 1 ? HC_CLS_EDGE : (e == 2 ? HC_CLS_AMBIG : cls);
+    cls = (s1.err | s2.err) ? HC_CLS_ERROR : cls;
+    cls = ns <= 0 ? (ns == 0 ? HC_CLS_ERROR : HC_CLS_DROP) : cls;
     res.x1 = s1.x;
     res.x2 = s2.x;
     res.mm = mm;
@@ -812,44 +889,8 @@ __device__ __forceinline__ hc_result_rec score_candidate(const ScoreParams& prm,
     const uint32_t L1 = ns == 2 ? sub_positions(sub1, prm.min_read_len) | (sub1.fatal << 31) : 0u;
     score_sub_wide<SymT, LG, G>(sym + sub0.offA + sub0.pos, sym + sub0.offB, sub_positions(sub0, prm.min_read_len), sub0.fatal, Kp, s1);
     if (ns == 2) score_sub_wide<SymT, LG, G>(a1, b1, L1 & 0x7FFFFFFFu, L1 >> 31, Kp, s2);
-    return classify_and_store(prm, ns, s1, s2, i, out);
+    return classify_and_store(class_params(prm), ns, s1, s2, i, out);
 }
-
-// What the stage and the multi-GPU collection need of a batch, produced by the scoring kernel itself: every record that
-// is not dropped is appended, tagged with base_index + its position in the batch, to `rows`; *count is the number of
-// appended rows (it may exceed cap: overflow, nothing is written beyond cap).  One atomic per workgroup and iteration
-// (same-address atomics serialise in L2: one per wave cost 0.1 ms per 2 M candidates); the rows arrive in no
-// particular order (they carry their index).  `rows` may be page-locked host memory mapped into the device's address
-// space (the stage: the few per cent of records that survive land where the host reads them, with no copy in
-// between); the counter always lives in device memory.
-struct RowSink {
-    hc_gather_row* rows;  // nullptr: no collection
-    unsigned long long* count;
-    uint64_t cap;
-    uint64_t base_index;
-    // the device parser's stage: the parsed line of every appended row travels with it (lines_out[pos] = lines_in[i])
-    const hc_line_rec* lines_in;
-    hc_line_rec* lines_out;
-    // Segment mode (the cooperative kernel's plain launches; hc_score_pack_device): every workgroup appends into a segment of its
-    // own — seg_rows rows at seg_buf + blockIdx.x * seg_rows, its place taken from a counter in LDS, so the waves neither meet at a
-    // barrier nor share a global atomic — and leaves its count in seg_count[blockIdx.x]; sink_compact_kernel then moves the
-    // segments into `rows` back to back and writes *count.  nullptr: rows are appended directly (one global atomic per workgroup
-    // and iteration behind two barriers, or one per wave in the bucketed launch).
-    // A row that finds its workgroup's segment full is not lost (round 4, ADVICE: one workgroup's share of the kept rows is not bounded
-    // by any multiple of the mean — bucketed launches pull pieces at their own pace, and a file may keep all its rows in one stretch):
-    // it goes to the SPILL area behind the segments (spill_cap rows, its place from one global counter per wave — the slow path, taken
-    // by skewed launches only), and sink_compact_kernel appends the spilled rows behind the segments' rows.  *count is then exactly
-    // the number of kept rows, above cap only when there were more kept rows than cap.
-    hc_gather_row* seg_buf;
-    uint32_t* seg_count;
-    uint32_t seg_rows;
-    uint32_t spill_cap;
-    hc_gather_row* spill_buf;
-    uint32_t* spill_count;  // zero when the launch starts (sink_compact_kernel re-arms the counter of the launch after the next)
-    // hc_comm_gate_device (the multi-GPU step): every workgroup of a cooperative launch adds one here when it starts, so that a gate
-    // kernel on the exchange's stream can hold the collective back until this launch's workgroups sit on their CUs.  nullptr: not counted.
-    unsigned long long* started;
-};
 
 // Called by ALL lanes of the workgroup (uniform control flow; `valid` = this lane scored candidate i).
 __device__ __forceinline__ void append_rows_block(const RowSink& sink, bool valid, const hc_result_rec& res, uint64_t i, uint32_t* lds4) {
@@ -1275,10 +1316,14 @@ __global__ __launch_bounds__(1024) void bucket_perm_kernel(StoreView st, uint32_
 // global queue (eight counters in memory, items of 512 candidates): C2 0.191 / 0.210 / 0.165 ms, C3-lite 1.525 / 1.531 / 1.482, C3
 // 7.04 / 6.67 / 6.55 (profiles/r04_wave_queue.txt, r04_wq_local.txt); the CUs hold 15.3 of their 16 waves on average instead of 12.7.
 template <typename SymT, int LG, int WG, bool SORT, bool DYN, int DEPTH = 1, bool WQ = false>
-__global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 2 : 1))) void score_kernel_coop(StoreView st, ScoreParams prm, const double* __restrict__ lut_g,
-                                                            const void* __restrict__ in, uint64_t n, hc_result_rec* __restrict__ out,
-                                                            const uint32_t* __restrict__ perm, RowSink sink, uint32_t* __restrict__ queue) {
+__global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 2 : 1))) void score_kernel_coop(CoopArgs args) {
     static_assert(SORT && (WQ || !DYN), "score_kernel_coop: no launch takes the unsorted form or the bucketed form without tickets");
+    const StoreView& st = args.st;
+    const ScoreParams& prm = args.prm;
+    const double* __restrict__ lut_g = args.lut_g;
+    const void* __restrict__ in = args.in;
+    uint64_t n = args.n;
+    const uint32_t* __restrict__ perm = args.perm;
     // DYN: n_hint = the launch's n, which the bucketing's geometry was laid out for (the device may know fewer records)
     const uint64_t n_hint = n;
     if (prm.n_dev) {
@@ -1296,7 +1341,7 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
     if (threadIdx.x == 0) {
         scratch[24] = 0;
         scratch[29] = 0;  // WQ: the workgroup's ticket counter
-        if (sink.started) atomicAdd(sink.started, 1ull);     // kernel-argument-uniform branch
+        if (args.sink.started) atomicAdd(args.sink.started, 1ull);     // kernel-argument-uniform branch
     }
     __syncthreads();
     // this wave's image (LDS byte address); the images start at a multiple of 1 KiB (the XOR swizzle needs whole 64-byte rows)
@@ -1304,9 +1349,7 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
     // (wave-uniform, and told so: the LDS-DMA form's M0 values and every image address + constant are then scalar work)
     const uint32_t stage = (uint32_t)__builtin_amdgcn_readfirstlane(
         (int)(stage_base + (threadIdx.x >> 6) * (DEPTH == 0 ? 2u * kStageBytesPerWave : kStageBytesPerWave)));  // DEPTH 0: LDS-DMA, A and B images
-    const SymT* sym = (const SymT*)st.sym;
     const uint32_t Kp = st.K + 2u;
-    const uint32_t fmt = prm.rec_fmt;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)st.sym, 0, (uint32_t)st.store_bytes, 0x00020000);
     const uint32_t oob = (uint32_t)st.store_bytes;  // the first offset the descriptor's range check rejects (no wrap-around at +16)
     const uint32_t tid = threadIdx.x;
@@ -1381,22 +1424,28 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
         // a sub-overlap as it travels: window starts as byte offsets into the store, positions | fatal << 31
         uint32_t a0 = 0, b0 = 0, l0 = 0, a1 = 0, b1 = 0, l1 = 0;
         if (slot < n) {
+            const coop_args_ptr ks = coop_args_here();  // the records' place and the store's geometry: read here, once per 64 candidates
             i = perm ? (uint64_t)perm[slot] : slot;
-            const Cand rec = load_cand(in, i, fmt);
-            if (st.regular) {  // kernel-argument-uniform: descriptors are arithmetic, 32-bit offsets, no `fatal` (hc_resolve.h)
-                ns = resolve_regular32<(int)sizeof(SymT)>(st, prm.min_read_len, rec, a0, b0, l0, a1, b1, l1);
+            const Cand rec = load_cand(ks->in, i, ks->prm.rec_fmt);
+            if (ks->st.regular) {  // kernel-argument-uniform: descriptors are arithmetic, 32-bit offsets, no `fatal` (hc_resolve.h)
+                const RegularGeom g{ks->st.n_reads, ks->st.n_single, ks->st.seq_syms, ks->st.ulen, ks->prm.min_read_len};
+                ns = resolve_regular32<(int)sizeof(SymT)>(g, rec, a0, b0, l0, a1, b1, l1);
             } else {
                 Sub sub0{}, sub1{};
-                ns = resolve<(int)sizeof(SymT)>(st, rec, sub0, sub1);
+                StoreView sv{};  // what resolve() reads of a store that is not regular
+                sv.reads = ks->st.reads;
+                sv.n_reads = ks->st.n_reads;
+                const uint32_t min_read_len = ks->prm.min_read_len;
+                ns = resolve<(int)sizeof(SymT)>(sv, rec, sub0, sub1);
                 if (ns >= 1) {
                     a0 = (uint32_t)((sub0.offA + sub0.pos) * sizeof(SymT));
                     b0 = (uint32_t)(sub0.offB * sizeof(SymT));
-                    l0 = sub_positions(sub0, prm.min_read_len) | (sub0.fatal << 31);
+                    l0 = sub_positions(sub0, min_read_len) | (sub0.fatal << 31);
                 }
                 if (ns == 2) {
                     a1 = (uint32_t)((sub1.offA + sub1.pos) * sizeof(SymT));
                     b1 = (uint32_t)(sub1.offB * sizeof(SymT));
-                    l1 = sub_positions(sub1, prm.min_read_len) | (sub1.fatal << 31);
+                    l1 = sub_positions(sub1, min_read_len) | (sub1.fatal << 31);
                 }
             }
         }
@@ -1442,13 +1491,13 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
             const u32x4 p0 = lds_load128(x + 16u * lane), p1 = lds_load128(x + 16u * (127u - lane));  // rank `lane`, then the other half mirrored
             wave_lds_order();
             SubScore r[2];
-            score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, sym, stage, p0[0], p0[1], p0[2] & 0x7FFFFFFFu, p0[2] >> 31, Kp, st.inv_n, r[0]);
+            score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, stage, p0[0], p0[1], p0[2] & 0x7FFFFFFFu, p0[2] >> 31, Kp, r[0]);
             r[1].x = -__builtin_inf();
             r[1].mm = 1;
             r[1].n = 1;
             r[1].err = p1[2] >> 31;
             if (__ballot((p1[2] & 0x7FFFFFFFu) != 0u) != 0ull)
-                score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, sym, stage, p1[0], p1[1], p1[2] & 0x7FFFFFFFu, p1[2] >> 31, Kp, st.inv_n, r[1]);
+                score_sub_coop<SymT, LG, DEPTH>(rsrc, oob, stage, p1[0], p1[1], p1[2] & 0x7FFFFFFFu, p1[2] >> 31, Kp, r[1]);
             wave_lds_order();
             lds_store128(x + 16u * p0[3], u32x4{(uint32_t)__double2loint(r[0].x), (uint32_t)__double2hiint(r[0].x), r[0].mm, r[0].n | (r[0].err << 31)});
             lds_store128(x + 16u * p1[3], u32x4{(uint32_t)__double2loint(r[1].x), (uint32_t)__double2hiint(r[1].x), r[1].mm, r[1].n | (r[1].err << 31)});
@@ -1470,28 +1519,26 @@ __global__ __launch_bounds__(WG, DEPTH == 2 ? 2 : (WG == 256 ? 4 : (WG == 512 ? 
             s2.n = 1;
             s2.err = 0;
         }
+        const coop_args_ptr ka = coop_args_here();
         hc_result_rec res;
         res.n_cls = 0;
         if (slot < n) {
-            if (ns <= 0) {  // malformed record: an error; "skip" record: a dropped result
-                res.x1 = -__builtin_inf();
-                res.x2 = __builtin_nan("");
-                res.mm = 1;
-                res.n_cls = 1u | ((ns == 0 ? HC_CLS_ERROR : HC_CLS_DROP) << 28);
-                store_result<!DYN>(out, i, res);
-            } else {
-                res = classify_and_store<!DYN>(prm, ns, s1, s2, i, out);
-            }
+            const ClassParams cp{Band{ka->prm.edge.lo, ka->prm.edge.hi}, Band{ka->prm.ov.lo, ka->prm.ov.hi}, ka->prm.merge_contigs, ka->prm.flags};
+            res = classify_and_store<!DYN>(cp, ns, s1, s2, i, ka->out);
         }
-        if (sink.rows) {  // kernel-argument-uniform branch
+        if (ka->sink.rows) {  // kernel-argument-uniform branch
+            const RowSink sink{ka->sink.rows,      ka->sink.count,     ka->sink.cap,      ka->sink.base_index, ka->sink.lines_in,
+                               ka->sink.lines_out, ka->sink.seg_buf,   ka->sink.seg_count, ka->sink.seg_rows,  ka->sink.spill_cap,
+                               ka->sink.spill_buf, ka->sink.spill_count, ka->sink.started};
             if (sink.seg_count) append_rows_segment(sink, slot < n, res, i, seg_counter);
             else if (DYN) append_rows_wave(sink, slot < n, res, i);
             else append_rows_block(sink, slot < n, res, i, scratch);
         }
     }
-    if (sink.rows && sink.seg_count) {  // kernel-argument-uniform: every wave of the workgroup leaves its loop and arrives here
+    const coop_args_ptr ke = coop_args_here();
+    if (ke->sink.rows && ke->sink.seg_count) {  // kernel-argument-uniform: every wave of the workgroup leaves its loop and arrives here
         __syncthreads();
-        if (threadIdx.x == 0) sink.seg_count[blockIdx.x] = scratch[24];
+        if (threadIdx.x == 0) ke->sink.seg_count[blockIdx.x] = scratch[24];
     }
 }
 
@@ -1725,8 +1772,10 @@ hipError_t launch_score(const ScorePlan& plan, const StoreView& st, ScoreParams 
     }
     if (k.wq) prm.pad = (prm.pad & 0xFFu) | (kTicketSteps << 8);
     uint32_t* queue = plan.bucketed ? b.bucket_queue : nullptr;
-    void* args[] = {(void*)&st, &prm, &lut_g, &in, &n, &out, &perm, &sink, &queue};  // (the per-lane kernels take the first eight)
-    const hipError_t le = hipLaunchKernel(k.fn, dim3(plan.blocks), dim3(k.wg), args, plan.lds, stream);
+    CoopArgs coop{st, prm, lut_g, in, n, out, perm, sink, queue};  // the cooperative kernels take one block
+    void* coop_args[] = {&coop};
+    void* lane_args[] = {(void*)&st, &prm, &lut_g, &in, &n, &out, &perm, &sink};
+    const hipError_t le = hipLaunchKernel(k.fn, dim3(plan.blocks), dim3(k.wg), k.coop ? coop_args : lane_args, plan.lds, stream);
     if (plan.segmented) {
         hipLaunchKernelGGL(sink_compact_kernel, dim3(plan.blocks), dim3(256), 0, stream, (const hc_gather_row*)b.seg_buf, (const uint32_t*)b.seg_count,
                            sink.seg_rows, plan.blocks, b.rows, (unsigned long long)b.cap, b.row_count, (const hc_gather_row*)sink.spill_buf,

@@ -145,45 +145,35 @@ __device__ __forceinline__ int resolve(const StoreView& st, const Cand& r, Sub& 
 // F(R, o) = o ? /1 : rc(/2) at base + (o ? 0 : 3 slot) and its back K(R, o) = o ? /2 : rc(/1) at base + (o ? slot : 2 slot)
 // ([/1 fwd][/2 fwd][/1 rc][/2 rc]); every length is `ulen`, so min(lenA - pos, lenB) = ulen - pos.  Round 5: the generic path cost ~215
 // VALU instructions per candidate of the kernel's 1 856 (profiles/r05_valu_attribution.txt).
+// Straight-line: every decision is a select and nothing returns early (an early return inside a divergent branch leaves a merge block of
+// register copies behind).  A record that is not scored — skip, ids out of range, read1 == read2, an order code other than '1' / '2' on a
+// p-p record — gets L0 = L1 = 0: its lane idles through both passes and the kernel writes the record's class from the return value alone.
+struct RegularGeom {  // what resolve_regular32 reads of StoreView and ScoreParams
+    uint32_t n_reads, n_single, seq_syms, ulen, min_read_len;
+};
 template <int SB>
-__device__ __forceinline__ int resolve_regular32(const StoreView& st, uint32_t min_read_len, const Cand& r, uint32_t& a0, uint32_t& b0, uint32_t& L0,
-                                                 uint32_t& a1, uint32_t& b1, uint32_t& L1) {
-    a0 = b0 = L0 = a1 = b1 = L1 = 0u;
-    if (r.skip) return -1;
-    if (r.read1 >= st.n_reads || r.read2 >= st.n_reads || r.read1 == r.read2) return 0;
+__device__ __forceinline__ int resolve_regular32(const RegularGeom& st, const Cand& r, uint32_t& a0, uint32_t& b0, uint32_t& L0, uint32_t& a1,
+                                                 uint32_t& b1, uint32_t& L1) {
     const uint32_t slot = st.seq_syms >> 1;
     const bool p1 = r.read1 >= st.n_single, p2 = r.read2 >= st.n_single;
+    const bool bad = r.read1 >= st.n_reads || r.read2 >= st.n_reads || r.read1 == r.read2 || (p1 && p2 && r.ord != '1' && r.ord != '2');
+    const int ns = r.skip ? -1 : (bad ? 0 : ((p1 || p2) ? 2 : 1));
     const uint32_t base1 = (p1 ? 2u * r.read1 - st.n_single : r.read1) * st.seq_syms;  // n_single + 2 (r - n_single)
     const uint32_t base2 = (p2 ? 2u * r.read2 - st.n_single : r.read2) * st.seq_syms;
     const uint32_t F1 = base1 + (r.ori1 ? 0u : (p1 ? 3u * slot : slot));
     const uint32_t F2 = base2 + (r.ori2 ? 0u : (p2 ? 3u * slot : slot));
-    const uint32_t ok = st.ulen >= min_read_len ? st.ulen : 0u;  // :82-84 (wave-uniform)
+    const uint32_t ok = st.ulen >= st.min_read_len ? st.ulen : 0u;  // :82-84 (wave-uniform)
     a0 = (F1 + r.pos1) * SB;
     b0 = F2 * SB;
-    L0 = r.pos1 < ok ? ok - r.pos1 : 0u;  // :76-79, :88
-    if (!p1 && !p2) return 1;
+    L0 = (ns >= 1 && r.pos1 < ok) ? ok - r.pos1 : 0u;  // :76-79, :88
     const uint32_t K1 = p1 ? base1 + (r.ori1 ? slot : 2u * slot) : F1;
     const uint32_t K2 = p2 ? base2 + (r.ori2 ? slot : 2u * slot) : F2;
-    uint32_t A, B;
-    if (!p1) {
-        A = F1;
-        B = K2;
-    } else if (!p2) {
-        A = F2;
-        B = K1;
-    } else if (r.ord == '1') {
-        A = K1;
-        B = K2;
-    } else if (r.ord == '2') {
-        A = K2;
-        B = K1;
-    } else {
-        return 0;
-    }
-    a1 = (A + r.pos2) * SB;
-    b1 = B * SB;
-    L1 = r.pos2 < ok ? ok - r.pos2 : 0u;
-    return 2;
+    // s-p: (S1, K2); p-s: (S2, K1); p-p: (K1, K2) for order '1', (K2, K1) for '2' — a single's K is its F
+    const bool swap = p1 && (!p2 || r.ord == '2');
+    a1 = ((swap ? K2 : K1) + r.pos2) * SB;
+    b1 = (swap ? K1 : K2) * SB;
+    L1 = (ns == 2 && r.pos2 < ok) ? ok - r.pos2 : 0u;
+    return ns;
 }
 
 __device__ __forceinline__ uint32_t sub_positions(const Sub& s, uint32_t min_read_len) {

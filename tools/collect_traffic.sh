@@ -17,7 +17,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export HC_WORKLOAD_CACHE=${HC_WORKLOAD_CACHE:-/tmp/hcw}
 B="python3 $R/bench.py --workload $W --steps 3 --warmup 1 --full --no-cpu-baseline --no-stage --also none"
-pass() { d=$1; shift; rocprofv3 "$@" --kernel-trace --output-format csv -d $O/$d -- $B > $O/$d.out 2> $O/$d.err || echo "pass $d failed" >&2; }
+# every pass under a time limit of its own; a pass that fails or runs out of time ends the collection (nothing more is started on that GPU)
+pass() { d=$1; shift; timeout -k 10 ${HC_PASS_TIMEOUT:-600} rocprofv3 "$@" --kernel-trace --output-format csv -d $O/$d -- $B > $O/$d.out 2> $O/$d.err || { echo "pass $d failed: stopping" >&2; exit 1; }; }
 # the duration pass traces >= 30 launches of the kernel and the file keeps their MEDIAN (round 3 kept the mean of nine, one of them an outlier)
 B_COUNTERS=$B
 B="python3 $R/bench.py --workload $W --steps 30 --warmup 2 --full --no-cpu-baseline --no-stage --also none"
