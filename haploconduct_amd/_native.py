@@ -99,10 +99,22 @@ class hc_sr_stats(C.Structure):
     _fields_ = [("n_columns", C.c_uint64), ("n_host_columns", C.c_uint64), ("ms_device", C.c_double), ("ms_host_finish", C.c_double)]
 
 
+class hc_sr_self_settings(C.Structure):
+    _fields_ = [("min_score", C.c_double), ("min_qual", C.c_double), ("min_overlap", C.c_uint32), ("n_threads", C.c_uint32)]
+
+
+class hc_sr_self_stats(C.Structure):
+    _fields_ = [("n_merged", C.c_uint64), ("n_host_pairs", C.c_uint64), ("n_offsets", C.c_uint64), ("ms_device", C.c_double), ("ms_host", C.c_double)]
+
+
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
 _sr_tail = [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]
+_sr_self_tail = [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_self_settings), _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p,
+                 C.POINTER(hc_sr_self_stats)]
 _sig = {
+    "hc_sr_merge_self_overlaps": (C.c_int, [_vp] + _sr_self_tail),
+    "hc_host_sr_merge_self_overlaps": (C.c_int, [C.POINTER(hc_settings)] + _sr_self_tail),
     "hc_sr_consensus": (C.c_int, [_vp] + _sr_tail),
     "hc_host_sr_consensus": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32] + _sr_tail),
     "hc_host_sr_column": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_double, _vp]),

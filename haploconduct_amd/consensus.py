@@ -1,6 +1,7 @@
 """Super-read consensus (include/hcsr.h): SRBuilder::consensus / consensus_pos (reference src/SRBuilder.cpp:289-535)
 for a batch of layouts.  Record views, the result type and the plumbing shared by EdgeScorer.sr_consensus (device)
-and host.sr_consensus (the host mirror)."""
+and host.sr_consensus (the host mirror); the same for the merge of self-overlapping paired super-reads
+(SRBuilder::merge_self_overlap, src/SRBuilder.cpp:872-955): EdgeScorer.sr_merge_self_overlaps / host.sr_merge_self_overlaps."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -92,3 +93,81 @@ def table(min_qual, n_q):
     t = np.zeros(SR_TABLE_BYTES, np.uint8)
     N.check(N.lib.hc_host_sr_table(float(min_qual), int(n_q), t.ctypes.data), "hc_host_sr_table")
     return t
+
+
+# ---- self-overlapping paired super-reads (hc_sr_merge_self_overlaps) ----------------------------------------------------
+SR_PAIR_DTYPE = np.dtype([("off1", "<u8"), ("off2", "<u8"), ("len1", "<u4"), ("len2", "<u4")], align=False)  # hc_sr_pair
+assert SR_PAIR_DTYPE.itemsize == 24
+SR_SELF_NONE, SR_SELF_MERGED, SR_SELF_BAD_PAIR, SR_SELF_BAD_SYMBOL = range(4)
+
+
+@dataclass
+class SrSelfResult:
+    overlap_pos: np.ndarray  # int32 per pair: the offset taken, or -1
+    score: np.ndarray        # float64 per pair: overlap_score at that offset, or 0
+    status: np.ndarray       # uint32 per pair: SR_SELF_*
+    out_off: np.ndarray      # uint64, n_pairs + 1
+    merged_seq: np.ndarray   # uint8, packed
+    merged_qual: np.ndarray  # uint8, packed
+    n_merged: int
+    n_host_pairs: int        # device call: pairs the host threads decided
+    n_offsets: int
+    ms_device: float
+    ms_host: float
+
+    def merged(self, i):
+        a, b = int(self.out_off[i]), int(self.out_off[i + 1])
+        return self.merged_seq[a:b].tobytes(), self.merged_qual[a:b].tobytes()
+
+
+def make_self_settings(min_score=0.99, min_qual=0.99, min_overlap=15, n_threads=1):
+    return N.hc_sr_self_settings(float(min_score), float(min_qual), int(min_overlap), int(n_threads))
+
+
+def pack_pairs(mates):
+    """[(seq1, qual1, seq2, qual2) as bytes] -> (seq, qual, pairs): the packed buffers hc_sr_consensus would have written."""
+    pairs = np.zeros(len(mates), SR_PAIR_DTYPE)
+    s, q, at = [], [], 0
+    for i, (s1, q1, s2, q2) in enumerate(mates):
+        pairs[i] = (at, at + len(s1), len(s1), len(s2))
+        s += [s1, s2]
+        q += [q1, q2]
+        at += len(s1) + len(s2)
+    return np.frombuffer(b"".join(s), np.uint8), np.frombuffer(b"".join(q), np.uint8), pairs
+
+
+def run_self(call, seq, qual, pairs, settings, count_first=True):
+    """call(seq, qual, n_bytes, pairs, n_pairs, settings_ref, pos, score, status, out_off, mseq, mqual, cap, n_out_ref, stats_ref) -> status.
+    count_first: ask with cap = 0, then fetch; otherwise one call with room for every pair merged at its first offset."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    pairs = np.ascontiguousarray(pairs, dtype=SR_PAIR_DTYPE)
+    if seq.size != qual.size:
+        raise ValueError("seq and qual differ in length")
+    n = pairs.size
+    pos = np.zeros(n, np.int32)
+    score = np.zeros(n, np.float64)
+    status = np.zeros(n, np.uint32)
+    out_off = np.zeros(n + 1, np.uint64)
+    n_out = C.c_uint64(0)
+    stats = N.hc_sr_self_stats()
+
+    def once(mseq, mqual, cap):
+        return call(_ptr(seq), _ptr(qual), seq.size, _ptr(pairs), n, C.byref(settings), _ptr(pos), _ptr(score), _ptr(status), out_off.ctypes.data,
+                    _ptr(mseq), _ptr(mqual), cap, C.byref(n_out), C.byref(stats))
+
+    empty = np.zeros(0, np.uint8)
+    if count_first:
+        rc = once(empty, empty, 0)
+        if rc != 0 and n_out.value == 0:
+            N.check(rc, "sr_merge_self_overlaps")
+        cap = int(n_out.value)
+    else:
+        cap = int(pairs["len1"].astype(np.int64).sum() + pairs["len2"].astype(np.int64).sum())
+    mseq = np.zeros(cap, np.uint8)
+    mqual = np.zeros(cap, np.uint8)
+    if cap or not count_first:
+        N.check(once(mseq, mqual, cap), "sr_merge_self_overlaps")
+    nb = int(n_out.value)
+    return SrSelfResult(pos, score, status, out_off, mseq[:nb], mqual[:nb], int(stats.n_merged), int(stats.n_host_pairs), int(stats.n_offsets),
+                        float(stats.ms_device), float(stats.ms_host))

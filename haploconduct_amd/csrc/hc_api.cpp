@@ -36,7 +36,7 @@ int set_last_error(int status, const std::string& what) { return fail(status, wh
 // In x that is |x - ln T| > 1.5 * 2^-52 (+ the error of log()).  Everything inside
 // [ln T - d, ln T + d], d = 2^-49 * max(1, |ln T|), is handed to the host libm
 // (HC_CLS_AMBIG); the band covers ~1e-13 of the x values that occur.
-static hc::Band make_band(double T) {
+static hc::Band make_band(double T, int log2_width = -49) {
     hc::Band b;
     const double inf = std::numeric_limits<double>::infinity();
     if (T != T) {  // NaN: `score > T` is never true
@@ -53,7 +53,7 @@ static hc::Band make_band(double T) {
         b.hi = inf;
     } else {
         const double lt = std::log(T);
-        const double d = std::ldexp(1.0, -49) * std::fmax(1.0, std::fabs(lt));
+        const double d = std::ldexp(1.0, log2_width) * std::fmax(1.0, std::fabs(lt));
         b.lo = lt - d;
         b.hi = lt + d;
     }
@@ -260,6 +260,16 @@ static bool build_lut(const std::vector<int>& phred, const std::vector<int>& wid
         }
     }
     return symmetric;
+}
+
+// for the other translation units of the library (hc_ctx.h): the self-overlap scan of hc_api_sr.cpp scores with the same table and the same band
+extern "C++" {
+namespace hc {
+Band threshold_band(double T, int log2_width) { return make_band(T, log2_width); }
+bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting, std::vector<double>& lut) {
+    return build_lut(phred, std::vector<int>(), mismatch_setting, 2, lut);
+}
+}  // namespace hc
 }
 
 int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,

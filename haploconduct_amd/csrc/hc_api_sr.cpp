@@ -2,10 +2,15 @@
 // batch of layouts on the device.  The host builds what depends on libm — the per-quality log10 terms and the table of one- and
 // two-member columns, once per read set and min_qual —, the kernels of hc_sr_kernels.hip do the rest, and the columns they could not
 // decide by comparisons come back as four sums that host threads finish with the reference's expressions (host/SrConsensus.h).
+// hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end of this file.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <atomic>
+#include <cmath>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -15,7 +20,9 @@
 #include "hc_ctx.h"
 #include "hc_prims.h"
 #include "hc_sr.h"
+#include "hc_sr_self.h"
 #include "host/SrConsensus.h"
+#include "host/SrSelfOverlap.h"
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
 
@@ -184,5 +191,233 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         stats->ms_device = (double)ms_a + ms_b;
         stats->ms_host_finish = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    return HC_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------------------------------------
+// hc_sr_merge_self_overlaps: the host checks the pairs and builds what depends on libm (the log p table of the batch's quality values, by
+// the scoring path's own builder; 1.0 / n; the consensus table), the scan kernel finds every pair's offset, the host decides the offsets
+// inside the guard band (host/SrSelfOverlap.h), the merge kernel writes the merged reads at the offsets of an exclusive sum.
+namespace {
+
+// `work(a, b)` over [0, n) in blocks, on up to n_threads threads
+template <typename F>
+void in_blocks(uint64_t n, uint64_t block, unsigned n_threads, F work) {
+    const uint64_t n_blocks = (n + block - 1) / block;
+    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_threads, 64, n_blocks}));
+    std::atomic<uint64_t> turn{0};
+    auto run = [&]() {
+        for (uint64_t b = turn.fetch_add(1); b < n_blocks; b = turn.fetch_add(1)) work(b * block, std::min(n, (b + 1) * block));
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < T; t++) th.emplace_back(run);
+    run();
+    for (auto& x : th) x.join();
+}
+
+}  // namespace
+
+extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair* pairs,
+                                         uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score,
+                                         uint32_t* status, uint64_t* out_off, uint8_t* merged_seq, uint8_t* merged_qual, uint64_t cap,
+                                         uint64_t* n_out, hc_sr_self_stats* stats) {
+    const char* me = "hc_sr_merge_self_overlaps: ";
+    if (!c || !settings || !out_off || !n_out || (n_pairs && (!pairs || !overlap_pos || !score || !status)) || (n_bytes && (!seq || !qual)))
+        return fail(HC_ERR_ARG, std::string(me) + "null argument");
+    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, std::string(me) + "min_qual is NaN");
+    if (n_pairs >= (1ull << 32) - 1) return fail(HC_ERR_ARG, std::string(me) + "more than 2^32 - 2 pairs");
+    if (stats) memset(stats, 0, sizeof *stats);
+    *n_out = 0;
+    out_off[0] = 0;
+    if (n_pairs == 0) return HC_OK;
+    HC_HIP(hipSetDevice(c->device));
+    const auto t_host0 = std::chrono::steady_clock::now();
+    double ms_host = 0;
+    const unsigned n_thr = std::max(1u, settings->n_threads);
+    // the pairs' checks and the quality values of the batch
+    std::vector<uint32_t> skip(n_pairs);
+    const uint64_t check_block = 1024, n_check_blocks = (n_pairs + check_block - 1) / check_block;
+    std::vector<std::array<uint8_t, 128>> seen(n_check_blocks);
+    std::vector<uint32_t> block_max(n_check_blocks, 0);
+    in_blocks(n_pairs, check_block, n_thr, [&](uint64_t a, uint64_t b) {
+        std::array<uint8_t, 128>& sn = seen[a / check_block];
+        sn.fill(0);
+        uint32_t mx = 0;
+        for (uint64_t i = a; i < b; i++) {
+            skip[i] = hc::srself::check_pair(seq, qual, n_bytes, pairs[i]);
+            if (skip[i]) continue;
+            const hc_sr_pair& P = pairs[i];
+            for (uint32_t k = 0; k < P.len1; k++) sn[qual[P.off1 + k] & 127u] = 1;
+            for (uint32_t k = 0; k < P.len2; k++) sn[qual[P.off2 + k] & 127u] = 1;
+            mx = std::max({mx, P.len1, P.len2});
+        }
+        block_max[a / check_block] = mx;
+    });
+    uint32_t max_len = 0, max_first = 0;
+    uint64_t n_offsets = 0, n_valid = 0;
+    uint8_t qs_seen[96] = {0};
+    for (uint64_t b = 0; b < n_check_blocks; b++) {
+        max_len = std::max(max_len, block_max[b]);
+        for (uint32_t q = 33; q <= 126; q++) qs_seen[q - 33] |= seen[b][q];
+    }
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        overlap_pos[i] = -1;
+        score[i] = 0;
+        status[i] = skip[i];
+        if (skip[i]) continue;
+        n_valid++;
+        const uint32_t f = hc::srself::first_offset(pairs[i].len1, settings->min_overlap);
+        n_offsets += f;
+        max_first = std::max(max_first, f);
+    }
+    if (stats) stats->n_offsets = n_offsets;
+    hc_ctx::SrSelf& S = c->sr_self;
+    hipStream_t s = c->stream;
+    std::vector<hc::SrSelfScan> res(n_pairs);
+    std::vector<uint64_t> len(n_pairs + 1, 0);
+    std::vector<int32_t> mpos(n_pairs, -1);
+    // pairs the host finishes: (pair, the offset its scan goes on from)
+    std::vector<std::pair<uint64_t, uint32_t>> host_pairs;
+    float ms_scan = 0, ms_merge = 0;
+    int rc = HC_OK;
+    if (n_valid && max_first) {
+        // tables: log p by the scoring path's builder for the batch's values (row = rank of the value), 1.0 / n, the consensus table
+        std::vector<int> phred;
+        std::vector<uint32_t> qs;
+        uint8_t qmap[256];
+        memset(qmap, 0, sizeof qmap);
+        for (uint32_t q = 0; q < hc::srself::kQ; q++) {
+            if (!qs_seen[q]) continue;
+            qmap[q + 33] = (uint8_t)phred.size();
+            phred.push_back((int)q);
+            qs.push_back(q);
+        }
+        std::vector<double> lut;
+        if (!hc::build_log_table_u16(phred, c->settings.mismatch, lut)) return fail(HC_ERR_STATE, std::string(me) + "the log table is not symmetric");
+        std::vector<double> inv_n((size_t)max_len + 1, 0.0);
+        for (uint32_t k = 1; k <= max_len; k++) inv_n[k] = 1.0 / (double)k;  // :137
+        if (!(S.table_valid && memcmp(&S.table_min_qual, &settings->min_qual, sizeof(double)) == 0 && memcmp(S.table_qs, qs_seen, sizeof qs_seen) == 0)) {
+            S.table_valid = false;
+            std::vector<uint8_t> table(HC_SR_TABLE_BYTES);
+            hc::sr::build_table(settings->min_qual, qs, table.data());
+            std::vector<double> terms(2 * hc::kSrQIdx, 0.0);
+            for (uint32_t q : qs) hc::sr::terms((int)q, terms[q], terms[hc::kSrQIdx + q]);
+            S.table_has_nan = memchr(table.data(), hc::sr::kEntryNaN, table.size()) != nullptr;
+            if ((rc = S.table.ensure(table.size())) || (rc = S.terms.ensure(terms.size() * sizeof(double)))) return rc;
+            HC_HIP(hipMemcpyAsync(S.table.p, table.data(), table.size(), hipMemcpyHostToDevice, s));
+            HC_HIP(hipMemcpyAsync(S.terms.p, terms.data(), terms.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            HC_HIP(hipStreamSynchronize(s));  // (the host vectors go out of scope)
+            S.table_valid = true;
+            S.table_min_qual = settings->min_qual;
+            memcpy(S.table_qs, qs_seen, sizeof qs_seen);
+        }
+        hc::SrSelfParams prm;
+        int log2_width = -49;
+        if (const char* e = getenv("HC_SR_SELF_BAND_LOG2")) {  // test knob: a wider guard band, so that the host-decided path runs
+            const int v = atoi(e);
+            if (v >= -60 && v <= -2) log2_width = v;
+        }
+        prm.band = hc::threshold_band(settings->min_score, log2_width);
+        prm.always = settings->min_score < 0 ? 1u : 0u;
+        prm.min_overlap = settings->min_overlap;
+        prm.min_read_len = c->settings.min_read_len;
+        prm.K = (uint32_t)phred.size();
+        prm.lut_doubles = (uint32_t)lut.size();
+        prm.inv_len = (uint32_t)inv_n.size();
+        const size_t scan_bytes = hc::prims::scan_temp_bytes(n_pairs + 1, sizeof(uint64_t));
+        if ((rc = S.seq.ensure(n_bytes)) || (rc = S.qual.ensure(n_bytes)) || (rc = S.pairs.ensure(n_pairs * sizeof(hc_sr_pair))) ||
+            (rc = S.skip.ensure(n_pairs * sizeof(uint32_t))) || (rc = S.qmap.ensure(256)) || (rc = S.lut.ensure(lut.size() * sizeof(double))) ||
+            (rc = S.inv_n.ensure(inv_n.size() * sizeof(double))) || (rc = S.res.ensure(n_pairs * sizeof(hc::SrSelfScan))) ||
+            (rc = S.len.ensure((n_pairs + 1) * sizeof(uint64_t))) || (rc = S.off.ensure((n_pairs + 1) * sizeof(uint64_t))) ||
+            (rc = S.mpos.ensure(n_pairs * sizeof(int32_t))) || (rc = S.temp.ensure(scan_bytes ? scan_bytes : 16)))
+            return rc;
+        ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+        HC_HIP(hipMemcpyAsync(S.seq.p, seq, n_bytes, hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.qual.p, qual, n_bytes, hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.pairs.p, pairs, n_pairs * sizeof(hc_sr_pair), hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.skip.p, skip.data(), n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.qmap.p, qmap, 256, hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.lut.p, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.inv_n.p, inv_n.data(), inv_n.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        const uint32_t lanes = 64u * std::max(1u, std::min(hc::kSelfMaxChunk / 64u, (max_first + 63u) / 64u));
+        HC_HIP(hipEventRecord(c->ev0, s));
+        HC_HIP(hc::sr_self_launch_scan(c->n_cu, lanes, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), S.pairs.as<hc_sr_pair>(), S.skip.as<uint32_t>(), n_pairs,
+                                       S.qmap.as<uint8_t>(), S.lut.as<double>(), S.inv_n.as<double>(), prm, S.res.as<hc::SrSelfScan>(), s));
+        HC_HIP(hipEventRecord(c->ev1, s));
+        HC_HIP(hipMemcpyAsync(res.data(), S.res.p, n_pairs * sizeof(hc::SrSelfScan), hipMemcpyDeviceToHost, s));
+        HC_HIP(hipStreamSynchronize(s));
+        HC_HIP(hipEventElapsedTime(&ms_scan, c->ev0, c->ev1));
+        for (uint64_t i = 0; i < n_pairs; i++) {
+            if (skip[i] || res[i].p < 0) continue;
+            if (res[i].kind == hc::kSelfHit && !S.table_has_nan) {
+                overlap_pos[i] = res[i].p;
+                score[i] = exp(res[i].x);  // :138
+                status[i] = HC_SR_SELF_MERGED;
+                len[i] = (uint64_t)pairs[i].len2 + (uint32_t)res[i].p;  // :890
+                mpos[i] = res[i].p;
+            } else {
+                host_pairs.emplace_back(i, (uint32_t)res[i].p);
+            }
+        }
+    }
+    // the host's share: the scan goes on from the offset in the band with the host's libm, as the mirror walks it
+    struct HostOut {
+        std::vector<uint8_t> seq, qual;
+    };
+    std::vector<HostOut> host_out(host_pairs.size());
+    if (!host_pairs.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const hc::srself::Tables T(c->settings.mismatch, c->settings.min_read_len);
+        in_blocks(host_pairs.size(), 1, n_thr, [&](uint64_t a, uint64_t b) {
+            for (uint64_t k = a; k < b; k++) {
+                const uint64_t i = host_pairs[k].first;
+                const hc_sr_pair& P = pairs[i];
+                const hc::srself::Mates M{seq + P.off1, qual + P.off1, seq + P.off2, qual + P.off2, P.len1, P.len2};
+                overlap_pos[i] = hc::srself::scan_pair(T, M, host_pairs[k].second, *settings, &score[i], host_out[k].seq, host_out[k].qual);
+                if (overlap_pos[i] < 0) continue;
+                status[i] = HC_SR_SELF_MERGED;
+                len[i] = host_out[k].seq.size();
+            }
+        });
+        ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    uint64_t total = 0, n_merged = 0;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        out_off[i] = total;
+        total += len[i];
+        n_merged += status[i] == HC_SR_SELF_MERGED;
+    }
+    out_off[n_pairs] = total;
+    *n_out = total;
+    if (stats) {
+        stats->n_merged = n_merged;
+        stats->n_host_pairs = host_pairs.size();
+        stats->ms_device = ms_scan;
+        stats->ms_host = ms_host;
+    }
+    if (total > cap || (total && (!merged_seq || !merged_qual)))
+        return fail(HC_ERR_ARG, std::string(me) + "merged_seq / merged_qual have no room (*n_out says how much is needed)");
+    if (total == 0) return HC_OK;
+    // the merged reads: offsets by an exclusive sum on the device, one lane per column
+    if ((rc = S.out_seq.ensure(total)) || (rc = S.out_qual.ensure(total))) return rc;
+    HC_HIP(hipMemcpyAsync(S.len.p, len.data(), (n_pairs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemcpyAsync(S.mpos.p, mpos.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HC_HIP(hipEventRecord(c->ev0, s));
+    HC_HIP(hc::prims::exclusive_sum(S.temp.p, S.temp.cap, S.len.as<uint64_t>(), S.off.as<uint64_t>(), n_pairs + 1, s));
+    HC_HIP(hc::sr_self_launch_merge(S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), S.pairs.as<hc_sr_pair>(), n_pairs, S.mpos.as<int32_t>(),
+                                    S.off.as<uint64_t>(), total, S.terms.as<double>(), S.table.as<uint8_t>(), S.out_seq.as<uint8_t>(),
+                                    S.out_qual.as<uint8_t>(), s));
+    HC_HIP(hipEventRecord(c->ev1, s));
+    HC_HIP(hipMemcpyAsync(merged_seq, S.out_seq.p, total, hipMemcpyDeviceToHost, s));
+    HC_HIP(hipMemcpyAsync(merged_qual, S.out_qual.p, total, hipMemcpyDeviceToHost, s));
+    HC_HIP(hipStreamSynchronize(s));
+    HC_HIP(hipEventElapsedTime(&ms_merge, c->ev0, c->ev1));
+    for (size_t k = 0; k < host_pairs.size(); k++) {  // the host's pairs are spliced in
+        const uint64_t i = host_pairs[k].first;
+        if (host_out[k].seq.empty()) continue;
+        memcpy(merged_seq + out_off[i], host_out[k].seq.data(), host_out[k].seq.size());
+        memcpy(merged_qual + out_off[i], host_out[k].qual.data(), host_out[k].qual.size());
+    }
+    if (stats) stats->ms_device = (double)ms_scan + ms_merge;
     return HC_OK;
 }

@@ -104,6 +104,11 @@ hipError_t launch_locality_index(const uint32_t* order, uint32_t n_reads, const 
                                  uint32_t* start, uint32_t* flag, uint32_t* perm, void* temp, size_t temp_bytes, hipStream_t stream);
 
 int set_last_error(int status, const std::string& what);  // thread-local text behind hc_last_error()
+// hc_api.cpp: the x-space image of a score threshold with a guard band of 2^log2_width relative width (-49: the scoring path's), and the
+// log-probability table of the scoring path in its 16-bit-symbol layout (hc_device.h: two triangles of (K + 2) rows) for the Phred values
+// `phred`; false: the table is not symmetric in the two qualities
+Band threshold_band(double T, int log2_width);
+bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting, std::vector<double>& lut);
 }  // namespace hc
 
 #define HC_HIP(call)                                                                                   \
@@ -262,6 +267,14 @@ struct hc_ctx {
         bool tables_valid = false;
         double table_min_qual = 0;
     } sr;
+    // self-overlap merge (hc_api_sr.cpp: hc_sr_merge_self_overlaps): grow-only scratch; the consensus table is rebuilt when min_qual or
+    // the batch's quality values change
+    struct SrSelf {
+        hc_scratch seq, qual, pairs, skip, qmap, lut, inv_n, res, len, off, mpos, temp, terms, table, out_seq, out_qual;
+        bool table_valid = false, table_has_nan = false;
+        double table_min_qual = 0;
+        uint8_t table_qs[96] = {0};  // which Q = byte - 33 the table was built for
+    } sr_self;
 };
 
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,

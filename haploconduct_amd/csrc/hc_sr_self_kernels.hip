@@ -1,0 +1,216 @@
+// hc_sr_self_kernels.hip — SRBuilder::merge_self_overlap (reference src/SRBuilder.cpp:872-955) for a batch of pairs on the device
+// (include/hcsr.h: hc_sr_merge_self_overlaps).
+//
+// sr_self_scan_kernel: one workgroup per pair, one lane per offset.  The offsets are taken in descending chunks of as many as the
+// workgroup has lanes (the reference's order: smallest overlap first, :879-882); a lane adds the log p terms of its offset in position
+// order in fp64 — the sum is then overlap_score's (src/EdgeCalculator.cpp:103-137), bit for bit — from a host-built table, multiplies by
+// the host-built 1.0 / n and compares with the x-space image of min_score.  After a chunk the workgroup takes the largest offset that
+// is a hit or lies in the guard band and stops there (the reference's early exit).  Both mates sit in LDS as (quality row << 3 | base
+// code) symbols: at step i every lane reads the same symbol of mate 2 and consecutive symbols of mate 1, nothing comes from device
+// memory inside the loop.  Mates of up to kSelfCap symbols are staged once per pair; longer ones go through LDS in windows of
+// kSelfWindow positions per chunk, which a lane walks in order, so the sum's order does not change.
+// The log table sits in LDS when it fits beside the mates (LDS_LUT) and is read from device memory otherwise.
+//
+// sr_self_merge_kernel: one lane per output column of the merged pairs: consensus() of {mate 1 at 0, mate 2 at p} (:890-903), the
+// quality from the host-built table of one- and two-member columns, the base from the exact sums by comparison (hc_sr_kernels.hip).
+// No transcendental function runs on the device.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hc_sr.h"
+#include "hc_sr_self.h"
+
+namespace hc {
+namespace {
+
+__device__ inline uint32_t self_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : kCodeN; }
+
+// (row << 3 | code) of a checked symbol; an N takes row K, the all-zero row of the table
+__device__ inline uint16_t self_sym(uint8_t base, uint8_t q, const uint8_t* qmap_s, uint32_t K) {
+    const uint32_t code = self_code(base);
+    return (uint16_t)(((code == kCodeN ? K : (uint32_t)qmap_s[q]) << 3) | code);
+}
+
+// one position: the term of (a, b) joins the lane's sum
+__device__ inline void self_step(uint32_t a, uint32_t b, const double* lut, uint32_t tri, double& S, uint32_t& n) {
+    const uint32_t qa = a >> 3, qb = b >> 3;
+    const uint32_t hi = qa > qb ? qa : qb, lo = qa > qb ? qb : qa;
+    const uint32_t m = ((a ^ b) & 7u) ? 1u : 0u;  // plane 1: the bases differ (an N: row K holds 0.0 in both planes)
+    S += lut[m * tri + hi * (hi + 1u) / 2u + lo];
+    n += ((a & 7u) < kCodeN && (b & 7u) < kCodeN) ? 1u : 0u;
+}
+
+template <bool LDS_LUT>
+__global__ __launch_bounds__(256) void sr_self_scan_kernel(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual,
+                                                           const hc_sr_pair* __restrict__ pairs, const uint32_t* __restrict__ skip, uint64_t n_pairs,
+                                                           const uint8_t* __restrict__ qmap, const double* __restrict__ lut_g,
+                                                           const double* __restrict__ inv_n, SrSelfParams prm, SrSelfScan* __restrict__ out) {
+    extern __shared__ double self_smem[];  // [the table, LDS_LUT][mate 1: kSelfCap symbols][mate 2: kSelfCap symbols]
+    __shared__ uint8_t qmap_s[256];
+    __shared__ int best;
+    uint16_t* s1 = (uint16_t*)(self_smem + (LDS_LUT ? prm.lut_doubles : 0u));
+    uint16_t* s2 = s1 + kSelfCap;
+    const uint32_t tid = threadIdx.x, chunk = blockDim.x;
+    if (LDS_LUT)
+        for (uint32_t i = tid; i < prm.lut_doubles; i += chunk) self_smem[i] = lut_g[i];
+    for (uint32_t i = tid; i < 256; i += chunk) qmap_s[i] = qmap[i];
+    const double* lut = LDS_LUT ? (const double*)self_smem : lut_g;
+    const uint32_t tri = lut_tri(prm.K + 2u);
+    const double ninf = -__builtin_inf();
+    for (uint64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
+        __syncthreads();  // the table and qmap are in place; the last pair's symbols are no longer read
+        if (skip[pi]) continue;
+        const hc_sr_pair P = pairs[pi];
+        const uint8_t *b1 = seq + P.off1, *q1 = qual + P.off1, *b2 = seq + P.off2, *q2 = qual + P.off2;
+        const uint32_t len1 = P.len1, len2 = P.len2;
+        const bool too_short = len1 < prm.min_read_len || len2 < prm.min_read_len;  // :82-84: every offset scores 0
+        const bool resident = len1 <= kSelfCap && len2 <= kSelfCap;
+        if (resident) {
+            for (uint32_t i = tid; i < len1; i += chunk) s1[i] = self_sym(b1[i], q1[i], qmap_s, prm.K);
+            for (uint32_t i = tid; i < len2; i += chunk) s2[i] = self_sym(b2[i], q2[i], qmap_s, prm.K);
+        }
+        bool found = false;
+        const int64_t first = len1 > prm.min_overlap ? (int64_t)len1 - prm.min_overlap : 0;
+        for (int64_t p_hi = first; p_hi >= 1; p_hi -= chunk) {
+            const int64_t p_lo = p_hi - chunk + 1 > 1 ? p_hi - chunk + 1 : 1;
+            if (tid == 0) best = 0;
+            const int64_t p = p_hi - tid;
+            const bool active = p >= p_lo;
+            // (p = len1 when min_overlap is 0: overlap_score returns 0 there, :76-79)
+            const uint32_t Lp = (active && !too_short && p < (int64_t)len1) ? min(len1 - (uint32_t)p, len2) : 0u;
+            double S = 0.0;
+            uint32_t n = 0;
+            if (resident) {
+                __syncthreads();  // the symbols are staged
+                const uint16_t* a = s1 + (active ? p : 0);  // an idle lane (Lp = 0) forms no pointer before the buffer
+                for (uint32_t i = 0; i < Lp; i++) self_step(a[i], s2[i], lut, tri, S, n);
+            } else {
+                const uint32_t Lmax = (too_short || p_lo >= (int64_t)len1) ? 0u : min(len1 - (uint32_t)p_lo, len2);  // the chunk's longest overlap
+                for (uint32_t i0 = 0; i0 < Lmax; i0 += kSelfWindow) {
+                    __syncthreads();  // the last window is no longer read
+                    const uint32_t n2 = min(kSelfWindow, len2 - i0), at1 = i0 + (uint32_t)p_lo, n1 = min(kSelfWindow + chunk - 1u, len1 - at1);
+                    for (uint32_t j = tid; j < n2; j += chunk) s2[j] = self_sym(b2[i0 + j], q2[i0 + j], qmap_s, prm.K);
+                    for (uint32_t j = tid; j < n1; j += chunk) s1[j] = self_sym(b1[at1 + j], q1[at1 + j], qmap_s, prm.K);
+                    __syncthreads();
+                    const uint32_t end = min(i0 + kSelfWindow, Lp);
+                    const uint16_t* a = s1 + (active ? (uint32_t)(p - p_lo) : 0u);
+                    for (uint32_t i = i0; i < end; i++) self_step(a[i - i0], s2[i - i0], lut, tri, S, n);
+                }
+            }
+            __syncthreads();  // best = 0 is written
+            // x = (1.0 / total_len) * total_score (:137); -inf where overlap_score returns 0: no counted position, or a term below --mismatch (+inf)
+            double x = ninf;
+            if (n > 0 && S < __builtin_inf() && n < prm.inv_len) x = inv_n[n] * S;
+            const bool hit = active && (prm.always || x > prm.band.hi);
+            const bool amb = active && !hit && x > prm.band.lo;
+            if (hit || amb) atomicMax(&best, (int)p);
+            __syncthreads();
+            const int b = best;
+            if (b > 0) {
+                if (active && p == (int64_t)b) {
+                    SrSelfScan r;
+                    r.p = b;
+                    r.kind = hit ? kSelfHit : kSelfBand;
+                    r.x = x;
+                    out[pi] = r;
+                }
+                found = true;
+                break;
+            }
+            __syncthreads();  // everybody has read `best` before the next chunk clears it
+        }
+        if (!found && tid == 0) {
+            SrSelfScan r;
+            r.p = -1;
+            r.kind = kSelfNone;
+            r.x = ninf;
+            out[pi] = r;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void sr_self_merge_kernel(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual,
+                                                            const hc_sr_pair* __restrict__ pairs, uint64_t n_pairs, const int32_t* __restrict__ mpos,
+                                                            const uint64_t* __restrict__ off, uint64_t total, const double* __restrict__ terms,
+                                                            const uint8_t* __restrict__ table, uint8_t* __restrict__ out_seq,
+                                                            uint8_t* __restrict__ out_qual) {
+    __shared__ double t_same[kSrQIdx], t_other[kSrQIdx];
+    for (uint32_t i = threadIdx.x; i < kSrQIdx; i += blockDim.x) {
+        t_same[i] = terms[i];
+        t_other[i] = terms[kSrQIdx + i];
+    }
+    __syncthreads();
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    // the pair that owns column g: the last i with off[i] <= g (pairs without columns share their successor's offset)
+    uint64_t lo = 0, hi = n_pairs;  // off[lo] <= g < off[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (off[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const int32_t p = mpos[lo];
+    if (p < 0) return;
+    const hc_sr_pair P = pairs[lo];
+    const uint32_t c = (uint32_t)(g - off[lo]);
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;  // by base code A, C, G, T
+    uint32_t cnt = 0, key = 0;
+    for (uint32_t k = 0; k < 2; k++) {  // the members in list order: mate 1 at 0, mate 2 at p
+        const bool in = k == 0 ? c < P.len1 : c >= (uint32_t)p;
+        if (!in) continue;
+        const uint64_t at = k == 0 ? P.off1 + c : P.off2 + (c - (uint32_t)p);
+        const uint32_t code = self_code(seq[at]);
+        const uint32_t q = code == kCodeN ? 0u : ((uint32_t)qual[at] - 33u) & 127u;
+        key |= (code * 128u + q) << (cnt * 16);
+        cnt++;
+        if (code < 4) {  // :309-338: the member's term goes to all four scores
+            const double a = t_same[q], b = t_other[q];
+            s0 += code == 0 ? a : b;
+            s1 += code == 1 ? a : b;
+            s2 += code == 2 ? a : b;
+            s3 += code == 3 ? a : b;
+        }
+    }
+    const double smax = fmax(fmax(s0, s3), fmax(s1, s2));
+    const uint8_t nuc = smax == s0 ? 'A' : (smax == s3 ? 'T' : (smax == s1 ? 'C' : 'G'));  // :390-393
+    uint32_t entry = 255;
+    if (cnt == 1) {
+        entry = table[kSrTable1 + (key & 0xffffu)];
+    } else if (cnt == 2) {
+        const uint32_t k1 = key & 0xffffu, k2 = key >> 16;
+        entry = table[(((k1 >> 7) * 5u + (k2 >> 7)) * 128u + (k1 & 127u)) * 128u + (k2 & 127u)];
+    }
+    out_seq[g] = entry <= 93 ? nuc : (uint8_t)'N';
+    out_qual[g] = entry <= 93 ? (uint8_t)(entry + 33) : (uint8_t)'$';
+}
+
+}  // namespace
+
+hipError_t sr_self_launch_scan(uint32_t n_cu, uint32_t lanes, const uint8_t* seq, const uint8_t* qual, const hc_sr_pair* pairs, const uint32_t* skip,
+                               uint64_t n_pairs, const uint8_t* qmap, const double* lut, const double* inv_n, const SrSelfParams& prm, SrSelfScan* out,
+                               hipStream_t s) {
+    if (n_pairs == 0) return hipSuccess;
+    if (lanes == 0 || lanes > kSelfMaxChunk || (lanes & 63u)) return hipErrorInvalidValue;
+    const bool lds_lut = (size_t)prm.lut_doubles * sizeof(double) <= kSelfLdsLutBytes;
+    const size_t lds = (lds_lut ? (size_t)prm.lut_doubles * sizeof(double) : 0) + 2 * (size_t)kSelfCap * sizeof(uint16_t);
+    const uint64_t most = (uint64_t)n_cu * (2048u / lanes);
+    const uint32_t blocks = (uint32_t)(n_pairs < most ? n_pairs : most);
+    if (lds_lut)
+        hipLaunchKernelGGL(sr_self_scan_kernel<true>, dim3(blocks), dim3(lanes), lds, s, seq, qual, pairs, skip, n_pairs, qmap, lut, inv_n, prm, out);
+    else
+        hipLaunchKernelGGL(sr_self_scan_kernel<false>, dim3(blocks), dim3(lanes), lds, s, seq, qual, pairs, skip, n_pairs, qmap, lut, inv_n, prm, out);
+    return hipGetLastError();
+}
+
+hipError_t sr_self_launch_merge(const uint8_t* seq, const uint8_t* qual, const hc_sr_pair* pairs, uint64_t n_pairs, const int32_t* mpos,
+                                const uint64_t* off, uint64_t total, const double* terms, const uint8_t* table, uint8_t* out_seq, uint8_t* out_qual,
+                                hipStream_t s) {
+    if (total == 0 || n_pairs == 0) return hipSuccess;
+    const uint64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sr_self_merge_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, seq, qual, pairs, n_pairs, mpos, off, total, terms, table, out_seq,
+                       out_qual);
+    return hipGetLastError();
+}
+
+}  // namespace hc

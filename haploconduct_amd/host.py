@@ -458,6 +458,17 @@ def sr_consensus(reads, layouts, members, min_qual=0.99, min_clique_size=2, erro
                   layouts, members, st)
 
 
+def sr_merge_self_overlaps(seq, qual, pairs, settings=None, min_score=0.99, min_qual=0.99, min_overlap=15, n_threads=1, count_first=False):
+    """hc_host_sr_merge_self_overlaps: the host mirror of EdgeScorer.sr_merge_self_overlaps (SRBuilder::merge_self_overlap,
+    src/SRBuilder.cpp:872-955).  settings: a records.Settings, of which --mismatch and --min_read_len are read."""
+    from . import consensus as SR
+    from .records import Settings
+
+    cs = (settings or Settings()).to_c()
+    st = SR.make_self_settings(min_score, min_qual, min_overlap, n_threads)
+    return SR.run_self(lambda *a: N.lib.hc_host_sr_merge_self_overlaps(C.byref(cs), *a), seq, qual, pairs, st, count_first)
+
+
 def sr_edge_layouts(edges, reads):
     """hc_host_sr_edge_layouts: layouts of edge merges between single-end reads (sort_vertices type 's', src/SRBuilder.cpp:33-285)."""
     from . import consensus as SR

@@ -58,6 +58,15 @@ class EdgeScorer:
         st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
         return SR.run(lambda *a: N.lib.hc_sr_consensus(self._ctx, *a), layouts, members, st)
 
+    def sr_merge_self_overlaps(self, seq, qual, pairs, min_score=0.99, min_qual=0.99, min_overlap=15, n_threads=16, count_first=False):
+        """hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (src/SRBuilder.cpp:872-955) for every pair, on the device.  seq / qual:
+        packed bytes (what sr_consensus returns as cons_seq / cons_qual), pairs: consensus.SR_PAIR_DTYPE records.  --mismatch and
+        --min_read_len are this scorer's settings.  Needs no set_reads.  Returns a consensus.SrSelfResult."""
+        from . import consensus as SR
+
+        st = SR.make_self_settings(min_score, min_qual, min_overlap, n_threads)
+        return SR.run_self(lambda *a: N.lib.hc_sr_merge_self_overlaps(self._ctx, *a), seq, qual, pairs, st, count_first)
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

@@ -248,3 +248,42 @@ def records_to_lines(rec, reads):
             str(int(r["perc"])), "-" if ss else str(int(r["perc"])), str(int(r["len1"])),
             "-" if ss else str(int(r["len2"])), "p" if p1 else "s", "p" if p2 else "s"]))
     return lines
+
+
+def make_mate_pairs(n_pairs, lo, hi, seed, qvals=None, qweights=None, sub_rate=0.01, overlap_frac=0.5, max_overlap=None):
+    """Mate pairs for the self-overlap merge (hc_sr_merge_self_overlaps): packed bases, packed qualities, SR_PAIR_DTYPE records and the mask
+    of the pairs built to overlap.  Mates of lo..hi bases from a synthetic genome with sub_rate substitutions; qualities i.i.d. from qvals
+    with qweights (default: QUAL_SET).  A fragment is mate 1 followed (overlapping or after a gap) by mate 2: for about overlap_frac of the
+    pairs mate 2 starts 15 .. max_overlap (default: len1 - 1) bases before mate 1's end, the others lie apart.  (An overlap merges when its
+    mean log p stays above log 0.99: one high-quality substitution costs about 10, so at 1 % substitutions it is the short overlaps that
+    merge.)"""
+    from .consensus import SR_PAIR_DTYPE
+    rng = np.random.default_rng(seed)
+    if qvals is None:
+        qvals, qweights = QUAL_SET, None
+    G = 50000 + 4 * hi
+    genome = rng.choice(_ACGT, G)
+    l1 = rng.integers(lo, hi + 1, n_pairs)
+    l2 = rng.integers(lo, hi + 1, n_pairs)
+    over = rng.random(n_pairs) < overlap_frac
+    start = rng.integers(0, 50000, n_pairs)
+    # an overlapping pair: mate 2 starts ov bases before mate 1's end, p = l1 - ov in [1, l1 - 15]; the others: 10 .. 200 bases behind the end
+    ov_hi = l1 - 1 if max_overlap is None else np.minimum(l1 - 1, max_overlap)
+    ov = 15 + (rng.random(n_pairs) * (ov_hi - 14)).astype(np.int64)
+    p = np.where(over, l1 - ov, l1 + rng.integers(10, 200, n_pairs))
+    pairs = np.zeros(n_pairs, SR_PAIR_DTYPE)
+    pairs["len1"], pairs["len2"] = l1, l2
+    off = np.zeros(2 * n_pairs + 1, np.int64)
+    off[1:] = np.cumsum(np.stack([l1, l2], 1).reshape(-1))
+    pairs["off1"], pairs["off2"] = off[0:-1:2], off[1::2]
+    total = int(off[-1])
+    seq = np.empty(total, np.uint8)
+    for i in range(n_pairs):
+        a = int(start[i])
+        seq[off[2 * i]:off[2 * i + 1]] = genome[a:a + l1[i]]
+        b = a + int(p[i])
+        seq[off[2 * i + 1]:off[2 * i + 2]] = genome[b:b + l2[i]]
+    sub = rng.random(total) < sub_rate
+    seq[sub] = rng.choice(_ACGT, int(sub.sum()))
+    qual = rng.choice(np.asarray(qvals, np.uint8), total, p=qweights).astype(np.uint8)
+    return seq, qual, pairs, over

@@ -106,6 +106,84 @@ int hc_host_sr_table(double min_qual, uint32_t n_q, uint8_t* table);
 int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const uint32_t* seq_len_by_read, const uint8_t* paired,
                             uint32_t n_reads, hc_sr_layout* layouts, hc_sr_member* members, uint64_t* first_bad);
 
+/* ---- self-overlapping paired super-reads: SRBuilder::merge_self_overlap (src/SRBuilder.cpp:872-955) --------------------
+ *
+ * process_cliques (src/SRBuilder.cpp:958-1029) hands every paired super-read with two non-empty mates to merge_self_overlap,
+ * which slides mate 2 along mate 1 from the smallest allowed overlap on (:879-888), scores every offset with
+ * EdgeCalculator::overlap_score (src/EdgeCalculator.cpp:67-139) and replaces the pair, at the first offset that scores above
+ * min_score, by the two-member consensus of the mates (:890-903) as one single-end super-read.
+ *
+ * A PAIR names its two mates inside one packed base buffer and one packed quality buffer — what hc_sr_consensus writes
+ * (cons_seq, cons_qual, out_off), so that a caller passes those buffers on unchanged. */
+typedef struct hc_sr_pair {
+    uint64_t off1, off2; /* first byte of mate 1 / mate 2 in seq and qual */
+    uint32_t len1, len2;
+} hc_sr_pair; /* 24 bytes */
+
+typedef struct hc_sr_self_settings {
+    double min_score;     /* 0.99, src/SRBuilder.cpp:874                                                          */
+    double min_qual;      /* SRBuilder::minQual for the consensus of the merged read, src/SRBuilder.h:89          */
+    uint32_t min_overlap; /* 15, src/SRBuilder.cpp:873                                                            */
+    uint32_t n_threads;   /* host threads (the mirror's pairs; the device call's checks and host-decided pairs); 0 = 1 */
+} hc_sr_self_settings; /* 24 bytes */
+
+/* Per-pair status. */
+enum {
+    HC_SR_SELF_NONE = 0,      /* no offset scored above min_score: the pair stays as it is, return superread, :954       */
+    HC_SR_SELF_MERGED = 1,    /* merged at overlap_pos, :890-950                                                         */
+    HC_SR_SELF_BAD_PAIR = 2,  /* refused: len1 == 0, len2 == 0 (the asserts of src/EdgeCalculator.cpp:70-73), a mate that
+                                 does not lie inside n_bytes, or len1 + len2 > INT32_MAX (overlap_pos is an int32_t and
+                                 the merged read has up to len1 + len2 - 1 columns).  Nothing of the buffers is read for
+                                 it.                                                                                    */
+    HC_SR_SELF_BAD_SYMBOL = 3 /* a base outside ACGTN or a quality byte outside [33,126] ANYWHERE in either mate.  The
+                                 reference asserts on such a symbol when an offset touches it
+                                 (src/EdgeCalculator.cpp:29-30,61); checking the whole pair before the scan is a stated
+                                 tightening: a pair whose bad symbol no tried offset would have reached is refused too. */
+};
+
+typedef struct hc_sr_self_stats {
+    uint64_t n_merged;     /* pairs with HC_SR_SELF_MERGED                                                              */
+    uint64_t n_host_pairs; /* device call only: pairs whose deciding offset fell into the guard band of min_score (or
+                              whose consensus table holds a NaN entry) and that host threads finished                  */
+    uint64_t n_offsets;    /* offsets the batch holds in all, sum of max(len1 - min_overlap, 0) over the valid pairs:
+                              what a batch that merges nothing scans                                                   */
+    double ms_device;      /* device call only: the kernels, by events on the context's stream                         */
+    double ms_host;        /* device call only: the host threads' share (checks, table, host-decided pairs)            */
+} hc_sr_self_stats;
+
+/* merge_self_overlap (src/SRBuilder.cpp:872-955) for every pair, on the device.  Needs no hc_set_reads; --mismatch and
+ * --min_read_len are those of the context's hc_settings, as EdgeCalculator takes them from program_settings
+ * (src/EdgeCalculator.cpp:49,82).
+ * The scan of pair i (:879-888): the offsets p = len1 - min_overlap, len1 - min_overlap - 1, ..., 1 in that order (none
+ * when len1 <= min_overlap; p = 0 is never tried), each scored over L = min(len1 - p, len2) positions: 0 when a mate is
+ * shorter than min_read_len, when a position's probability lies below --mismatch or when every position holds an N, else
+ * exp((1.0 / n) * sum of log p_i) with the terms added in position order.  The first p with score > min_score is taken.
+ * The merge (:890-903): consensus() of {mate 1 at 0, mate 2 at p}, total_len = len2 + p, no error correction — column c
+ * holds mate 1 when c < len1 and mate 2 when c >= p; with len2 + p < len1 the output stops at total_len (a layout
+ * hc_sr_consensus refuses and consensus() as called here does not).  Where consensus() comes back empty (the NaN exit of
+ * consensus_pos) the scan goes on with the next offset (:904).
+ * Outputs per pair: overlap_pos[i] = p or -1; score[i] = overlap_score's value at p (host exp) or 0; status[i] = HC_SR_SELF_*;
+ * the merged bytes of pair i at [out_off[i], out_off[i + 1]) of merged_seq / merged_qual (out_off has n_pairs + 1 entries; an
+ * unmerged pair owns no bytes).  cap / *n_out: as hc_sr_consensus' cap / *n_bytes, cap = 0 with NULL buffers is the count of
+ * count-then-fetch (HC_ERR_ARG, everything but the bytes filled).  stats may be NULL.
+ * Left to the caller: index2 += p in the subread map and in the original indexes and the re-sort of the clique by
+ * index (:911-949), and Read::test_N_rate (src/Read.h:214-234).
+ * Numerics (DESIGN.md "Self-overlap merge"): the device adds host-built log p terms, one lane per offset, in position order;
+ * score > min_score is decided on x = (1.0 / n) * sum against the x-space image of min_score, an offset inside the guard band
+ * goes to the host's libm; the merged bytes come from hc_host_sr_table.  The result is the reference's, byte for byte. */
+int hc_sr_merge_self_overlaps(hc_ctx* ctx, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair* pairs,
+                              uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score,
+                              uint32_t* status, uint64_t* out_off, uint8_t* merged_seq, uint8_t* merged_qual, uint64_t cap,
+                              uint64_t* n_out, hc_sr_self_stats* stats);
+
+/* The same contract on the host (no device, no context): overlap_score (src/EdgeCalculator.cpp:26-139) offset by offset and
+ * consensus_pos column by column, as the reference walks them, on settings->n_threads threads.  Of hc_settings only
+ * mismatch and min_read_len are read. */
+int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes,
+                                   const hc_sr_pair* pairs, uint64_t n_pairs, const hc_sr_self_settings* settings,
+                                   int32_t* overlap_pos, double* score, uint32_t* status, uint64_t* out_off, uint8_t* merged_seq,
+                                   uint8_t* merged_qual, uint64_t cap, uint64_t* n_out, hc_sr_self_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
