@@ -18,6 +18,7 @@
 
 #include "../../include/hcedge.h"
 #include "hc_ctx.h"
+#include "host/LogP.h"
 
 static thread_local std::string g_last_error;
 
@@ -214,14 +215,13 @@ int hc_destroy(hc_ctx* c) {
 }
 
 // The log-probability table.  Built with the HOST libm by the reference's own expressions
-// (EdgeCalculator.cpp:41,44,52,60) so that every term the device adds is bit-identical to the
+// (host/LogP.h) so that every term the device adds is bit-identical to the
 // reference's log(p).  Dimension Kp = K + 2: index K is the N row/column (0.0: the position is
 // skipped, :35-39), index K+1 the invalid-symbol row/column (NaN poison).  Layouts: hc_device.h.
 // `wide_rows` (the wide 8-bit encoding only, 64 entries): what each quality index means there — a Phred value, -1 = N, -2 = not a value.
 static bool build_lut(const std::vector<int>& phred, const std::vector<int>& wide_rows, double mismatch_setting, uint32_t symbytes,
                       std::vector<double>& lut) {
     const size_t K = phred.size(), Kp = K + 2;
-    const double inf = std::numeric_limits<double>::infinity();
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const uint32_t lg = hc::lut_lg((uint32_t)K);
     const bool wide = symbytes == 1 && lg >= 6;
@@ -240,12 +240,8 @@ static bool build_lut(const std::vector<int>& phred, const std::vector<int>& wid
                 vm = vx = 0.0;
             } else {
                 const int ph1 = wide ? wide_rows[a] : phred[a], ph2 = wide ? wide_rows[b] : phred[b];
-                const double p1 = pow(10, -ph1 / 10.0);  // phred_to_prob, :59-63
-                const double p2 = pow(10, -ph2 / 10.0);
-                const double pm = (1 - p1) * (1 - p2) + (p1 * p2) / 3.0;                               // :41
-                const double px = p1 * (1 - p2) / 3.0 + p2 * (1 - p1) / 3.0 + (2 / 9.0) * p1 * p2;  // :44
-                vm = (pm < mismatch_setting) ? inf : log(pm);  // :49-52
-                vx = (px < mismatch_setting) ? inf : log(px);
+                vm = hc::log_p(ph1, ph2, true, mismatch_setting);
+                vx = hc::log_p(ph1, ph2, false, mismatch_setting);
             }
             if (symbytes == 1) {
                 lut[hc::lut_addr_u8(lg, (uint32_t)a, (uint32_t)b, 0) / 8] = vm;
@@ -382,7 +378,7 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
     memset(c->sr_qbyte, 255, sizeof c->sr_qbyte);
     for (int b = 33; b <= 127; b++)
         if (qmap[b] < 128) c->sr_qbyte[qmap[b]] = (uint8_t)(b - 33);
-    c->sr.tables_valid = false;
+    c->sr.tables.valid = false;
     if (phred.empty()) phred.push_back(0);
     const uint32_t K = (uint32_t)phred.size();
     const uint32_t symbytes = hc::sym_bytes_for(K);

@@ -2,7 +2,8 @@
 // batch of layouts on the device.  The host builds what depends on libm — the per-quality log10 terms and the table of one- and
 // two-member columns, once per read set and min_qual —, the kernels of hc_sr_kernels.hip do the rest, and the columns they could not
 // decide by comparisons come back as four sums that host threads finish with the reference's expressions (host/SrConsensus.h).
-// hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end of this file.
+// hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end of this file.  Both calls build
+// their consensus tables with sr_tables and run their host loops with in_blocks (host/InBlocks.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +14,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/hcsr.h"
@@ -21,6 +21,7 @@
 #include "hc_prims.h"
 #include "hc_sr.h"
 #include "hc_sr_self.h"
+#include "host/InBlocks.h"
 #include "host/SrConsensus.h"
 #include "host/SrSelfOverlap.h"
 
@@ -28,28 +29,33 @@ static int fail(int status, const std::string& what) { return hc::set_last_error
 
 namespace {
 
-int build_tables(hc_ctx* c, double min_qual) {
-    if (c->sr.tables_valid && memcmp(&c->sr.table_min_qual, &min_qual, sizeof(double)) == 0) return HC_OK;
-    c->sr.tables_valid = false;
-    std::vector<double> terms(2 * hc::kSrQIdx, 0.0);
+// The consensus tables (host/SrConsensus.h) for the quality values q_of[i] = byte - 33 of term index i (255: none) and min_qual, on the
+// device: built and uploaded unless T holds them already.  The consensus call's term index is the store's quality index, the merge
+// call's the quality value itself.
+int sr_tables(hc_ctx* c, hc_ctx::SrTables& T, const uint8_t* q_of, double min_qual) {
+    constexpr uint32_t kQDim = hc::sr::kQDim;
+    static_assert(sizeof T.q_of == kQDim, "one entry per term index");
+    if (T.valid && memcmp(&T.min_qual, &min_qual, sizeof(double)) == 0 && memcmp(T.q_of, q_of, kQDim) == 0) return HC_OK;
+    T.valid = false;
+    std::vector<double> terms(2 * kQDim, 0.0);
     std::vector<uint32_t> qs;
-    for (uint32_t i = 0; i < hc::kSrQIdx; i++) {
-        if (c->sr_qbyte[i] == 255) continue;
-        hc::sr::terms((int)c->sr_qbyte[i], terms[i], terms[hc::kSrQIdx + i]);
-        qs.push_back(c->sr_qbyte[i]);
+    for (uint32_t i = 0; i < kQDim; i++) {
+        if (q_of[i] == 255) continue;
+        hc::sr::terms((int)q_of[i], terms[i], terms[kQDim + i]);
+        qs.push_back(q_of[i]);
     }
     std::vector<uint8_t> table(HC_SR_TABLE_BYTES);
     hc::sr::build_table(min_qual, qs, table.data());
-    int rc = c->sr.terms.ensure(terms.size() * sizeof(double));
-    if (rc == HC_OK) rc = c->sr.qbyte.ensure(hc::kSrQIdx);
-    if (rc == HC_OK) rc = c->sr.table.ensure(table.size());
-    if (rc) return rc;
-    HC_HIP(hipMemcpyAsync(c->sr.terms.p, terms.data(), terms.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HC_HIP(hipMemcpyAsync(c->sr.qbyte.p, c->sr_qbyte, hc::kSrQIdx, hipMemcpyHostToDevice, c->stream));
-    HC_HIP(hipMemcpyAsync(c->sr.table.p, table.data(), table.size(), hipMemcpyHostToDevice, c->stream));
+    int rc;
+    if ((rc = T.terms.ensure(terms.size() * sizeof(double))) || (rc = T.qbyte.ensure(kQDim)) || (rc = T.table.ensure(table.size()))) return rc;
+    HC_HIP(hipMemcpyAsync(T.terms.p, terms.data(), terms.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(T.qbyte.p, q_of, kQDim, hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(T.table.p, table.data(), table.size(), hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));  // (the host vectors go out of scope)
-    c->sr.tables_valid = true;
-    c->sr.table_min_qual = min_qual;
+    T.valid = true;
+    T.has_nan = memchr(table.data(), hc::sr::kEntryNaN, table.size()) != nullptr;
+    T.min_qual = min_qual;
+    memcpy(T.q_of, q_of, kQDim);
     return HC_OK;
 }
 
@@ -68,9 +74,9 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
     out_off[0] = 0;
     if (n_layouts == 0) return HC_OK;
     HC_HIP(hipSetDevice(c->device));
-    int rc = build_tables(c, settings->min_qual);
-    if (rc) return rc;
     hc_ctx::Sr& S = c->sr;
+    int rc = sr_tables(c, S.tables, c->sr_qbyte, settings->min_qual);
+    if (rc) return rc;
     const size_t scan_bytes = hc::prims::scan_temp_bytes(n_layouts + 1, sizeof(uint64_t));
     if ((rc = S.layouts.ensure(n_layouts * sizeof(hc_sr_layout))) || (rc = S.members.ensure((n_members ? n_members : 1) * sizeof(hc_sr_member))) ||
         (rc = S.mem.ensure((n_members ? n_members : 1) * sizeof(hc::SrMember))) || (rc = S.info.ensure(n_layouts * sizeof(hc::SrLayoutInfo))) ||
@@ -103,8 +109,7 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         stats->n_columns = total;
         stats->ms_device = ms_a;
     }
-    if (total > cap || (total && (!cons_seq || !cons_qual)))
-        return fail(HC_ERR_ARG, "hc_sr_consensus: cons_seq / cons_qual have no room (*n_bytes says how much is needed)");
+    if ((rc = hc::sr::check_room("hc_sr_consensus", "cons_seq / cons_qual", "n_bytes", total, cap, cons_seq, cons_qual))) return rc;
     if (total == 0) return HC_OK;
     if ((rc = S.seq.ensure(total)) || (rc = S.qual.ensure(total))) return rc;
     // columns for the host: room for an eighth of all columns at first; the count tells when that was too little, and the kernel runs again
@@ -117,7 +122,7 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         HC_HIP(hipMemsetAsync(S.counter.p, 0, sizeof(unsigned long long), s));
         HC_HIP(hipEventRecord(c->ev0, s));
         HC_HIP(hc::sr_launch_columns(c->view, c->n_cu, S.layouts.as<hc_sr_layout>(), n_layouts, S.mem.as<hc::SrMember>(), S.info.as<hc::SrLayoutInfo>(),
-                                     S.off.as<uint64_t>(), S.terms.as<double>(), S.qbyte.as<uint8_t>(), S.table.as<uint8_t>(),
+                                     S.off.as<uint64_t>(), S.tables.terms.as<double>(), S.tables.qbyte.as<uint8_t>(), S.tables.table.as<uint8_t>(),
                                      hc::sr::safe_region_allowed(settings->min_qual) ? 1u : 0u, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(),
                                      S.late.as<uint32_t>(), S.host_cols.as<hc::SrHostColumn>(), host_cap, S.counter.as<unsigned long long>(), s));
         HC_HIP(hipEventRecord(c->ev1, s));
@@ -138,31 +143,19 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
     HC_HIP(hipStreamSynchronize(s));
     // the host's share: :348-396 with the host libm on the device's sums, spliced into the packed buffers
     const auto t0 = std::chrono::steady_clock::now();
-    if (n_host) {
-        const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)settings->n_threads, 64, n_host / 4096 + 1}));
-        std::atomic<uint64_t> turn{0};
-        const uint64_t block = 4096;
-        const double min_qual = settings->min_qual;
-        auto work = [&]() {
-            for (uint64_t a = turn.fetch_add(block); a < n_host; a = turn.fetch_add(block)) {
-                for (uint64_t i = a; i < std::min<uint64_t>(n_host, a + block); i++) {
-                    const hc::SrHostColumn& h = cols[i];
-                    uint8_t o[2];
-                    if (hc::sr::finish(h.s[0], h.s[1], h.s[2], h.s[3], h.n, min_qual, o)) {
-                        cons_seq[h.out] = o[0];
-                        cons_qual[h.out] = o[1];
-                    } else {
-                        // (several threads may store the same value)
-                        reinterpret_cast<std::atomic<uint32_t>*>(&late[h.layout])->fetch_or(hc::kSrLateNaN, std::memory_order_relaxed);
-                    }
-                }
+    hc::in_blocks(n_host, 4096, settings->n_threads, [&](uint64_t a, uint64_t b) {
+        for (uint64_t i = a; i < b; i++) {
+            const hc::SrHostColumn& h = cols[i];
+            uint8_t o[2];
+            if (hc::sr::finish(h.s[0], h.s[1], h.s[2], h.s[3], h.n, settings->min_qual, o)) {
+                cons_seq[h.out] = o[0];
+                cons_qual[h.out] = o[1];
+            } else {
+                // (several threads may store the same value)
+                reinterpret_cast<std::atomic<uint32_t>*>(&late[h.layout])->fetch_or(hc::kSrLateNaN, std::memory_order_relaxed);
             }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < T; t++) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
-    }
+        }
+    });
     // layouts that failed late (:528-532, an invalid symbol): their bytes leave the packed buffers
     bool any_late = false;
     for (uint64_t l = 0; l < n_layouts && !any_late; l++) any_late = late[l] != 0;
@@ -198,25 +191,6 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
 // hc_sr_merge_self_overlaps: the host checks the pairs and builds what depends on libm (the log p table of the batch's quality values, by
 // the scoring path's own builder; 1.0 / n; the consensus table), the scan kernel finds every pair's offset, the host decides the offsets
 // inside the guard band (host/SrSelfOverlap.h), the merge kernel writes the merged reads at the offsets of an exclusive sum.
-namespace {
-
-// `work(a, b)` over [0, n) in blocks, on up to n_threads threads
-template <typename F>
-void in_blocks(uint64_t n, uint64_t block, unsigned n_threads, F work) {
-    const uint64_t n_blocks = (n + block - 1) / block;
-    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_threads, 64, n_blocks}));
-    std::atomic<uint64_t> turn{0};
-    auto run = [&]() {
-        for (uint64_t b = turn.fetch_add(1); b < n_blocks; b = turn.fetch_add(1)) work(b * block, std::min(n, (b + 1) * block));
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < T; t++) th.emplace_back(run);
-    run();
-    for (auto& x : th) x.join();
-}
-
-}  // namespace
-
 extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair* pairs,
                                          uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score,
                                          uint32_t* status, uint64_t* out_off, uint8_t* merged_seq, uint8_t* merged_qual, uint64_t cap,
@@ -239,7 +213,7 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
     const uint64_t check_block = 1024, n_check_blocks = (n_pairs + check_block - 1) / check_block;
     std::vector<std::array<uint8_t, 128>> seen(n_check_blocks);
     std::vector<uint32_t> block_max(n_check_blocks, 0);
-    in_blocks(n_pairs, check_block, n_thr, [&](uint64_t a, uint64_t b) {
+    hc::in_blocks(n_pairs, check_block, n_thr, [&](uint64_t a, uint64_t b) {
         std::array<uint8_t, 128>& sn = seen[a / check_block];
         sn.fill(0);
         uint32_t mx = 0;
@@ -283,34 +257,20 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
     if (n_valid && max_first) {
         // tables: log p by the scoring path's builder for the batch's values (row = rank of the value), 1.0 / n, the consensus table
         std::vector<int> phred;
-        std::vector<uint32_t> qs;
-        uint8_t qmap[256];
+        uint8_t qmap[256], q_of[hc::sr::kQDim];
         memset(qmap, 0, sizeof qmap);
+        memset(q_of, 255, sizeof q_of);
         for (uint32_t q = 0; q < hc::srself::kQ; q++) {
             if (!qs_seen[q]) continue;
             qmap[q + 33] = (uint8_t)phred.size();
             phred.push_back((int)q);
-            qs.push_back(q);
+            q_of[q] = (uint8_t)q;
         }
         std::vector<double> lut;
         if (!hc::build_log_table_u16(phred, c->settings.mismatch, lut)) return fail(HC_ERR_STATE, std::string(me) + "the log table is not symmetric");
         std::vector<double> inv_n((size_t)max_len + 1, 0.0);
         for (uint32_t k = 1; k <= max_len; k++) inv_n[k] = 1.0 / (double)k;  // :137
-        if (!(S.table_valid && memcmp(&S.table_min_qual, &settings->min_qual, sizeof(double)) == 0 && memcmp(S.table_qs, qs_seen, sizeof qs_seen) == 0)) {
-            S.table_valid = false;
-            std::vector<uint8_t> table(HC_SR_TABLE_BYTES);
-            hc::sr::build_table(settings->min_qual, qs, table.data());
-            std::vector<double> terms(2 * hc::kSrQIdx, 0.0);
-            for (uint32_t q : qs) hc::sr::terms((int)q, terms[q], terms[hc::kSrQIdx + q]);
-            S.table_has_nan = memchr(table.data(), hc::sr::kEntryNaN, table.size()) != nullptr;
-            if ((rc = S.table.ensure(table.size())) || (rc = S.terms.ensure(terms.size() * sizeof(double)))) return rc;
-            HC_HIP(hipMemcpyAsync(S.table.p, table.data(), table.size(), hipMemcpyHostToDevice, s));
-            HC_HIP(hipMemcpyAsync(S.terms.p, terms.data(), terms.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            HC_HIP(hipStreamSynchronize(s));  // (the host vectors go out of scope)
-            S.table_valid = true;
-            S.table_min_qual = settings->min_qual;
-            memcpy(S.table_qs, qs_seen, sizeof qs_seen);
-        }
+        if ((rc = sr_tables(c, S.tables, q_of, settings->min_qual))) return rc;
         hc::SrSelfParams prm;
         int log2_width = -49;
         if (const char* e = getenv("HC_SR_SELF_BAND_LOG2")) {  // test knob: a wider guard band, so that the host-decided path runs
@@ -349,7 +309,7 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
         HC_HIP(hipEventElapsedTime(&ms_scan, c->ev0, c->ev1));
         for (uint64_t i = 0; i < n_pairs; i++) {
             if (skip[i] || res[i].p < 0) continue;
-            if (res[i].kind == hc::kSelfHit && !S.table_has_nan) {
+            if (res[i].kind == hc::kSelfHit && !S.tables.has_nan) {
                 overlap_pos[i] = res[i].p;
                 score[i] = exp(res[i].x);  // :138
                 status[i] = HC_SR_SELF_MERGED;
@@ -368,7 +328,7 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
     if (!host_pairs.empty()) {
         const auto t0 = std::chrono::steady_clock::now();
         const hc::srself::Tables T(c->settings.mismatch, c->settings.min_read_len);
-        in_blocks(host_pairs.size(), 1, n_thr, [&](uint64_t a, uint64_t b) {
+        hc::in_blocks(host_pairs.size(), 1, n_thr, [&](uint64_t a, uint64_t b) {
             for (uint64_t k = a; k < b; k++) {
                 const uint64_t i = host_pairs[k].first;
                 const hc_sr_pair& P = pairs[i];
@@ -395,8 +355,7 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
         stats->ms_device = ms_scan;
         stats->ms_host = ms_host;
     }
-    if (total > cap || (total && (!merged_seq || !merged_qual)))
-        return fail(HC_ERR_ARG, std::string(me) + "merged_seq / merged_qual have no room (*n_out says how much is needed)");
+    if ((rc = hc::sr::check_room("hc_sr_merge_self_overlaps", "merged_seq / merged_qual", "n_out", total, cap, merged_seq, merged_qual))) return rc;
     if (total == 0) return HC_OK;
     // the merged reads: offsets by an exclusive sum on the device, one lane per column
     if ((rc = S.out_seq.ensure(total)) || (rc = S.out_qual.ensure(total))) return rc;
@@ -405,7 +364,7 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
     HC_HIP(hipEventRecord(c->ev0, s));
     HC_HIP(hc::prims::exclusive_sum(S.temp.p, S.temp.cap, S.len.as<uint64_t>(), S.off.as<uint64_t>(), n_pairs + 1, s));
     HC_HIP(hc::sr_self_launch_merge(S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), S.pairs.as<hc_sr_pair>(), n_pairs, S.mpos.as<int32_t>(),
-                                    S.off.as<uint64_t>(), total, S.terms.as<double>(), S.table.as<uint8_t>(), S.out_seq.as<uint8_t>(),
+                                    S.off.as<uint64_t>(), total, S.tables.terms.as<double>(), S.tables.table.as<uint8_t>(), S.out_seq.as<uint8_t>(),
                                     S.out_qual.as<uint8_t>(), s));
     HC_HIP(hipEventRecord(c->ev1, s));
     HC_HIP(hipMemcpyAsync(merged_seq, S.out_seq.p, total, hipMemcpyDeviceToHost, s));

@@ -259,21 +259,26 @@ struct hc_ctx {
         hipEvent_t stage_free[2] = {nullptr, nullptr};
         int stage_turn = 0;
     } graph;
+    // The consensus tables of one call path on the device (hc_api_sr.cpp: sr_tables): the log10 terms by term index, q_of itself, the
+    // table of one- and two-member columns — and what they were built for.
+    struct SrTables {
+        hc_scratch terms, qbyte, table;
+        bool valid = false, has_nan = false;  // has_nan: the table holds a kEntryNaN
+        double min_qual = 0;
+        uint8_t q_of[128];  // the quality value (byte - 33) of term index i, 255: none
+    };
     // super-read consensus (hc_api_sr.cpp).  hc_set_reads keeps the inverse of its quality map: sr_qbyte[i] = quality byte - 33 of the
     // store's quality index i (255: the index is not a quality value).  The tables are rebuilt when the store or min_qual changes.
     uint8_t sr_qbyte[128];
     struct Sr {
-        hc_scratch layouts, members, mem, info, len, off, temp, seq, qual, late, host_cols, counter, terms, qbyte, table;
-        bool tables_valid = false;
-        double table_min_qual = 0;
+        hc_scratch layouts, members, mem, info, len, off, temp, seq, qual, late, host_cols, counter;
+        SrTables tables;
     } sr;
-    // self-overlap merge (hc_api_sr.cpp: hc_sr_merge_self_overlaps): grow-only scratch; the consensus table is rebuilt when min_qual or
-    // the batch's quality values change
+    // self-overlap merge (hc_api_sr.cpp: hc_sr_merge_self_overlaps): grow-only scratch; the consensus tables are rebuilt when min_qual or
+    // the batch's quality values change (term index = the value itself)
     struct SrSelf {
-        hc_scratch seq, qual, pairs, skip, qmap, lut, inv_n, res, len, off, mpos, temp, terms, table, out_seq, out_qual;
-        bool table_valid = false, table_has_nan = false;
-        double table_min_qual = 0;
-        uint8_t table_qs[96] = {0};  // which Q = byte - 33 the table was built for
+        hc_scratch seq, qual, pairs, skip, qmap, lut, inv_n, res, len, off, mpos, temp, out_seq, out_qual;
+        SrTables tables;
     } sr_self;
 };
 

@@ -31,12 +31,11 @@
 #pragma once
 #include <stdint.h>
 
+#include "host/SrCodes.h"  // kCodeN, kCodeBadQual, kCodeBadBase, code_of
+
 namespace hc {
 
 constexpr uint64_t kSinkMaxGroups = 4096;  // the largest grid that collects its rows in per-workgroup segments (n_cu x 16; hc_kernels.hip: RowSink)
-constexpr uint32_t kCodeN = 4;
-constexpr uint32_t kCodeBadQual = 6;
-constexpr uint32_t kCodeBadBase = 7;
 
 // per-read flags in ReadDesc
 constexpr uint32_t kReadPaired = 1u;

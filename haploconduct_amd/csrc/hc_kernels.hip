@@ -74,15 +74,8 @@ __global__ __launch_bounds__(256) void encode_store_kernel(const uint8_t* __rest
             if (i < len) {
                 const uint8_t b = bases[r0 + i];
                 const uint8_t qi = qmap[quals[r0 + i]];
-                uint32_t code;
-                switch (b) {
-                    case 'A': code = 0; break;
-                    case 'C': code = 1; break;
-                    case 'G': code = 2; break;
-                    case 'T': code = 3; break;
-                    case 'N': code = kCodeN; break;
-                    default: code = kCodeBadBase; bad = 1; break;
-                }
+                uint32_t code = code_of(b);
+                if (code == kCodeBadBase) bad = 1;
                 uint32_t qx = qi;
                 if (WIDE) {
                     // sym = qidx << 2 | base2; N / invalid are reserved quality indices with base bits 0

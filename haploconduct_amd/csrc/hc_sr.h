@@ -8,11 +8,9 @@
 
 namespace hc {
 
-constexpr uint32_t kSrQIdx = 128;                 // quality indices of a store symbol the tables are addressed by (K + 2 <= 97, wide labels < 64)
-constexpr uint32_t kSrTable1 = 25u * 128u * 128u;  // hcsr.h: where the one-member entries of the table start
+// (the tables' geometry, the entry codes and the safe region: host/SrCodes.h.  The store's quality indices are term indices as they
+// stand: K + 2 <= 97, wide labels < 64, both below sr::kQDim)
 constexpr uint32_t kSrLateBadSymbol = 1u, kSrLateNaN = 2u;  // what a column reports about its layout
-constexpr double kSrSafeLead = 9.79;               // host/SrConsensus.h: kSafeLead, kSafeFloor
-constexpr double kSrSafeFloor = -300.0;
 
 struct SrMember {  // a member resolved against the store
     uint64_t off;  // first symbol of the oriented sequence

@@ -10,11 +10,13 @@
 // members in list order in fp64 — the four sums are then the reference's, bit for bit — and takes the base by exact comparison in the
 // reference's order A, T, C, G (:390-393).  The quality never comes from device transcendental functions (DESIGN.md "Super-read
 // consensus"): columns of one or two members read it from a host-built table, a deeper column is finished here only where Phred 93
-// follows from the sums by comparisons, and every other column is handed to the host as (layout, column, four sums).
+// follows from the sums by comparisons, and every other column is handed to the host as (layout, column, four sums).  The column's
+// sums, its base, the table look-up and the output bytes are hc_sr_column.h's, which sr_self_merge_kernel uses too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hc_sr.h"
+#include "hc_sr_column.h"
 
 namespace hc {
 namespace {
@@ -145,13 +147,10 @@ __global__ __launch_bounds__(256) void sr_column_kernel(StoreView st, uint32_t l
                                                         uint8_t* __restrict__ cons_seq, uint8_t* __restrict__ cons_qual,
                                                         uint32_t* __restrict__ late, SrHostColumn* __restrict__ host_cols, uint64_t host_cap,
                                                         unsigned long long* __restrict__ host_count) {
-    __shared__ double t_same[kSrQIdx], t_other[kSrQIdx];
-    __shared__ uint8_t q_of[kSrQIdx];
-    for (uint32_t i = threadIdx.x; i < kSrQIdx; i += blockDim.x) {
-        t_same[i] = terms[i];
-        t_other[i] = terms[kSrQIdx + i];
-        q_of[i] = qbyte[i];
-    }
+    __shared__ SrTerms T;
+    __shared__ uint8_t q_of[sr::kQDim];
+    T.load(terms);
+    for (uint32_t i = threadIdx.x; i < sr::kQDim; i += blockDim.x) q_of[i] = qbyte[i];
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -174,8 +173,7 @@ __global__ __launch_bounds__(256) void sr_column_kernel(StoreView st, uint32_t l
             const bool valid = c < end;
             while (w_hi < n && r[w_hi].pos < c0 + 64) w_hi++;
             while (w_lo < w_hi && (int64_t)r[w_lo].pos + r[w_lo].len <= c0) w_lo++;
-            double s0 = 0, s1 = 0, s2 = 0, s3 = 0;  // by base code A, C, G, T
-            uint32_t cnt = 0, key = 0;              // key: (code, q) of the first two members, for the table
+            SrColumn col;
             bool bad = false;
             for (uint32_t i = w_lo; i < w_hi; i++) {
                 const SrMember m = r[i];
@@ -188,43 +186,28 @@ __global__ __launch_bounds__(256) void sr_column_kernel(StoreView st, uint32_t l
                     bad = true;
                     code = kCodeN;
                 }
-                qi = code == kCodeN ? 0u : qi & (kSrQIdx - 1);
+                qi = code == kCodeN ? 0u : qi & (sr::kQDim - 1);
                 const uint32_t q = code == kCodeN ? 0u : q_of[qi] & 127u;
-                if (cnt < 2) key |= (code * 128u + q) << (cnt * 16);
-                cnt++;
-                if (code < 4) {  // :309-338: the member's term goes to all four scores
-                    const double a = t_same[qi], b = t_other[qi];
-                    s0 += code == 0 ? a : b;
-                    s1 += code == 1 ? a : b;
-                    s2 += code == 2 ? a : b;
-                    s3 += code == 3 ? a : b;
-                }
+                col.add(code, q, qi, T);
             }
             if (bad) atomicOr(&late[l], kSrLateBadSymbol);
-            const double smax = fmax(fmax(s0, s3), fmax(s1, s2));
-            const uint8_t nuc = smax == s0 ? 'A' : (smax == s3 ? 'T' : (smax == s1 ? 'C' : 'G'));  // :390-393
-            uint32_t entry = 255;  // Phred, 255 = 'N' '$', 254 = NaN
+            const double smax = col.max_sum();
+            uint32_t entry = sr::kEntryN;  // Phred, kEntryN or kEntryNaN
             bool to_host = false;
             if (valid) {
-                if (cnt == 1) {
-                    entry = table[kSrTable1 + (key & 0xffffu)];
-                } else if (cnt == 2) {
-                    const uint32_t k1 = key & 0xffffu, k2 = key >> 16;
-                    entry = table[(((k1 >> 7) * 5u + (k2 >> 7)) * 128u + (k1 & 127u)) * 128u + (k2 & 127u)];
-                } else if (cnt >= 3) {
-                    // Phred 93 without libm: the largest sum leads each of the other three by kSrSafeLead decades
-                    const uint32_t led = (uint32_t)(smax - s0 >= kSrSafeLead) + (uint32_t)(smax - s1 >= kSrSafeLead) +
-                                         (uint32_t)(smax - s2 >= kSrSafeLead) + (uint32_t)(smax - s3 >= kSrSafeLead);
-                    if (safe_region && led == 3 && smax < 0.0 && smax > kSrSafeFloor) entry = 93;
+                if (col.cnt == 1) entry = col.entry1(table);
+                else if (col.cnt == 2) entry = col.entry2(table);
+                else if (col.cnt >= 3) {
+                    // Phred 93 without libm: the largest sum leads each of the other three by kSafeLead decades
+                    const uint32_t led = (uint32_t)(smax - col.s0 >= sr::kSafeLead) + (uint32_t)(smax - col.s1 >= sr::kSafeLead) +
+                                         (uint32_t)(smax - col.s2 >= sr::kSafeLead) + (uint32_t)(smax - col.s3 >= sr::kSafeLead);
+                    if (safe_region && led == 3 && smax < 0.0 && smax > sr::kSafeFloor) entry = 93;
                     else to_host = true;
                 }
-                if (entry == 254) atomicOr(&late[l], kSrLateNaN);
+                if (entry == sr::kEntryNaN) atomicOr(&late[l], kSrLateNaN);
             }
             const uint64_t o = o0 + (uint32_t)(c - I.trim);
-            if (valid && !to_host) {
-                cons_seq[o] = entry <= 93 ? nuc : (uint8_t)'N';
-                cons_qual[o] = entry <= 93 ? (uint8_t)(entry + 33) : (uint8_t)'$';
-            }
+            if (valid && !to_host) sr_put(entry, col.nuc(smax), cons_seq[o], cons_qual[o]);
             // the columns for the host: one atomic per wave
             const unsigned long long want = __ballot(to_host);
             if (want) {
@@ -235,12 +218,12 @@ __global__ __launch_bounds__(256) void sr_column_kernel(StoreView st, uint32_t l
                 if (to_host && at < host_cap) {
                     SrHostColumn h;
                     h.out = o;
-                    h.n = cnt;
+                    h.n = col.cnt;
                     h.layout = (uint32_t)l;
-                    h.s[0] = s0;
-                    h.s[1] = s1;
-                    h.s[2] = s2;
-                    h.s[3] = s3;
+                    h.s[0] = col.s0;
+                    h.s[1] = col.s1;
+                    h.s[2] = col.s2;
+                    h.s[3] = col.s3;
                     host_cols[at] = h;
                 }
             }

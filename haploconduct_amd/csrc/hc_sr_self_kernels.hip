@@ -12,22 +12,20 @@
 // The log table sits in LDS when it fits beside the mates (LDS_LUT) and is read from device memory otherwise.
 //
 // sr_self_merge_kernel: one lane per output column of the merged pairs: consensus() of {mate 1 at 0, mate 2 at p} (:890-903), the
-// quality from the host-built table of one- and two-member columns, the base from the exact sums by comparison (hc_sr_kernels.hip).
+// quality from the host-built table of one- and two-member columns, the base from the exact sums by comparison (hc_sr_column.h).
 // No transcendental function runs on the device.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hc_sr.h"
+#include "hc_sr_column.h"
 #include "hc_sr_self.h"
 
 namespace hc {
 namespace {
 
-__device__ inline uint32_t self_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : kCodeN; }
-
-// (row << 3 | code) of a checked symbol; an N takes row K, the all-zero row of the table
+// (row << 3 | code) of a checked symbol (the pairs are checked before the launch: code_or_n); an N takes row K, the all-zero row of the table
 __device__ inline uint16_t self_sym(uint8_t base, uint8_t q, const uint8_t* qmap_s, uint32_t K) {
-    const uint32_t code = self_code(base);
+    const uint32_t code = code_or_n(base);
     return (uint16_t)(((code == kCodeN ? K : (uint32_t)qmap_s[q]) << 3) | code);
 }
 
@@ -134,11 +132,8 @@ __global__ __launch_bounds__(256) void sr_self_merge_kernel(const uint8_t* __res
                                                             const uint64_t* __restrict__ off, uint64_t total, const double* __restrict__ terms,
                                                             const uint8_t* __restrict__ table, uint8_t* __restrict__ out_seq,
                                                             uint8_t* __restrict__ out_qual) {
-    __shared__ double t_same[kSrQIdx], t_other[kSrQIdx];
-    for (uint32_t i = threadIdx.x; i < kSrQIdx; i += blockDim.x) {
-        t_same[i] = terms[i];
-        t_other[i] = terms[kSrQIdx + i];
-    }
+    __shared__ SrTerms T;
+    T.load(terms);
     __syncthreads();
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -153,35 +148,19 @@ __global__ __launch_bounds__(256) void sr_self_merge_kernel(const uint8_t* __res
     if (p < 0) return;
     const hc_sr_pair P = pairs[lo];
     const uint32_t c = (uint32_t)(g - off[lo]);
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;  // by base code A, C, G, T
-    uint32_t cnt = 0, key = 0;
+    SrColumn col;
     for (uint32_t k = 0; k < 2; k++) {  // the members in list order: mate 1 at 0, mate 2 at p
         const bool in = k == 0 ? c < P.len1 : c >= (uint32_t)p;
         if (!in) continue;
         const uint64_t at = k == 0 ? P.off1 + c : P.off2 + (c - (uint32_t)p);
-        const uint32_t code = self_code(seq[at]);
+        const uint32_t code = code_or_n(seq[at]);
         const uint32_t q = code == kCodeN ? 0u : ((uint32_t)qual[at] - 33u) & 127u;
-        key |= (code * 128u + q) << (cnt * 16);
-        cnt++;
-        if (code < 4) {  // :309-338: the member's term goes to all four scores
-            const double a = t_same[q], b = t_other[q];
-            s0 += code == 0 ? a : b;
-            s1 += code == 1 ? a : b;
-            s2 += code == 2 ? a : b;
-            s3 += code == 3 ? a : b;
-        }
+        col.add(code, q, q, T);  // (the terms of this call are indexed by q itself)
     }
-    const double smax = fmax(fmax(s0, s3), fmax(s1, s2));
-    const uint8_t nuc = smax == s0 ? 'A' : (smax == s3 ? 'T' : (smax == s1 ? 'C' : 'G'));  // :390-393
-    uint32_t entry = 255;
-    if (cnt == 1) {
-        entry = table[kSrTable1 + (key & 0xffffu)];
-    } else if (cnt == 2) {
-        const uint32_t k1 = key & 0xffffu, k2 = key >> 16;
-        entry = table[(((k1 >> 7) * 5u + (k2 >> 7)) * 128u + (k1 & 127u)) * 128u + (k2 & 127u)];
-    }
-    out_seq[g] = entry <= 93 ? nuc : (uint8_t)'N';
-    out_qual[g] = entry <= 93 ? (uint8_t)(entry + 33) : (uint8_t)'$';
+    uint32_t entry = sr::kEntryN;
+    if (col.cnt == 1) entry = col.entry1(table);
+    else if (col.cnt == 2) entry = col.entry2(table);
+    sr_put(entry, col.nuc(col.max_sum()), out_seq[g], out_qual[g]);
 }
 
 }  // namespace

@@ -4,13 +4,7 @@
 // reference does, so that the device's closed forms (hc_sr_kernels.hip) have something independent to be compared with.
 #include "SrConsensus.h"
 
-#include <atomic>
-#include <string>
-#include <thread>
-
-namespace hc {
-int set_last_error(int status, const std::string& what);  // hc_api.cpp (or the sanitizer build's stub)
-}
+#include "InBlocks.h"
 
 namespace {
 using namespace hc;
@@ -26,17 +20,10 @@ struct MemberView {
     const uint8_t *b, *q;  // first base / quality of the stored (forward) sequence
     uint32_t len;
     bool rev;
-    // base code (0..3, 4 = N, 7 = not a base) and quality byte at position i of the oriented sequence (Read.h: get_rev_comp / get_rev_phred)
+    // base code (SrCodes.h) and quality byte at position i of the oriented sequence (Read.h: get_rev_comp / get_rev_phred)
     inline void at(uint32_t i, uint32_t& code, uint8_t& qual) const {
         const uint32_t j = rev ? len - 1 - i : i;
-        switch (b[j]) {
-            case 'A': code = 0; break;
-            case 'C': code = 1; break;
-            case 'G': code = 2; break;
-            case 'T': code = 3; break;
-            case 'N': code = 4; break;
-            default: code = 7; break;
-        }
+        code = code_of(b[j]);
         if (rev && code < 4) code = 3 - code;
         qual = q[j];
     }
@@ -160,11 +147,9 @@ int hc_host_sr_column(const uint8_t* nucleotides, const uint8_t* qualities, uint
     if (!out || (n && (!nucleotides || !qualities))) return hc::set_last_error(HC_ERR_ARG, "hc_host_sr_column: null"), 0;
     sr::Sums sums;
     for (uint32_t i = 0; i < n; i++) {
-        const uint8_t c = nucleotides[i];
-        const uint32_t code = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
         double a, b;
         sr::terms((int)qualities[i] - 33, a, b);
-        sums.add(code, a, b);
+        sums.add(code_or_n(nucleotides[i]), a, b);
     }
     return sr::finish(sums.s[0], sums.s[1], sums.s[2], sums.s[3], n, min_qual, out);
 }
@@ -187,7 +172,6 @@ int hc_host_sr_consensus(const uint8_t* bases, const uint8_t* quals, const uint6
     const Reads R{bases, quals, seq_off, read_first_seq, n_reads};
     double t_same[sr::kQDim], t_other[sr::kQDim];
     for (uint32_t q = 0; q < sr::kQDim; q++) sr::terms((int)q, t_same[q], t_other[q]);
-    const unsigned T = std::max(1u, std::min(settings->n_threads, 64u));
     // every thread takes blocks of layouts and keeps their bytes; the packed buffer is filled once the offsets are known
     struct Piece {
         std::vector<uint8_t> seq, qual;
@@ -195,30 +179,23 @@ int hc_host_sr_consensus(const uint8_t* bases, const uint8_t* quals, const uint6
     const uint64_t block = 256, n_blocks = (n_layouts + block - 1) / block;
     std::vector<Piece> pieces(n_blocks);
     std::vector<uint32_t> lens(n_layouts);
-    std::atomic<uint64_t> turn{0};
-    auto work = [&]() {
+    in_blocks(n_layouts, block, settings->n_threads, [&](uint64_t l0, uint64_t l1) {
         std::vector<MemberView> mv;
         std::vector<uint8_t> s, q;
-        for (uint64_t b = turn.fetch_add(1); b < n_blocks; b = turn.fetch_add(1)) {
-            Piece& P = pieces[b];
-            for (uint64_t l = b * block; l < std::min(n_layouts, (b + 1) * block); l++) {
-                if (!check_layout(R, layouts[l], members, n_members, mv)) {
-                    ret[l] = 0;
-                    status[l] = HC_SR_BAD_LAYOUT;
-                    lens[l] = 0;
-                    continue;
-                }
-                status[l] = one_layout(layouts[l], members + layouts[l].first_member, mv, *settings, t_same, t_other, s, q, &ret[l]);
-                lens[l] = (uint32_t)s.size();
-                P.seq.insert(P.seq.end(), s.begin(), s.end());
-                P.qual.insert(P.qual.end(), q.begin(), q.end());
+        Piece& P = pieces[l0 / block];
+        for (uint64_t l = l0; l < l1; l++) {
+            if (!check_layout(R, layouts[l], members, n_members, mv)) {
+                ret[l] = 0;
+                status[l] = HC_SR_BAD_LAYOUT;
+                lens[l] = 0;
+                continue;
             }
+            status[l] = one_layout(layouts[l], members + layouts[l].first_member, mv, *settings, t_same, t_other, s, q, &ret[l]);
+            lens[l] = (uint32_t)s.size();
+            P.seq.insert(P.seq.end(), s.begin(), s.end());
+            P.qual.insert(P.qual.end(), q.begin(), q.end());
         }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < T; t++) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
+    });
     uint64_t total = 0;
     for (uint64_t l = 0; l < n_layouts; l++) {
         out_off[l] = total;
@@ -230,8 +207,7 @@ int hc_host_sr_consensus(const uint8_t* bases, const uint8_t* quals, const uint6
         memset(stats, 0, sizeof *stats);
         stats->n_columns = total;
     }
-    if (total > cap || (total && (!cons_seq || !cons_qual)))
-        return hc::set_last_error(HC_ERR_ARG, "hc_host_sr_consensus: cons_seq / cons_qual have no room (*n_bytes says how much is needed)");
+    if (int rc = sr::check_room("hc_host_sr_consensus", "cons_seq / cons_qual", "n_bytes", total, cap, cons_seq, cons_qual)) return rc;
     for (uint64_t b = 0; b < n_blocks; b++) {
         if (pieces[b].seq.empty()) continue;
         memcpy(cons_seq + out_off[b * block], pieces[b].seq.data(), pieces[b].seq.size());

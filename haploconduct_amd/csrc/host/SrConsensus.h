@@ -7,17 +7,15 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../../include/hcsr.h"
+#include "SrCodes.h"  // the base codes, the table's geometry and entry codes, kSafeLead / kSafeFloor
 
 namespace hc {
+int set_last_error(int status, const std::string& what);  // hc_api.cpp (or the sanitizer build's stub)
 namespace sr {
-
-constexpr uint32_t kQDim = 128;                     // quality bytes 33 .. 127 as q = byte - 33 < 128
-constexpr uint32_t kTable1 = 25u * kQDim * kQDim;   // where the one-member entries start
-constexpr uint8_t kEntryN = 255, kEntryNaN = 254;   // 'N' / '$' column; consensus_pos returns 0
-// base codes as in the store (hc_device.h): A, C, G, T = 0..3, N = 4
 
 // log10(1 - p) and log10(p / 3.0) with p = phred_to_prob(Q) = pow(10, -Q/10.0)   (:289-293, :316-344)
 inline void terms(int Q, double& t_same, double& t_other) {
@@ -102,11 +100,16 @@ inline void build_table(double min_qual, const std::vector<uint32_t>& qs, uint8_
     }
 }
 
-// A deeper column that the device may finish itself (DESIGN.md "Super-read consensus"): the largest sum leads every other by at least
-// 9.3 + log10(3) + 0.01 decades, lies in (-300, 0), and min_qual <= 1 - 1e-9 — then Phred 93 and the minQual test pass whatever libm rounds.
-constexpr double kSafeLead = 9.79;  // > 9.3 + log10(3) + 0.01 = 9.7871...
-constexpr double kSafeFloor = -300.0;
+// Whether the device may finish a deeper column itself (SrCodes.h: kSafeLead, kSafeFloor) — then Phred 93 and the minQual test pass
+// whatever libm rounds.
 inline bool safe_region_allowed(double min_qual) { return min_qual <= 1 - 1e-9; }
+
+// The packed output buffers a, b of `cap` bytes are to take `total` bytes: HC_OK, or the error of entry point `fn`, whose argument
+// `counter` has been given the size to come back with.
+inline int check_room(const char* fn, const char* buffers, const char* counter, uint64_t total, uint64_t cap, const void* a, const void* b) {
+    if (total <= cap && (total == 0 || (a && b))) return HC_OK;
+    return set_last_error(HC_ERR_ARG, std::string(fn) + ": " + buffers + " have no room (*" + counter + " says how much is needed)");
+}
 
 }  // namespace sr
 }  // namespace hc

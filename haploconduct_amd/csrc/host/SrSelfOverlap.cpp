@@ -4,14 +4,9 @@
 // to be compared with.
 #include "SrSelfOverlap.h"
 
-#include <atomic>
 #include <cstring>
-#include <string>
-#include <thread>
 
-namespace hc {
-int set_last_error(int status, const std::string& what);  // hc_api.cpp (or the sanitizer build's stub)
-}
+#include "InBlocks.h"
 
 extern "C" int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes,
                                               const hc_sr_pair* pairs, uint64_t n_pairs, const hc_sr_self_settings* settings,
@@ -27,39 +22,31 @@ extern "C" int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, co
     out_off[0] = 0;
     if (n_pairs == 0) return HC_OK;
     const srself::Tables T(ec_settings->mismatch, ec_settings->min_read_len);
-    const unsigned n_thr = std::max(1u, std::min(settings->n_threads, 64u));
     struct Piece {
         std::vector<uint8_t> seq, qual;
     };
     const uint64_t block = 64, n_blocks = (n_pairs + block - 1) / block;
     std::vector<Piece> pieces(n_blocks);
     std::vector<uint32_t> lens(n_pairs);
-    std::atomic<uint64_t> turn{0};
-    auto work = [&]() {
+    in_blocks(n_pairs, block, settings->n_threads, [&](uint64_t i0, uint64_t i1) {
         std::vector<uint8_t> s, q;
-        for (uint64_t b = turn.fetch_add(1); b < n_blocks; b = turn.fetch_add(1)) {
-            Piece& P = pieces[b];
-            for (uint64_t i = b * block; i < std::min(n_pairs, (b + 1) * block); i++) {
-                overlap_pos[i] = -1;
-                score[i] = 0;
-                lens[i] = 0;
-                status[i] = srself::check_pair(seq, qual, n_bytes, pairs[i]);
-                if (status[i] != HC_SR_SELF_NONE) continue;
-                const hc_sr_pair& p = pairs[i];
-                const srself::Mates M{seq + p.off1, qual + p.off1, seq + p.off2, qual + p.off2, p.len1, p.len2};
-                overlap_pos[i] = srself::scan_pair(T, M, srself::first_offset(p.len1, settings->min_overlap), *settings, &score[i], s, q);
-                if (overlap_pos[i] < 0) continue;
-                status[i] = HC_SR_SELF_MERGED;
-                lens[i] = (uint32_t)s.size();
-                P.seq.insert(P.seq.end(), s.begin(), s.end());
-                P.qual.insert(P.qual.end(), q.begin(), q.end());
-            }
+        Piece& P = pieces[i0 / block];
+        for (uint64_t i = i0; i < i1; i++) {
+            overlap_pos[i] = -1;
+            score[i] = 0;
+            lens[i] = 0;
+            status[i] = srself::check_pair(seq, qual, n_bytes, pairs[i]);
+            if (status[i] != HC_SR_SELF_NONE) continue;
+            const hc_sr_pair& p = pairs[i];
+            const srself::Mates M{seq + p.off1, qual + p.off1, seq + p.off2, qual + p.off2, p.len1, p.len2};
+            overlap_pos[i] = srself::scan_pair(T, M, srself::first_offset(p.len1, settings->min_overlap), *settings, &score[i], s, q);
+            if (overlap_pos[i] < 0) continue;
+            status[i] = HC_SR_SELF_MERGED;
+            lens[i] = (uint32_t)s.size();
+            P.seq.insert(P.seq.end(), s.begin(), s.end());
+            P.qual.insert(P.qual.end(), q.begin(), q.end());
         }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < n_thr; t++) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
+    });
     uint64_t total = 0, n_merged = 0, n_offsets = 0;
     for (uint64_t i = 0; i < n_pairs; i++) {
         out_off[i] = total;
@@ -73,8 +60,7 @@ extern "C" int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, co
         stats->n_merged = n_merged;
         stats->n_offsets = n_offsets;
     }
-    if (total > cap || (total && (!merged_seq || !merged_qual)))
-        return set_last_error(HC_ERR_ARG, "hc_host_sr_merge_self_overlaps: merged_seq / merged_qual have no room (*n_out says how much is needed)");
+    if (int rc = sr::check_room("hc_host_sr_merge_self_overlaps", "merged_seq / merged_qual", "n_out", total, cap, merged_seq, merged_qual)) return rc;
     for (uint64_t b = 0; b < n_blocks; b++) {
         if (pieces[b].seq.empty()) continue;
         memcpy(merged_seq + out_off[b * block], pieces[b].seq.data(), pieces[b].seq.size());

@@ -6,34 +6,22 @@
 // Why overlap_score is restated here and not called: the project's EdgeCalculator::overlap_score (host/EdgeCalculator.cpp) creates a device
 // context and scores the pair with hc_score_batch, so it needs a GPU and costs a context per call.  The mirror has to run without a device
 // (the CPU tests, the sanitizer build) and about L1 * L2 / 2 positions per pair, hence the plain loop over a [same][Q1][Q2] table of log p.
-// The table's entries are the expressions of build_lut (hc_api.cpp), the third place that writes them down.  What ties the copies
-// together is not this text: tests/golden/self_overlap.json (the reference's function run whole) pins the mirror, and
-// tests/test_gpu_self_overlap.py compares the device's scores with the oracle's overlap_score bit for bit, independently of the mirror.
+// The table's entries are LogP.h's, as the scoring path's own table's are (hc_api.cpp: build_lut).  tests/golden/self_overlap.json (the
+// reference's function run whole) pins the mirror, and tests/test_gpu_self_overlap.py compares the device's scores with the oracle's
+// overlap_score bit for bit, independently of the mirror.
 #pragma once
 #include <cmath>
 #include <cstdint>
-#include <limits>
 #include <vector>
 
 #include "../../../include/hcsr.h"
+#include "LogP.h"
 #include "SrConsensus.h"
 
 namespace hc {
 namespace srself {
 
 constexpr uint32_t kQ = 94;  // quality bytes 33 .. 126 as Q = byte - 33
-
-// base code as in the store (A, C, G, T = 0..3, N = 4), 7 = not a base
-inline uint32_t code_of(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : c == 'N' ? 4u : 7u; }
-
-// what score() returns for two called bases with qualities Q1, Q2 (src/EdgeCalculator.cpp:40-55): log(p), or +inf where it returns 2
-// ("p < program_settings.mismatch")
-inline double log_p(int Q1, int Q2, bool same, double mismatch) {
-    const double p1 = pow(10, -Q1 / 10.0);  // phred_to_prob, :59-63
-    const double p2 = pow(10, -Q2 / 10.0);
-    const double p = same ? (1 - p1) * (1 - p2) + (p1 * p2) / 3.0 : p1 * (1 - p2) / 3.0 + p2 * (1 - p1) / 3.0 + (2 / 9.0) * p1 * p2;
-    return p < mismatch ? std::numeric_limits<double>::infinity() : log(p);
-}
 
 struct Tables {
     std::vector<double> lp;  // [same][Q1][Q2]
@@ -60,7 +48,7 @@ inline uint32_t check_pair(const uint8_t* seq, const uint8_t* qual, uint64_t n_b
         const uint64_t off = mate ? P.off2 : P.off1;
         const uint32_t len = mate ? P.len2 : P.len1;
         for (uint32_t i = 0; i < len; i++)
-            if (code_of(seq[off + i]) > 4 || qual[off + i] < 33 || qual[off + i] > 126) return HC_SR_SELF_BAD_SYMBOL;
+            if (code_of(seq[off + i]) > kCodeN || qual[off + i] < 33 || qual[off + i] > 126) return HC_SR_SELF_BAD_SYMBOL;
     }
     return HC_SR_SELF_NONE;
 }

@@ -195,3 +195,63 @@ def test_round_trip_from_sr_consensus():
     _srself.assert_same(dev, ref, "round trip")
     assert n >= 500 and (pairs["len1"] > 0).mean() > 0.9 and np.unique(cons.cons_qual).size > 6
     print(f"round trip: {n} pairs, {dev.n_merged} merged, {np.unique(cons.cons_qual).size} quality values")
+
+
+def _same_columns(n_values, n_pairs=64, min_overlap=5):
+    """Single-end reads (A_0, B_0, A_1, ...) of 33 .. 70 symbols, the pairs (A_i, B_i) over their packed bytes, and the two-member layouts
+    {A_i at 0, B_i at p} with p = len1 - min_overlap, the first offset of the scan.  Every tenth base is an N; B_i starts with A_i's
+    last min_overlap bases, each replaced by a random one with probability 1/2, so the shared columns agree, disagree and hold Ns."""
+    from haploconduct_amd.readstore import ReadSet
+    rng = np.random.default_rng(1000 + n_values)
+    qvals = np.array([60, 64, 66, 68, 70, 71], np.uint8) if n_values == 6 else np.arange(35, 35 + n_values, dtype=np.uint8)
+    singles = []
+    for _ in range(n_pairs):
+        a, b = (rng.choice(np.frombuffer(b"ACGTN", np.uint8), int(n), p=[0.225] * 4 + [0.1]) for n in rng.integers(33, 71, 2))
+        keep = rng.random(min_overlap) < 0.5
+        b[:min_overlap][keep] = a[-min_overlap:][keep]
+        singles += [(x.tobytes(), rng.choice(qvals, x.size).tobytes()) for x in (a, b)]
+    reads = ReadSet.from_lists(singles=singles)
+    assert np.unique(reads.quals).size == n_values
+    off = reads.seq_off
+    pairs = np.zeros(n_pairs, SR.SR_PAIR_DTYPE)
+    pairs["off1"], pairs["off2"] = off[0:-1:2], off[1:-1:2]
+    pairs["len1"], pairs["len2"] = off[1::2] - off[0:-1:2], off[2::2] - off[1:-1:2]
+    p = pairs["len1"].astype(np.int32) - min_overlap
+    members = np.zeros(2 * n_pairs, SR.SR_MEMBER_DTYPE)
+    members["read"] = np.arange(2 * n_pairs)
+    members["pos"][1::2] = p
+    layouts = np.zeros(n_pairs, SR.SR_LAYOUT_DTYPE)
+    layouts["first_member"], layouts["n_members"], layouts["total_len"] = 2 * np.arange(n_pairs), 2, pairs["len2"].astype(np.int32) + p
+    return reads, pairs, p, layouts, members
+
+
+def _assert_same_columns(merged, cons, reads, pairs, p, min_qual):
+    assert (merged.status == SR.SR_SELF_MERGED).all() and np.array_equal(merged.overlap_pos, p)
+    assert (cons.status == SR.SR_OK).all() and (cons.ret == 0).all()
+    assert np.array_equal(merged.out_off, cons.out_off) and merged.out_off[-1] == (pairs["len2"] + p).sum()
+    assert np.array_equal(merged.merged_seq, cons.cons_seq) and np.array_equal(merged.merged_qual, cons.cons_qual)
+    # The shared columns in which two called bases of comparable quality disagree: 'N' / '$' at min_qual 0.99, a base at 0.0.  (Phred values
+    # at most 10 apart: the better base's share of the total probability is then at most 10 / 11, whatever the two values are.)
+    n_disagree = n_masked = 0
+    for i, P in enumerate(pairs):
+        at1, at2, n = int(P["off1"]) + int(p[i]), int(P["off2"]), int(P["len1"]) - int(p[i])
+        a, b = reads.bases[at1:at1 + n], reads.bases[at2:at2 + n]
+        out = merged.merged_seq[int(merged.out_off[i]) + int(p[i]):int(merged.out_off[i]) + int(P["len1"])]
+        differ = (a != b) & (a != ord("N")) & (b != ord("N")) & (np.abs(reads.quals[at1:at1 + n].astype(int) - reads.quals[at2:at2 + n]) <= 10)
+        n_disagree += int(differ.sum())
+        n_masked += int((out[differ] == ord("N")).sum())
+    assert n_disagree >= 32 and n_masked == (n_disagree if min_qual == 0.99 else 0)
+
+
+@pytest.mark.parametrize("min_qual", [0.99, 0.0])
+@pytest.mark.parametrize("n_values", [6, 40])
+def test_merge_and_consensus_write_the_same_columns(n_values, min_qual):
+    """Both kernels finish a column with hc_sr_column.h.  With min_score < 0 every pair merges at its first offset p = len1 - min_overlap;
+    hc_sr_consensus on {A_i at 0, B_i at p}, total_len = len2 + p, without error correction, has to write the same bytes at the same
+    offsets.  6 quality values: the store's fused 8-bit symbols; 40: its wide ones.  Columns of one member (both ends), of two, Ns in both."""
+    reads, pairs, p, layouts, members = _same_columns(n_values)
+    with hc.EdgeScorer() as sc:
+        sc.set_reads(reads)
+        merged = sc.sr_merge_self_overlaps(reads.bases, reads.quals, pairs, min_score=-1.0, min_qual=min_qual, min_overlap=5)
+        cons = sc.sr_consensus(layouts, members, min_qual=min_qual)
+    _assert_same_columns(merged, cons, reads, pairs, p, min_qual)
