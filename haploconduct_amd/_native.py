@@ -107,12 +107,29 @@ class hc_sr_self_stats(C.Structure):
     _fields_ = [("n_merged", C.c_uint64), ("n_host_pairs", C.c_uint64), ("n_offsets", C.c_uint64), ("ms_device", C.c_double), ("ms_host", C.c_double)]
 
 
+class hc_sr_next_settings(C.Structure):
+    _fields_ = [("keep_singletons", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class hc_sr_next_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_kept", "n_dropped_empty", "n_dropped_n_rate", "n_dropped_short", "n_bad", "n_seq", "n_bytes")] + \
+               [("ms_device", C.c_double), ("ms_plan", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
 _sr_tail = [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]
 _sr_self_tail = [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_self_settings), _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p,
                  C.POINTER(hc_sr_self_stats)]
+_sr_next_tail = [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(hc_sr_next_settings), _vp, _vp, C.POINTER(hc_sr_next_counts)]
 _sig = {
+    "hc_sr_keep_device": (C.c_int, [_vp, C.c_int]),
+    "hc_sr_set_next_reads": (C.c_int, [_vp] + _sr_next_tail),
+    "hc_sr_next_reads_fetch": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, _u64p, _u64p]),
+    "hc_host_sr_next_reads": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64] + _sr_next_tail + [_vp, _vp, C.c_uint64, _u64p, _vp, _vp]),
     "hc_sr_merge_self_overlaps": (C.c_int, [_vp] + _sr_self_tail),
     "hc_host_sr_merge_self_overlaps": (C.c_int, [C.POINTER(hc_settings)] + _sr_self_tail),
     "hc_sr_consensus": (C.c_int, [_vp] + _sr_tail),

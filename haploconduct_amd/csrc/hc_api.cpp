@@ -268,51 +268,17 @@ bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting,
 }  // namespace hc
 }
 
-int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,
-                 const uint32_t* read_first_seq, uint32_t n_reads) {
-    if (!c || !seq_off || !read_first_seq) return fail(HC_ERR_ARG, "hc_set_reads: null argument");
-    HC_HIP(hipSetDevice(c->device));
+extern "C++" {
+namespace hc {
+void release_store(hc_ctx* c) { free_store(c, false); }
+
+// (b) of hc_set_reads: everything that follows from the byte histograms of the qualities (hist) and the bases (base_hist), the sequence
+// lengths (P.seq_len, P.total: filled by the caller) and which reads are pairs — the quality map with its frequency dealing and wide
+// labels, the encoding, the slots' alignment and offsets, the log-probability table.  Of the context it sets the inverse quality map
+// (sr_qbyte) and drops the consensus tables built for the old one.
+int plan_store(hc_ctx* c, const uint64_t* hist, const uint64_t* base_hist, const uint32_t* read_first_seq, uint32_t n_reads, StorePlan& P) {
     const uint32_t n_seq = read_first_seq[n_reads];
-    if (read_first_seq[0] != 0) return fail(HC_ERR_BAD_READ, "hc_set_reads: read_first_seq[0] != 0");
-    for (uint32_t r = 0; r < n_reads; r++) {
-        const uint32_t k = read_first_seq[r + 1] - read_first_seq[r];
-        if (k != 1 && k != 2) return fail(HC_ERR_BAD_READ, "hc_set_reads: a read must own 1 or 2 sequences");
-    }
-    const uint64_t total = seq_off[n_seq];
-    if (total > 0 && (!bases || !quals)) return fail(HC_ERR_ARG, "hc_set_reads: null bases/quals");
-    if (seq_off[0] != 0) return fail(HC_ERR_BAD_READ, "hc_set_reads: seq_off[0] != 0");
-    std::vector<uint32_t> seq_len(n_seq ? n_seq : 1);
-    for (uint32_t q = 0; q < n_seq; q++) {
-        if (seq_off[q + 1] <= seq_off[q])  // FastqStorage.cpp:143-146,218-221: empty sequence => exit(1)
-            return fail(HC_ERR_BAD_READ, "hc_set_reads: empty sequence");
-        const uint64_t len = seq_off[q + 1] - seq_off[q];
-        if (len >= (1ull << 28)) return fail(HC_ERR_BAD_READ, "hc_set_reads: sequence longer than 2^28-1");
-        seq_len[q] = (uint32_t)len;
-    }
-    // dense quality alphabet over the bytes the reference accepts: Q = byte-33 >= 0 as a signed char
-    uint64_t hist[256] = {0}, base_hist[256] = {0};
-    {  // byte histograms of the two arrays (300 MB each at C3): a few threads, one partial pair each
-        const unsigned T = total < (1u << 22) ? 1u : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-        std::vector<std::array<uint64_t, 512>> part(T);
-        auto work = [&](unsigned t) {
-            std::array<uint64_t, 512>& h = part[t];
-            h.fill(0);
-            const uint64_t a = total * t / T, b = total * (t + 1) / T;
-            for (uint64_t i = a; i < b; i++) {
-                h[quals[i]]++;
-                h[256 + bases[i]]++;
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < T; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto& x : th) x.join();
-        for (unsigned t = 0; t < T; t++)
-            for (int b = 0; b < 256; b++) {
-                hist[b] += part[t][(size_t)b];
-                base_hist[b] += part[t][256 + (size_t)b];
-            }
-    }
+    const std::vector<uint32_t>& seq_len = P.seq_len;
     bool any_bad_base = false;  // a base outside ACGTN somewhere (the encoder flags the sequence; the store is then not "regular")
     for (int b = 0; b < 256; b++)
         if (base_hist[b] && b != 'A' && b != 'C' && b != 'G' && b != 'T' && b != 'N') any_bad_base = true;
@@ -417,40 +383,51 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
     if (!build_lut(phred, wide_rows, c->settings.mismatch, symbytes, lut))  // (never seen: the reference's expressions commute for every Phred pair)
         return fail(HC_ERR_STATE, "hc_set_reads: the log-probability table is not symmetric in its two qualities (--mismatch within one ulp of a term?)");
 
-    // (the grow-only scratch of the finder and of the SFO ingest stays: it is capacity, not state.  A context that takes read set after read
-    // set — a pipeline's stages on parked devices — gave gigabytes back here and asked for them again in the next hc_find_overlaps, and one
-    // hipMalloc in three then took 0.75 - 0.9 s on this pool: tools/experiments/r06_find_stall_trace.sh, round 6.  hc_destroy returns it.)
-    free_store(c, false);
+    P.any_bad_base = any_bad_base;
+    memcpy(P.qmap, qmap, sizeof qmap);
+    P.K = K;
+    P.symbytes = symbytes;
+    P.slot_align = slot_align;
+    P.nsym = nsym;
+    P.sym_off = std::move(sym_off);
+    P.rc_delta = std::move(rc_delta);
+    P.lut = std::move(lut);
+    return HC_OK;
+}
+
+// (c) of hc_set_reads: the store from a plan and the raw arrays ON THE DEVICE (d_bases, d_quals, d_raw_off: n_seq + 1 offsets, d_first:
+// n_reads + 1) — encoding, descriptors, tables, locality order and the choices that follow from the set's shape.  read_first_seq is the
+// host's copy of d_first.  The caller has released the old store (release_store); the work is ordered behind whatever the context's
+// stream holds.
+int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_raw_off, const uint32_t* d_first,
+                 const uint32_t* read_first_seq, uint32_t n_reads) {
+    const uint32_t n_seq = read_first_seq[n_reads], K = P.K, symbytes = P.symbytes, slot_align = P.slot_align;
+    const uint64_t total = P.total, nsym = P.nsym;
+    const std::vector<uint32_t>& seq_len = P.seq_len;
+    const std::vector<uint64_t>& sym_off = P.sym_off;
+    const std::vector<uint32_t>& rc_delta = P.rc_delta;
+    const std::vector<double>& lut = P.lut;
+    const uint8_t* qmap = P.qmap;
+    const bool any_bad_base = P.any_bad_base;
     struct Tmp {  // freed on every return path
         void* p = nullptr;
         ~Tmp() {
             if (p) (void)hipFree(p);
         }
-    } t_bases, t_quals, t_qmap, t_seq_bad, t_raw_off, t_seq_off, t_first, t_rc_delta;
+    } t_qmap, t_seq_bad, t_seq_off, t_rc_delta;
     const uint64_t sym_bytes_total = (nsym ? nsym : 1) * symbytes;
     HC_HIP(hipMalloc(&c->d_sym, sym_bytes_total));
     HC_HIP(hipMalloc((void**)&c->d_reads, sizeof(hc::ReadDesc) * (n_reads ? n_reads : 1)));
     HC_HIP(hipMalloc((void**)&c->d_lut, sizeof(double) * lut.size()));
     HC_HIP(hipMalloc(&t_seq_off.p, sizeof(uint64_t) * (n_seq ? n_seq : 1)));
     HC_HIP(hipMalloc(&t_seq_bad.p, (n_seq ? n_seq : 1)));
-    HC_HIP(hipMalloc(&t_first.p, sizeof(uint32_t) * (n_reads + 1)));
-    HC_HIP(hipMalloc(&t_bases.p, total ? total : 1));
-    HC_HIP(hipMalloc(&t_quals.p, total ? total : 1));
-    HC_HIP(hipMalloc(&t_raw_off.p, sizeof(uint64_t) * (n_seq + 1)));
     HC_HIP(hipMalloc(&t_qmap.p, 256));
     HC_HIP(hipMalloc(&t_rc_delta.p, sizeof(uint32_t) * (n_seq ? n_seq : 1)));
-    uint8_t *d_bases = (uint8_t*)t_bases.p, *d_quals = (uint8_t*)t_quals.p, *d_qmap = (uint8_t*)t_qmap.p, *d_seq_bad = (uint8_t*)t_seq_bad.p;
-    uint64_t *d_raw_off = (uint64_t*)t_raw_off.p, *d_seq_off = (uint64_t*)t_seq_off.p;
-    uint32_t* d_first = (uint32_t*)t_first.p;
-    if (total) {
-        HC_HIP(hipMemcpyAsync(d_bases, bases, total, hipMemcpyHostToDevice, c->stream));
-        HC_HIP(hipMemcpyAsync(d_quals, quals, total, hipMemcpyHostToDevice, c->stream));
-    }
-    HC_HIP(hipMemcpyAsync(d_raw_off, seq_off, sizeof(uint64_t) * (n_seq + 1), hipMemcpyHostToDevice, c->stream));
+    uint8_t *d_qmap = (uint8_t*)t_qmap.p, *d_seq_bad = (uint8_t*)t_seq_bad.p;
+    uint64_t* d_seq_off = (uint64_t*)t_seq_off.p;
     HC_HIP(hipMemcpyAsync(d_qmap, qmap, 256, hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(d_seq_off, sym_off.data(), sizeof(uint64_t) * n_seq, hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(t_rc_delta.p, rc_delta.data(), sizeof(uint32_t) * n_seq, hipMemcpyHostToDevice, c->stream));
-    HC_HIP(hipMemcpyAsync(d_first, read_first_seq, sizeof(uint32_t) * (n_reads + 1), hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(c->d_lut, lut.data(), sizeof(double) * lut.size(), hipMemcpyHostToDevice, c->stream));
     // 1.0 / n for every count a sub-overlap can reach (n <= positions rounded up to 16 <= the longest sequence + 15): the reference's
     // `1.0/total_len` (:137) as the host's IEEE division — the same quotient the device's gives — read by the kernel instead of divided
@@ -522,7 +499,7 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
         uint32_t* idx = (uint32_t*)(keys + 2 * (size_t)n_reads);
         HC_HIP(hc::launch_locality_order(d_bases, d_raw_off, d_first, n_reads, keys, keys + n_reads, idx, c->loc_order.as<uint32_t>(),
                                          (char*)idx + idx_bytes, tmp, c->stream));
-        HC_HIP(hipStreamSynchronize(c->stream));  // (the bases are freed on return)
+        HC_HIP(hipStreamSynchronize(c->stream));  // (the caller may free the bases on return)
         c->loc_reads = n_reads;
     }
     c->have_reads = true;
@@ -574,6 +551,86 @@ int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const ui
         if (short_mixed_singles) c->fetch_group = 2;
     }
     c->view.long_rows = (n_seq && total / n_seq > 600) ? 1u : 0u;
+    return HC_OK;
+}
+}  // namespace hc
+}
+
+// hc_set_reads = (a) the checks, the byte histograms and the copies to the device + (b) plan_store + (c) finish_store
+int hc_set_reads(hc_ctx* c, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,
+                 const uint32_t* read_first_seq, uint32_t n_reads) {
+    if (!c || !seq_off || !read_first_seq) return fail(HC_ERR_ARG, "hc_set_reads: null argument");
+    HC_HIP(hipSetDevice(c->device));
+    const uint32_t n_seq = read_first_seq[n_reads];
+    if (read_first_seq[0] != 0) return fail(HC_ERR_BAD_READ, "hc_set_reads: read_first_seq[0] != 0");
+    for (uint32_t r = 0; r < n_reads; r++) {
+        const uint32_t k = read_first_seq[r + 1] - read_first_seq[r];
+        if (k != 1 && k != 2) return fail(HC_ERR_BAD_READ, "hc_set_reads: a read must own 1 or 2 sequences");
+    }
+    const uint64_t total = seq_off[n_seq];
+    if (total > 0 && (!bases || !quals)) return fail(HC_ERR_ARG, "hc_set_reads: null bases/quals");
+    if (seq_off[0] != 0) return fail(HC_ERR_BAD_READ, "hc_set_reads: seq_off[0] != 0");
+    std::vector<uint32_t> seq_len(n_seq ? n_seq : 1);
+    for (uint32_t q = 0; q < n_seq; q++) {
+        if (seq_off[q + 1] <= seq_off[q])  // FastqStorage.cpp:143-146,218-221: empty sequence => exit(1)
+            return fail(HC_ERR_BAD_READ, "hc_set_reads: empty sequence");
+        const uint64_t len = seq_off[q + 1] - seq_off[q];
+        if (len >= (1ull << 28)) return fail(HC_ERR_BAD_READ, "hc_set_reads: sequence longer than 2^28-1");
+        seq_len[q] = (uint32_t)len;
+    }
+    // dense quality alphabet over the bytes the reference accepts: Q = byte-33 >= 0 as a signed char
+    uint64_t hist[256] = {0}, base_hist[256] = {0};
+    {  // byte histograms of the two arrays (300 MB each at C3): a few threads, one partial pair each
+        const unsigned T = total < (1u << 22) ? 1u : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        std::vector<std::array<uint64_t, 512>> part(T);
+        auto work = [&](unsigned t) {
+            std::array<uint64_t, 512>& h = part[t];
+            h.fill(0);
+            const uint64_t a = total * t / T, b = total * (t + 1) / T;
+            for (uint64_t i = a; i < b; i++) {
+                h[quals[i]]++;
+                h[256 + bases[i]]++;
+            }
+        };
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < T; t++) th.emplace_back(work, t);
+        work(0);
+        for (auto& x : th) x.join();
+        for (unsigned t = 0; t < T; t++)
+            for (int b = 0; b < 256; b++) {
+                hist[b] += part[t][(size_t)b];
+                base_hist[b] += part[t][256 + (size_t)b];
+            }
+    }
+    hc::StorePlan P;
+    P.seq_len = std::move(seq_len);
+    P.total = total;
+    int rc = hc::plan_store(c, hist, base_hist, read_first_seq, n_reads, P);
+    if (rc) return rc;
+    hc::release_store(c);
+    // the raw arrays on the device: the encoder's input, freed on every return path — or, with hc_sr_keep_device on, the context's
+    hc_ctx::SrNext& N = c->srn;
+    N.raw_valid = false;
+    hc_scratch t_bases, t_quals, t_raw_off, t_first;
+    hc_scratch &s_bases = N.keep ? N.bases : t_bases, &s_quals = N.keep ? N.quals : t_quals, &s_off = N.keep ? N.off : t_raw_off,
+               &s_first = N.keep ? N.first : t_first;
+    if ((rc = s_bases.ensure_exact(total ? total : 1)) || (rc = s_quals.ensure_exact(total ? total : 1)) ||
+        (rc = s_off.ensure_exact(sizeof(uint64_t) * ((size_t)n_seq + 1))) || (rc = s_first.ensure_exact(sizeof(uint32_t) * ((size_t)n_reads + 1))))
+        return rc;
+    if (total) {
+        HC_HIP(hipMemcpyAsync(s_bases.p, bases, total, hipMemcpyHostToDevice, c->stream));
+        HC_HIP(hipMemcpyAsync(s_quals.p, quals, total, hipMemcpyHostToDevice, c->stream));
+    }
+    HC_HIP(hipMemcpyAsync(s_off.p, seq_off, sizeof(uint64_t) * ((size_t)n_seq + 1), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(s_first.p, read_first_seq, sizeof(uint32_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, c->stream));
+    rc = hc::finish_store(c, P, s_bases.as<uint8_t>(), s_quals.as<uint8_t>(), s_off.as<uint64_t>(), s_first.as<uint32_t>(), read_first_seq, n_reads);
+    if (rc) return rc;
+    if (N.keep) {
+        N.h_off.assign(seq_off, seq_off + n_seq + 1);
+        N.h_first.assign(read_first_seq, read_first_seq + n_reads + 1);
+        N.total = total;
+        N.raw_valid = true;
+    }
     return HC_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "hc_ctx.h"
 #include "hc_prims.h"
 #include "hc_sr.h"
+#include "hc_sr_next.h"
 #include "hc_sr_self.h"
 #include "host/InBlocks.h"
 #include "host/SrConsensus.h"
@@ -72,9 +73,15 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
     if (stats) memset(stats, 0, sizeof *stats);
     *n_bytes = 0;
     out_off[0] = 0;
-    if (n_layouts == 0) return HC_OK;
-    HC_HIP(hipSetDevice(c->device));
     hc_ctx::Sr& S = c->sr;
+    const bool keep = c->srn.keep;  // hc_sr_keep_device: the bytes stay on the device in their final form
+    S.kept_valid = false;
+    S.kept_bytes = 0;
+    if (n_layouts == 0) {
+        S.kept_valid = keep;
+        return HC_OK;
+    }
+    HC_HIP(hipSetDevice(c->device));
     int rc = sr_tables(c, S.tables, c->sr_qbyte, settings->min_qual);
     if (rc) return rc;
     const size_t scan_bytes = hc::prims::scan_temp_bytes(n_layouts + 1, sizeof(uint64_t));
@@ -110,7 +117,10 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         stats->ms_device = ms_a;
     }
     if ((rc = hc::sr::check_room("hc_sr_consensus", "cons_seq / cons_qual", "n_bytes", total, cap, cons_seq, cons_qual))) return rc;
-    if (total == 0) return HC_OK;
+    if (total == 0) {
+        S.kept_valid = keep;
+        return HC_OK;
+    }
     if ((rc = S.seq.ensure(total)) || (rc = S.qual.ensure(total))) return rc;
     // columns for the host: room for an eighth of all columns at first; the count tells when that was too little, and the kernel runs again
     uint64_t host_cap = std::max<uint64_t>(1u << 16, total / 8);
@@ -143,13 +153,16 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
     HC_HIP(hipStreamSynchronize(s));
     // the host's share: :348-396 with the host libm on the device's sums, spliced into the packed buffers
     const auto t0 = std::chrono::steady_clock::now();
+    std::vector<hc::SrPatch> patches(keep ? n_host : 0);
     hc::in_blocks(n_host, 4096, settings->n_threads, [&](uint64_t a, uint64_t b) {
         for (uint64_t i = a; i < b; i++) {
             const hc::SrHostColumn& h = cols[i];
             uint8_t o[2];
+            if (keep) patches[i] = hc::SrPatch{~0ull, 0, 0, {0, 0, 0, 0, 0, 0}};
             if (hc::sr::finish(h.s[0], h.s[1], h.s[2], h.s[3], h.n, settings->min_qual, o)) {
                 cons_seq[h.out] = o[0];
                 cons_qual[h.out] = o[1];
+                if (keep) patches[i] = hc::SrPatch{h.out, o[0], o[1], {0, 0, 0, 0, 0, 0}};
             } else {
                 // (several threads may store the same value)
                 reinterpret_cast<std::atomic<uint32_t>*>(&late[h.layout])->fetch_or(hc::kSrLateNaN, std::memory_order_relaxed);
@@ -177,6 +190,21 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         }
         out_off[n_layouts] = w;
         *n_bytes = w;
+    }
+    if (keep) {
+        if (any_late) {  // (next to never: layouts left the packed buffers, and the kept bytes follow the host's)
+            if (*n_bytes) {
+                HC_HIP(hipMemcpyAsync(S.seq.p, cons_seq, *n_bytes, hipMemcpyHostToDevice, s));
+                HC_HIP(hipMemcpyAsync(S.qual.p, cons_qual, *n_bytes, hipMemcpyHostToDevice, s));
+            }
+        } else if (n_host) {  // one scatter of the columns the host threads finished
+            if ((rc = S.patches.ensure(n_host * sizeof(hc::SrPatch)))) return rc;
+            HC_HIP(hipMemcpyAsync(S.patches.p, patches.data(), n_host * sizeof(hc::SrPatch), hipMemcpyHostToDevice, s));
+            HC_HIP(hc::sr_launch_patch(S.patches.as<hc::SrPatch>(), n_host, total, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), s));
+        }
+        HC_HIP(hipStreamSynchronize(s));  // (the host vectors go out of scope)
+        S.kept_bytes = *n_bytes;
+        S.kept_valid = true;
     }
     if (stats) {
         stats->n_columns = *n_bytes;

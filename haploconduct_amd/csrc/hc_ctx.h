@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -108,6 +109,26 @@ int set_last_error(int status, const std::string& what);  // thread-local text b
 // log-probability table of the scoring path in its 16-bit-symbol layout (hc_device.h: two triangles of (K + 2) rows) for the Phred values
 // `phred`; false: the table is not symmetric in the two qualities
 Band threshold_band(double T, int log2_width);
+// hc_api.cpp: hc_set_reads in parts, for the calls that replace the store from raw arrays that are on the device already
+// (hc_api_sr_next.cpp).  hc_set_reads = its own checks, histograms and copies + plan_store + release_store + finish_store.
+struct StorePlan {
+    std::vector<uint32_t> seq_len;  // in: the sequences' lengths (one entry at least)
+    uint64_t total = 0;             // in: their sum
+    uint8_t qmap[256];              // quality byte -> quality index as the symbols carry it, 255: not a quality value of the set
+    uint32_t K = 0, symbytes = 0, slot_align = 0;
+    uint64_t nsym = 0;
+    std::vector<uint64_t> sym_off;
+    std::vector<uint32_t> rc_delta;
+    std::vector<double> lut;
+    bool any_bad_base = false;
+};
+}  // namespace hc
+struct hc_ctx;
+namespace hc {
+int plan_store(hc_ctx* c, const uint64_t* hist, const uint64_t* base_hist, const uint32_t* read_first_seq, uint32_t n_reads, StorePlan& P);
+void release_store(hc_ctx* c);
+int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_raw_off, const uint32_t* d_first,
+                 const uint32_t* read_first_seq, uint32_t n_reads);
 bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting, std::vector<double>& lut);
 }  // namespace hc
 
@@ -132,6 +153,19 @@ struct hc_scratch {
         else HC_HIP(hipMalloc(&p, want));
         cap = want;
         return HC_OK;
+    }
+    int ensure_exact(size_t bytes) {  // the same without the headroom: a block sized once per read set
+        if (bytes <= cap) return HC_OK;
+        release();
+        if (host) HC_HIP(hipHostMalloc(&p, bytes, hipHostMallocMapped));
+        else HC_HIP(hipMalloc(&p, bytes));
+        cap = bytes;
+        return HC_OK;
+    }
+    void swap(hc_scratch& o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        std::swap(host, o.host);
     }
     void release() {
         if (p) (void)(host ? hipHostFree(p) : hipFree(p));
@@ -273,7 +307,23 @@ struct hc_ctx {
     struct Sr {
         hc_scratch layouts, members, mem, info, len, off, temp, seq, qual, late, host_cols, counter;
         SrTables tables;
+        // hc_sr_keep_device: seq / qual hold the last call's bytes in their final form (kept_bytes of them), patched by `patches`
+        hc_scratch patches;
+        bool kept_valid = false;
+        uint64_t kept_bytes = 0;
     } sr;
+    // hc_sr_keep_device / hc_sr_set_next_reads (hc_api_sr_next.cpp).  While `keep` is on, the raw arrays of the current store stay on the
+    // device (bases, quals, off: n_seq + 1 offsets, first: n_reads + 1) with host copies of the two small ones; a call gathers the next
+    // store's into the next_* blocks, which then trade places with them.  The rest is grow-only scratch of one call.
+    struct SrNext {
+        bool keep = false, raw_valid = false;
+        hc_scratch bases, quals, off, first;
+        uint64_t total = 0;
+        std::vector<uint64_t> h_off;
+        std::vector<uint32_t> h_first;
+        hc_scratch next_bases, next_quals, next_off, next_first;
+        hc_scratch entries, status, cnt, bytes, cnt_off, byte_off, temp, hist, extra_seq, extra_qual;
+    } srn;
     // self-overlap merge (hc_api_sr.cpp: hc_sr_merge_self_overlaps): grow-only scratch; the consensus tables are rebuilt when min_qual or
     // the batch's quality values change (term index = the value itself)
     struct SrSelf {

@@ -67,6 +67,27 @@ class EdgeScorer:
         st = SR.make_self_settings(min_score, min_qual, min_overlap, n_threads)
         return SR.run_self(lambda *a: N.lib.hc_sr_merge_self_overlaps(self._ctx, *a), seq, qual, pairs, st, count_first)
 
+    # -- the next iteration's store from super-reads (include/hcsr.h) -----------
+    def sr_keep_device(self, on=True):
+        """hc_sr_keep_device: set_reads keeps its raw arrays and sr_consensus its output on the device (off by default)."""
+        N.check(N.lib.hc_sr_keep_device(self._ctx, int(bool(on))), "hc_sr_keep_device")
+
+    def sr_set_next_reads(self, entries, extra_seq=None, extra_qual=None, keep_singletons=0):
+        """hc_sr_set_next_reads: filter, number and gather the entries (next_reads.NEXT_ENTRY_DTYPE) on the device and replace the store
+        by the survivors.  Returns a next_reads.NextReads (empty = True: nothing was kept, the old store is in place)."""
+        from . import next_reads as NR
+
+        res = NR.set_next_reads(self._ctx, entries, extra_seq, extra_qual, keep_singletons)
+        if not res.empty:
+            self._reads = None  # (the new reads live on the device: sr_next_reads_fetch)
+        return res
+
+    def sr_next_reads_fetch(self):
+        """hc_sr_next_reads_fetch: the kept raw arrays of the current store as a ReadSet."""
+        from . import next_reads as NR
+
+        return NR.fetch(self._ctx)
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

@@ -184,6 +184,114 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
                                    int32_t* overlap_pos, double* score, uint32_t* status, uint64_t* out_off, uint8_t* merged_seq,
                                    uint8_t* merged_qual, uint64_t cap, uint64_t* n_out, hc_sr_self_stats* stats);
 
+/* ---- the next iteration's read store from super-reads, without leaving the device ---------------------------------------
+ *
+ * Between one SAVAGE / POLYTE iteration and the next the reference filters the super-reads (process_cliques,
+ * src/SRBuilder.cpp:983,986-996,999-1001; Read::get_len / test_N_rate, src/Read.h:203-234), numbers the survivors and adds
+ * the trivial super-reads (src/SRBuilder.cpp:1141-1233,1278-1380: single-end super-reads from id 0, the trivial ones in
+ * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
+ * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
+ * context's read store by the result.
+ * Left to the caller: the subread / original-index maps and subreads.txt; ignore_inclusions and the tip handling of
+ * mergeAlongEdges (:1298-1311: the caller omits those vertices); the FASTQ text itself; a device-input form of
+ * hc_sr_merge_self_overlaps. */
+
+/* Off by default: every other call then behaves and allocates as it does without this section.  While it is on, hc_set_reads
+ * keeps its device copies of the raw base, quality and offset arrays (trivial super-reads are copied from them: the encoded
+ * store cannot serve, its wide encodings drop the quality byte of an N) and hc_sr_consensus leaves its packed cons_seq /
+ * cons_qual bytes on the device in their final form (the columns host threads finish are written back by one scatter launch;
+ * the bytes returned to the host are the same).  Turning it off releases what was kept. */
+int hc_sr_keep_device(hc_ctx* ctx, int on);
+
+enum {
+    HC_SR_NEXT_SINGLE = 0,        /* a single-end super-read: mate 1 only                                                    */
+    HC_SR_NEXT_PAIRED = 1,        /* a paired super-read: mate 1 and mate 2                                                  */
+    HC_SR_NEXT_TRIVIAL = 2,       /* a trivial super-read: single-end read `read` of the current store                       */
+    HC_SR_NEXT_TRIVIAL_PAIRED = 3 /* the same for a paired read (the writers send the two to different files, :1461-1500)    */
+};
+enum {
+    HC_SR_SRC_CONSENSUS = 0, /* the kept cons_seq / cons_qual of the last hc_sr_consensus (the mirror: the arrays passed)   */
+    HC_SR_SRC_BYTES = 1      /* extra_seq / extra_qual of this call: hc_sr_merge_self_overlaps' merged reads, or anything
+                                else the caller holds on the host                                                          */
+};
+
+/* One candidate read of the next iteration. */
+typedef struct hc_sr_next_entry {
+    uint64_t off1, off2; /* a super-read: first byte of mate 1 / mate 2 in its source                                    */
+    uint32_t len1, len2; /* a super-read: their lengths (len2 is not read for HC_SR_NEXT_SINGLE)                          */
+    uint32_t read;       /* a trivial: index of the read in the current store                                            */
+    uint8_t kind;        /* HC_SR_NEXT_*                                                                                 */
+    uint8_t src1, src2;  /* a super-read: HC_SR_SRC_* of mate 1 / mate 2                                                  */
+    uint8_t rev;         /* a trivial: 1 = the reverse vertex, taken as rev_comp(0) or (rev_comp(2), rev_comp(1)) with the
+                            reversed Phred strings (:1342,1355)                                                         */
+} hc_sr_next_entry; /* 32 bytes */
+
+typedef struct hc_sr_next_settings {
+    uint32_t keep_singletons; /* program_settings.keep_singletons, :1286 */
+    uint32_t reserved;
+} hc_sr_next_settings; /* 8 bytes */
+
+/* Per-entry status.  The tests run in this order. */
+enum {
+    HC_SR_NEXT_KEPT = 0,
+    HC_SR_NEXT_DROPPED_EMPTY = 1,  /* a super-read with an empty mate: get_seq(0) == "" (:999), get_seq(1) or get_seq(2) == ""
+                                      (:983: the pair is dropped whole)                                                   */
+    HC_SR_NEXT_DROPPED_N_RATE = 2, /* test_N_rate is false: not (double)N_count < 0.05 * (double)len, over the
+                                      concatenation of the mates for a pair (src/Read.h:214-234)                          */
+    HC_SR_NEXT_DROPPED_SHORT = 3,  /* a trivial with get_len() < keep_singletons, len1 + len2 for a pair (:1286; tested
+                                      before the N rate, :1292)                                                           */
+    HC_SR_NEXT_BAD_ENTRY = 4       /* refused: kind > 3, src > 1, rev > 1, a range that does not lie inside its source, a
+                                      mate of 2^28 bytes or more (hc_set_reads refuses such a sequence), a read index >=
+                                      the store's reads, HC_SR_NEXT_TRIVIAL on a paired read or HC_SR_NEXT_TRIVIAL_PAIRED
+                                      on a single-end one.  Nothing is read for it.                                       */
+};
+
+typedef struct hc_sr_next_counts {
+    uint64_t n_kept, n_dropped_empty, n_dropped_n_rate, n_dropped_short, n_bad;
+    uint64_t n_seq;   /* sequences of the new store  */
+    uint64_t n_bytes; /* bases of the new store      */
+    double ms_device; /* device call only: the kernels of this section, by events on the context's stream */
+    double ms_plan;   /* device call only: the host's planning between them and the encoder              */
+} hc_sr_next_counts; /* 72 bytes */
+
+/* hc_sr_set_next_reads: HC_OK is 0; an empty result is no error of the arguments and has a status of its own. */
+#define HC_SR_NEXT_EMPTY 1
+
+/* Needs hc_sr_keep_device(ctx, 1) before the hc_set_reads that loaded the current store (HC_ERR_STATE otherwise).
+ * The entries are taken in the order given — the caller lists them as the writers do: singles, trivials, pairs — and
+ * new_id[i] = the rank of entry i among the kept ones (the read's index in the new store and its decimal FASTQ id), or -1;
+ * status[i] = HC_SR_NEXT_*.  extra_seq / extra_qual (n_extra bytes each, may be NULL with n_extra = 0) are uploaded by the call.
+ * A reverse trivial is written back to front with build_rev_comp's mapping (Types.h:109-129: A<->T, C<->G, N->N; any other byte,
+ * on which the reference exits, is copied as it is and the new store flags the sequence as hc_set_reads does).
+ * The survivors' raw bytes are gathered into new raw arrays on the device, and the context's store is replaced from them
+ * exactly as hc_set_reads would replace it from the same arrays on the host: the same quality map, encoding, slot alignment,
+ * `regular` flag, locality order and tables, and the same dependent state is invalidated.  The new raw arrays become the kept
+ * ones; the kept consensus bytes stay as they are.
+ * When nothing is kept: HC_SR_NEXT_EMPTY, new_id / status / counts filled, the old store in place.
+ * counts may be NULL. */
+int hc_sr_set_next_reads(hc_ctx* ctx, const hc_sr_next_entry* entries, uint64_t n, const uint8_t* extra_seq, const uint8_t* extra_qual,
+                         uint64_t n_extra, const hc_sr_next_settings* settings, int32_t* new_id, uint32_t* status,
+                         hc_sr_next_counts* counts);
+
+/* The kept raw arrays — what hc_set_reads or hc_sr_set_next_reads last loaded while keeping was on — in the form
+ * hc_set_reads takes: for the writer of singles.fastq / paired*.fastq, once, off the critical path.
+ * *n_bytes / *n_seq / *n_reads are always filled.  cap_bytes = room of bases and quals each, cap_seq = entries seq_off has
+ * room for beyond its first (n_seq + 1 are written) and read_first_seq likewise (n_reads + 1 <= n_seq + 1 are written);
+ * where either is too small or a buffer is NULL nothing is copied and HC_ERR_ARG is returned (count, then fetch). */
+int hc_sr_next_reads_fetch(hc_ctx* ctx, uint8_t* bases, uint8_t* quals, uint64_t cap_bytes, uint64_t* seq_off, uint32_t* read_first_seq,
+                           uint64_t cap_seq, uint64_t* n_bytes, uint64_t* n_seq, uint64_t* n_reads);
+
+/* The same contract on the host (no device, no context): the current store as hc_set_reads takes it, the consensus bytes
+ * (n_cons each), the entries — and the four arrays one would pass to hc_set_reads next.  out_seq_off needs room for
+ * 2 n + 1 entries and out_read_first_seq for n + 1; cap / *n_bytes as above (too small or NULL: HC_ERR_ARG, everything but
+ * the bytes filled).  An empty result returns HC_SR_NEXT_EMPTY. */
+int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off, const uint32_t* read_first_seq,
+                          uint32_t n_reads, const uint8_t* cons_seq, const uint8_t* cons_qual, uint64_t n_cons,
+                          const hc_sr_next_entry* entries, uint64_t n, const uint8_t* extra_seq, const uint8_t* extra_qual,
+                          uint64_t n_extra, const hc_sr_next_settings* settings, int32_t* new_id, uint32_t* status,
+                          hc_sr_next_counts* counts, uint8_t* out_bases, uint8_t* out_quals, uint64_t cap, uint64_t* n_bytes,
+                          uint64_t* out_seq_off, uint32_t* out_read_first_seq);
+
 #ifdef __cplusplus
 }
 #endif
