@@ -99,6 +99,10 @@ class hc_sr_stats(C.Structure):
     _fields_ = [("n_columns", C.c_uint64), ("n_host_columns", C.c_uint64), ("ms_device", C.c_double), ("ms_host_finish", C.c_double)]
 
 
+class hc_merge_pairs_stats(C.Structure):
+    _fields_ = [("ms_kernel", C.c_double), ("ms_copy", C.c_double), ("ms_walk", C.c_double)]
+
+
 class hc_sr_self_settings(C.Structure):
     _fields_ = [("min_score", C.c_double), ("min_qual", C.c_double), ("min_overlap", C.c_uint32), ("n_threads", C.c_uint32)]
 
@@ -137,6 +141,12 @@ _sig = {
     "hc_host_sr_column": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_double, _vp]),
     "hc_host_sr_table": (C.c_int, [C.c_double, C.c_uint32, _vp]),
     "hc_host_sr_edge_layouts": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp, _u64p]),
+    "hc_graph_merge_pairs": (C.c_int, [_vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_merge_pairs_stats)]),
+    "hc_host_graph_merge_pairs": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _u64p]),
+    "hc_sr_edge_merge": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]),
+    "hc_host_sr_edge_merge_layouts": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.POINTER(hc_sr_settings), _vp,
+                                                _vp, _vp, _vp, _vp, _vp]),
     "hc_version": (C.c_char_p, []),
     "hc_strerror": (C.c_char_p, [C.c_int]),
     "hc_last_error": (C.c_char_p, []),

@@ -82,6 +82,100 @@ def edge_layouts(edges, reads):
     return layouts, members
 
 
+# ---- edge merges on a graph (hc_graph_merge_pairs, hc_sr_edge_merge) ------------------------------------------------------
+SR_SUBREAD_DTYPE = np.dtype([("index1", "<i4"), ("startpos1", "<i4"), ("index2", "<i4"), ("startpos2", "<i4")], align=False)  # hc_sr_subread_info
+assert SR_SUBREAD_DTYPE.itemsize == 16
+SR_EDGE_OK, SR_EDGE_NO_EDGE, SR_EDGE_BAD_VERTEX, SR_EDGE_READ_MISMATCH, SR_EDGE_PAIRED_NEG_POS, SR_EDGE_BAD_GEOMETRY = range(6)
+
+
+@dataclass
+class SrEdgeLayouts:
+    pair_status: np.ndarray   # uint32 per pair: SR_EDGE_*
+    first_layout: np.ndarray  # uint64, n_pairs + 1
+    layouts: np.ndarray       # SR_LAYOUT_DTYPE, packed in pair order ('l' before 'r')
+    members: np.ndarray       # SR_MEMBER_DTYPE, packed
+    subreads: np.ndarray      # SR_SUBREAD_DTYPE, (n_pairs, 2): the smaller, the larger vertex (None: the mirror without ret)
+    result: SrResult = None   # the device call: hc_sr_consensus' outputs for the layouts
+
+
+def merge_pairs(call, n_vertices):
+    """call(pairs_ptr, cap, n_pairs_ref) -> status; the pairs of getEdgesForMerging (src/GraphAlgos.cpp:112-148) as an (n, 2) uint32 array."""
+    pairs = np.zeros((n_vertices // 2 + 1, 2), np.uint32)
+    n = C.c_uint64(0)
+    N.check(call(pairs.ctypes.data, pairs.shape[0], C.byref(n)), "merge_pairs")
+    return pairs[:int(n.value)].copy()
+
+
+def _edge_buffers(pairs):
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    n = pairs.shape[0]
+    return pairs, n, np.zeros(n, np.uint32), np.zeros(n + 1, np.uint64), np.zeros(2 * n, SR_LAYOUT_DTYPE), np.zeros(6 * n, SR_MEMBER_DTYPE)
+
+
+def _trim(status, first, layouts, members, subreads, result=None):
+    nl = int(first[-1])
+    nm = int(layouts["n_members"][:nl].astype(np.int64).sum())
+    return SrEdgeLayouts(status, first, layouts[:nl], members[:nm], subreads, result)
+
+
+def edge_merge(ctx, pairs, vertex_read, vertex_fwd, settings, cap=None):
+    """hc_sr_edge_merge on the context's graph and store: constructSuperread's ordering, sort_vertices, consensus and calcSubreadInfo
+    (src/SRBuilder.cpp:654-698, 33-285, 413-535, 536-595) for every pair of vertices.  Returns an SrEdgeLayouts with .result set.
+    cap: room for the consensus bytes; None asks with cap = 0 first and calls again with exactly the bytes needed."""
+    pairs, n, status, first, layouts, members = _edge_buffers(pairs)
+    vr = np.ascontiguousarray(vertex_read, dtype=np.uint32)
+    vf = np.ascontiguousarray(vertex_fwd, dtype=np.uint8)
+    if vr.size != vf.size:
+        raise ValueError("vertex_read and vertex_fwd differ in length")
+    sub = np.zeros((n, 2), SR_SUBREAD_DTYPE)
+    ret, lstat, out_off = np.zeros(2 * n, np.int32), np.zeros(2 * n, np.uint32), np.zeros(2 * n + 1, np.uint64)
+    n_bytes = C.c_uint64(0)
+    stats = N.hc_sr_stats()
+
+    def once(seq, qual, room):
+        return N.lib.hc_sr_edge_merge(ctx, _ptr(pairs), n, _ptr(vr), _ptr(vf), vr.size, C.byref(settings), _ptr(status), first.ctypes.data,
+                                      _ptr(layouts), _ptr(members), _ptr(sub), _ptr(ret), _ptr(lstat), out_off.ctypes.data, _ptr(seq), _ptr(qual), room,
+                                      C.byref(n_bytes), C.byref(stats))
+
+    if cap is None:
+        empty = np.zeros(0, np.uint8)
+        rc = once(empty, empty, 0)
+        if rc != 0 and n_bytes.value == 0:
+            N.check(rc, "sr_edge_merge")
+        cap = int(n_bytes.value)
+        seq, qual = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        if cap:
+            N.check(once(seq, qual, cap), "sr_edge_merge")
+    else:
+        seq, qual = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        N.check(once(seq, qual, cap), "sr_edge_merge")
+    nl, nb = int(first[-1]), int(n_bytes.value)
+    res = SrResult(ret[:nl], lstat[:nl], out_off[:nl + 1], seq[:nb], qual[:nb], int(stats.n_columns), int(stats.n_host_columns), float(stats.ms_device),
+                   float(stats.ms_host_finish))
+    return _trim(status, first, layouts, members, sub, res)
+
+
+def host_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fwd, settings, ret=None):
+    """hc_host_sr_edge_merge_layouts: the layouts (and, given the layouts' ret, the subread infos) of edge_merge on a host graph
+    (hc_graph_fetch's edges / out_off) and a ReadSet."""
+    from .host import EDGE_DTYPE
+
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    oo = np.ascontiguousarray(out_off, dtype=np.uint64)
+    pairs, n, status, first, layouts, members = _edge_buffers(pairs)
+    vr = np.ascontiguousarray(vertex_read, dtype=np.uint32)
+    vf = np.ascontiguousarray(vertex_fwd, dtype=np.uint8)
+    sub = None
+    if ret is not None:
+        ret = np.ascontiguousarray(ret, dtype=np.int32)
+        sub = np.zeros((n, 2), SR_SUBREAD_DTYPE)
+    N.check(N.lib.hc_host_sr_edge_merge_layouts(_ptr(edges), oo.ctypes.data, oo.size - 1, reads.seq_off.ctypes.data, reads.read_first_seq.ctypes.data,
+                                                reads.n_reads, _ptr(pairs), n, _ptr(vr), _ptr(vf), C.byref(settings), _ptr(status), first.ctypes.data,
+                                                _ptr(layouts), _ptr(members), None if ret is None else ret.ctypes.data,
+                                                None if sub is None else _ptr(sub)), "sr_edge_merge_layouts")
+    return _trim(status, first, layouts, members, sub)
+
+
 def column(nucleotides, qualities, min_qual=0.99):
     """consensus_pos for one column given as byte strings: (nucleotide, quality byte), or None where it returns 0."""
     out = (C.c_uint8 * 2)()

@@ -2,6 +2,8 @@
 // batch of layouts on the device.  The host builds what depends on libm — the per-quality log10 terms and the table of one- and
 // two-member columns, once per read set and min_qual —, the kernels of hc_sr_kernels.hip do the rest, and the columns they could not
 // decide by comparisons come back as four sums that host threads finish with the reference's expressions (host/SrConsensus.h).
+// hc_sr_consensus is in parts (hc_ctx.h: sr_consensus_begin / _room / _run) so that hc_sr_edge_merge (hc_api_sr_edge.cpp), whose layouts are
+// on the device already, runs the same code from there on.
 // hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end of this file.  Both calls build
 // their consensus tables with sr_tables and run their host loops with in_blocks (host/InBlocks.h).
 #include <hip/hip_runtime.h>
@@ -62,25 +64,17 @@ int sr_tables(hc_ctx* c, hc_ctx::SrTables& T, const uint8_t* q_of, double min_qu
 
 }  // namespace
 
-extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t n_layouts, const hc_sr_member* members, uint64_t n_members,
-                               const hc_sr_settings* settings, int32_t* ret, uint32_t* status, uint64_t* out_off, uint8_t* cons_seq,
-                               uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats) {
-    if (!c || !settings || !out_off || !n_bytes || (n_layouts && (!layouts || !ret || !status)) || (n_members && !members))
-        return fail(HC_ERR_ARG, "hc_sr_consensus: null argument");
-    if (!c->have_reads) return fail(HC_ERR_STATE, "hc_sr_consensus: hc_set_reads first");
-    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, "hc_sr_consensus: min_qual is NaN");
-    if (n_layouts >= (1ull << 32) - 1 || n_members >= (1ull << 32)) return fail(HC_ERR_ARG, "hc_sr_consensus: more than 2^32 - 2 layouts or members");
+int hc::sr_consensus_begin(hc_ctx* c, uint64_t* out_off, uint64_t* n_bytes, hc_sr_stats* stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     *n_bytes = 0;
     out_off[0] = 0;
+    c->sr.kept_valid = false;
+    c->sr.kept_bytes = 0;
+    return HC_OK;
+}
+
+int hc::sr_consensus_room(hc_ctx* c, const hc_sr_settings* settings, uint64_t n_layouts, uint64_t n_members) {
     hc_ctx::Sr& S = c->sr;
-    const bool keep = c->srn.keep;  // hc_sr_keep_device: the bytes stay on the device in their final form
-    S.kept_valid = false;
-    S.kept_bytes = 0;
-    if (n_layouts == 0) {
-        S.kept_valid = keep;
-        return HC_OK;
-    }
     HC_HIP(hipSetDevice(c->device));
     int rc = sr_tables(c, S.tables, c->sr_qbyte, settings->min_qual);
     if (rc) return rc;
@@ -91,10 +85,43 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         (rc = S.temp.ensure(scan_bytes ? scan_bytes : 16)) || (rc = S.late.ensure(n_layouts * sizeof(uint32_t))) ||
         (rc = S.counter.ensure(sizeof(unsigned long long))))
         return rc;
+    return HC_OK;
+}
+
+extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t n_layouts, const hc_sr_member* members, uint64_t n_members,
+                               const hc_sr_settings* settings, int32_t* ret, uint32_t* status, uint64_t* out_off, uint8_t* cons_seq,
+                               uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats) {
+    if (!c || !settings || !out_off || !n_bytes || (n_layouts && (!layouts || !ret || !status)) || (n_members && !members))
+        return fail(HC_ERR_ARG, "hc_sr_consensus: null argument");
+    if (!c->have_reads) return fail(HC_ERR_STATE, "hc_sr_consensus: hc_set_reads first");
+    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, "hc_sr_consensus: min_qual is NaN");
+    if (n_layouts >= (1ull << 32) - 1 || n_members >= (1ull << 32)) return fail(HC_ERR_ARG, "hc_sr_consensus: more than 2^32 - 2 layouts or members");
+    hc::sr_consensus_begin(c, out_off, n_bytes, stats);
+    if (n_layouts) {
+        int rc = hc::sr_consensus_room(c, settings, n_layouts, n_members);
+        if (rc) return rc;
+        hc_ctx::Sr& S = c->sr;
+        HC_HIP(hipMemcpyAsync(S.layouts.p, layouts, n_layouts * sizeof(hc_sr_layout), hipMemcpyHostToDevice, c->stream));
+        if (n_members) HC_HIP(hipMemcpyAsync(S.members.p, members, n_members * sizeof(hc_sr_member), hipMemcpyHostToDevice, c->stream));
+    }
+    return hc::sr_consensus_run(c, "hc_sr_consensus", n_layouts, n_members, settings, ret, status, out_off, cons_seq, cons_qual, cap, n_bytes, stats,
+                                nullptr);
+}
+
+// From the layouts and members on the device (S.layouts, S.members; the blocks of sr_consensus_room) on.
+int hc::sr_consensus_run(hc_ctx* c, const char* me, uint64_t n_layouts, uint64_t n_members, const hc_sr_settings* settings, int32_t* ret,
+                         uint32_t* status, uint64_t* out_off, uint8_t* cons_seq, uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes,
+                         hc_sr_stats* stats, bool* ret_late) {
+    hc_ctx::Sr& S = c->sr;
+    const bool keep = c->srn.keep;  // hc_sr_keep_device: the bytes stay on the device in their final form
+    if (ret_late) *ret_late = false;
+    if (n_layouts == 0) {
+        S.kept_valid = keep;
+        return HC_OK;
+    }
+    int rc;
     hipStream_t s = c->stream;
     float ms_a = 0, ms_b = 0;
-    HC_HIP(hipMemcpyAsync(S.layouts.p, layouts, n_layouts * sizeof(hc_sr_layout), hipMemcpyHostToDevice, s));
-    if (n_members) HC_HIP(hipMemcpyAsync(S.members.p, members, n_members * sizeof(hc_sr_member), hipMemcpyHostToDevice, s));
     const uint32_t minimum_support = settings->subreads_needed ? 2u : settings->min_clique_size;  // :421-427
     HC_HIP(hipEventRecord(c->ev0, s));
     HC_HIP(hc::sr_launch_layouts(c->view, S.layouts.as<hc_sr_layout>(), n_layouts, S.members.as<hc_sr_member>(), n_members, minimum_support,
@@ -116,7 +143,7 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         stats->n_columns = total;
         stats->ms_device = ms_a;
     }
-    if ((rc = hc::sr::check_room("hc_sr_consensus", "cons_seq / cons_qual", "n_bytes", total, cap, cons_seq, cons_qual))) return rc;
+    if ((rc = hc::sr::check_room(me, "cons_seq / cons_qual", "n_bytes", total, cap, cons_seq, cons_qual))) return rc;
     if (total == 0) {
         S.kept_valid = keep;
         return HC_OK;
@@ -142,7 +169,7 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
         HC_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         ms_b += ms;
         if (n_host <= host_cap) break;
-        if (pass == 1) return fail(HC_ERR_STATE, "hc_sr_consensus: the host's column count grew between two identical launches");
+        if (pass == 1) return fail(HC_ERR_STATE, std::string(me) + ": the host's column count grew between two identical launches");
         host_cap = n_host;
     }
     std::vector<hc::SrHostColumn> cols(n_host);
@@ -179,7 +206,10 @@ extern "C" int hc_sr_consensus(hc_ctx* c, const hc_sr_layout* layouts, uint64_t 
             out_off[l] = w;
             if (late[l]) {
                 status[l] = (late[l] & hc::kSrLateBadSymbol) ? HC_SR_BAD_SYMBOL : HC_SR_NAN;
-                if (late[l] & hc::kSrLateBadSymbol) ret[l] = 0;
+                if (late[l] & hc::kSrLateBadSymbol) {
+                    ret[l] = 0;
+                    if (ret_late) *ret_late = true;
+                }
                 continue;
             }
             if (len && w != a) {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/hcedge.h"
+#include "../../include/hcsr.h"
 #include "hc_device.h"
 #include "hc_overlap_finder.h"
 
@@ -330,7 +331,22 @@ struct hc_ctx {
         hc_scratch seq, qual, pairs, skip, qmap, lut, inv_n, res, len, off, mpos, temp, out_seq, out_qual;
         SrTables tables;
     } sr_self;
+    // edge merge (hc_api_sr_edge.cpp: hc_graph_merge_pairs, hc_sr_edge_merge): grow-only scratch — the target column; the call's pairs and
+    // vertex tables, the pairs' slots (hc_sr.h: SrEdgeSlots), the two sums and the subread infos
+    struct SrEdge {
+        hc_scratch targets, pairs, vread, vfwd, status, lay_cnt, mem_cnt, first, mem_off, layouts, members, who, sub, temp;
+    } sr_edge;
 };
+
+namespace hc {
+// hc_api_sr.cpp: hc_sr_consensus in parts, for the calls whose layouts are on the device already (hc_api_sr_edge.cpp).
+// hc_sr_consensus = its own checks + sr_consensus_begin + sr_consensus_room + the upload of layouts and members + sr_consensus_run.
+// `me` prefixes the error texts.  *ret_late (may be NULL): a layout failed late and its ret is no longer the device's.
+int sr_consensus_begin(hc_ctx* c, uint64_t* out_off, uint64_t* n_bytes, hc_sr_stats* stats);
+int sr_consensus_room(hc_ctx* c, const hc_sr_settings* settings, uint64_t n_layouts, uint64_t n_members);
+int sr_consensus_run(hc_ctx* c, const char* me, uint64_t n_layouts, uint64_t n_members, const hc_sr_settings* settings, int32_t* ret, uint32_t* status,
+                     uint64_t* out_off, uint8_t* cons_seq, uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats, bool* ret_late);
+}  // namespace hc
 
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,
                  hc_gather_row* rows, unsigned long long* row_count, uint64_t cap, uint64_t base_index,

@@ -42,4 +42,23 @@ hipError_t sr_launch_columns(const StoreView& st, uint32_t n_cu, const hc_sr_lay
                              uint32_t safe_region, uint8_t* cons_seq, uint8_t* cons_qual, uint32_t* late, SrHostColumn* host_cols,
                              uint64_t host_cap, unsigned long long* host_count, hipStream_t s);
 
+// hc_sr_edge_kernels.hip: the edge merge (hc_sr_edge_merge, hc_graph_merge_pairs).  A pair owns two layout slots and six member slots
+// until the counts are summed; `who` says which of the pair's sorted vertices (0 / 1) a member slot belongs to.
+struct SrEdgeSlots {
+    uint32_t* status;         // [n_pairs] HC_SR_EDGE_*
+    uint64_t* lay_cnt;        // [n_pairs + 1] layouts of the pair, the last entry 0
+    uint64_t* mem_cnt;        // [n_pairs + 1] members of the pair
+    hc_sr_layout* layouts;    // [2 n_pairs] first_member: unset
+    hc_sr_member* members;    // [6 n_pairs] members of slot k at 3 k
+    uint8_t* who;             // [6 n_pairs]
+};
+hipError_t sr_edge_launch_targets(const hc_edge_rec* edges, uint64_t n_edges, uint32_t* targets, hipStream_t s);
+hipError_t sr_edge_launch_layouts(const StoreView& st, const hc_edge_rec* edges, const unsigned long long* out_off, uint64_t n_vertices,
+                                  const uint32_t* pairs, uint64_t n_pairs, const uint32_t* vertex_read, const uint8_t* vertex_fwd, SrEdgeSlots slots,
+                                  hipStream_t s);
+hipError_t sr_edge_launch_compact(SrEdgeSlots slots, uint64_t n_pairs, const uint64_t* first_layout, const uint64_t* mem_off, hc_sr_layout* layouts,
+                                  hc_sr_member* members, hipStream_t s);
+hipError_t sr_edge_launch_subreads(SrEdgeSlots slots, uint64_t n_pairs, const uint64_t* first_layout, const SrLayoutInfo* info,
+                                   hc_sr_subread_info* subreads, hipStream_t s);
+
 }  // namespace hc

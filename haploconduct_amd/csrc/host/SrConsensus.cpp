@@ -1,6 +1,8 @@
 // SrConsensus.cpp — host mirror of the super-read consensus (include/hcsr.h): SRBuilder::consensus / consensus_pos
 // (reference src/SRBuilder.cpp:289-535) for a batch of layouts on plain base / quality arrays, and the layout of an edge merge
-// between single-end reads (sort_vertices type 's', :33-285).  Own implementation; it walks a layout column by column as the
+// between single-end reads (sort_vertices type 's', :33-285), and the mirrors of the edge merge on a graph: getEdgesForMerging
+// (src/GraphAlgos.cpp:112-148), sort_vertices for a clique of two of every read type and calcSubreadInfo (:536-595), walked with a list
+// as the reference walks them (the device: hc_sr_edge_kernels.hip).  Own implementation; it walks a layout column by column as the
 // reference does, so that the device's closed forms (hc_sr_kernels.hip) have something independent to be compared with.
 #include "SrConsensus.h"
 
@@ -255,6 +257,275 @@ int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const ui
         layouts[i].n_members = 2;
         layouts[i].total_len = (int32_t)total_len;
     }
+    return HC_OK;
+}
+
+int hc_host_graph_merge_pairs(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, uint32_t* pairs, uint64_t cap,
+                              uint64_t* n_pairs) {
+    if (!out_off || !n_pairs || (n_vertices && out_off[n_vertices] && !edges))
+        return hc::set_last_error(HC_ERR_ARG, "hc_host_graph_merge_pairs: null argument");
+    if (n_vertices >= (1ull << 32)) return hc::set_last_error(HC_ERR_ARG, "hc_host_graph_merge_pairs: more than 2^32 - 1 vertices");
+    // getEdgesForMerging (src/GraphAlgos.cpp:112-148): bitvec, the lists in vertex order, the first unmarked outneighbor
+    std::vector<uint8_t> bitvec(n_vertices, 0);
+    std::vector<uint32_t> node_vec;
+    for (uint64_t node = 0; node < n_vertices; node++) {
+        if (bitvec[node]) continue;
+        for (uint64_t k = out_off[node]; k < out_off[node + 1]; k++) {
+            const uint64_t outneighbor = edges[k].v2;
+            if (outneighbor >= n_vertices)
+                return hc::set_last_error(HC_ERR_BAD_OVERLAP, "hc_host_graph_merge_pairs: record " + std::to_string(k) + " leaves the graph");
+            if (!bitvec[outneighbor]) {
+                node_vec.push_back((uint32_t)node);
+                node_vec.push_back((uint32_t)outneighbor);
+                bitvec[node] = 1;
+                bitvec[outneighbor] = 1;
+                break;
+            }
+        }
+    }
+    *n_pairs = node_vec.size() / 2;
+    if (*n_pairs > cap || (*n_pairs && !pairs))
+        return hc::set_last_error(HC_ERR_ARG, "hc_host_graph_merge_pairs: room for " + std::to_string(cap) + " pairs, " + std::to_string(*n_pairs) +
+                                                  " needed (*n_pairs)");
+    if (*n_pairs) memcpy(pairs, node_vec.data(), node_vec.size() * sizeof(uint32_t));
+    return HC_OK;
+}
+
+namespace {
+
+struct EdgeGraph {
+    const hc_edge_rec* edges;
+    const uint64_t* out_off;
+    uint64_t V;
+    const uint64_t* seq_off;
+    const uint32_t* first;
+    uint32_t n_reads;
+    const uint32_t* vertex_read;
+    const uint8_t* vertex_fwd;
+    bool paired(uint32_t r) const { return first[r + 1] - first[r] == 2; }
+    int64_t len(uint32_t r, uint32_t seq) const {  // Read::get_seq(seq).length()
+        const uint32_t s = first[r] + (seq == 2 ? 1u : 0u);
+        return (int64_t)(seq_off[s + 1] - seq_off[s]);
+    }
+    // OverlapGraph::getEdgeInfo, src/OverlapGraph.cpp:263-282
+    const hc_edge_rec* edge_info(uint64_t v, uint64_t w) const {
+        for (uint64_t k = out_off[v]; k < out_off[v + 1]; k++)
+            if (edges[k].v2 == w) return &edges[k];
+        for (uint64_t k = out_off[w]; k < out_off[w + 1]; k++)
+            if (edges[k].v2 == v) return &edges[k];
+        return nullptr;
+    }
+};
+
+struct ListEntry {
+    int64_t pos;
+    uint64_t vertex;
+    hc_sr_member m;
+    int64_t len;
+};
+
+// sort_vertices (src/SRBuilder.cpp:33-285) for the clique {base_node, node}.  Returns HC_SR_EDGE_*; fills list and total_len.
+uint32_t sort_two(const EdgeGraph& G, char type, uint64_t base_node, uint64_t node, std::vector<ListEntry>& list, int64_t& total_len) {
+    list.clear();
+    const uint32_t base_ID = G.vertex_read[base_node];
+    ListEntry base{};
+    base.vertex = base_node;
+    base.m.read = base_ID;
+    if (G.vertex_fwd[base_node]) {  // :47-61
+        base.m.seq = type == 'l' ? 1 : type == 'r' ? 2 : 0;
+        base.m.rev = 0;
+    } else {  // :62-76
+        base.m.seq = type == 'l' ? 2 : type == 'r' ? 1 : 0;
+        base.m.rev = 1;
+    }
+    base.len = G.len(base_ID, base.m.seq);
+    base.pos = 0;
+    list.push_back(base);
+    total_len = base.len;
+    int64_t l_ext = 0, r_ext = 0;
+    const hc_edge_rec* edge = G.edge_info(base_node, node);  // :92
+    if (!edge) return HC_SR_EDGE_NO_EDGE;
+    const bool current_ori = G.vertex_fwd[node] != 0;
+    const uint32_t id1 = edge->read1, id2 = edge->read2;
+    const char ord = (char)edge->ord;
+    uint32_t current_id;
+    if (id1 == base_ID) current_id = id2;  // :104-110
+    else if (id2 == base_ID) current_id = id1;
+    else return HC_SR_EDGE_READ_MISMATCH;
+    if (current_id >= G.n_reads) return HC_SR_EDGE_BAD_VERTEX;
+    char current_type = type;
+    if (type == 's') current_type = G.paired(current_id) ? 'p' : 's';  // :114-122
+    else if (!G.paired(current_id)) return HC_SR_EDGE_READ_MISMATCH;    // get_seq(1 | 2) of a single-end read, src/Read.h:145-149
+    ListEntry cur{}, cur1{};
+    cur.vertex = cur1.vertex = node;
+    cur.m.read = cur1.m.read = current_id;
+    cur.m.rev = cur1.m.rev = current_ori ? 0 : 1;
+    int64_t new_pos = 0, new_pos1 = 0;
+    if (current_type == 's') {  // :132-148
+        const int64_t pos = edge->pos1;
+        cur.m.seq = 0;
+        new_pos = base_ID == id1 ? pos : -pos;
+    } else if (current_type == 'l' || current_type == 'p') {  // :149-170
+        const int64_t pos = edge->pos1;
+        cur.m.seq = current_ori ? 1 : 2;
+        new_pos = base_ID == id1 ? pos : -pos;
+        if (current_type == 'p') {
+            cur1 = cur;
+            new_pos1 = new_pos;
+        }
+    }
+    if (current_type == 'r' || current_type == 'p') {  // :171-188
+        const int64_t pos = edge->pos2;
+        cur.m.seq = current_ori ? 2 : 1;
+        if (current_type == 'p' || (base_ID == id1 && ord == '1') || (base_ID == id2 && ord == '2')) new_pos = pos;
+        else new_pos = -pos;
+    }
+    cur.len = G.len(current_id, cur.m.seq);
+    auto insert = [&](ListEntry e, int64_t p) {  // :198-222
+        size_t it = 0;
+        while (it != list.size() && list[it].pos < p) it++;
+        e.pos = p;
+        list.insert(list.begin() + it, e);
+    };
+    if (current_type == 'p') {
+        cur1.len = G.len(current_id, cur1.m.seq);
+        insert(cur1, new_pos1);
+    }
+    insert(cur, new_pos);
+    int64_t len1, len2;  // :225-240
+    if (current_type == 'p') {
+        if (new_pos < 0) return HC_SR_EDGE_PAIRED_NEG_POS;
+        len1 = -new_pos1;
+        len2 = cur.len + new_pos - base.len;
+        const int64_t seq1_len2 = cur1.len + new_pos1 - base.len;
+        if (seq1_len2 > len2) len2 = seq1_len2;
+    } else {
+        len1 = -new_pos;
+        len2 = cur.len + new_pos - base.len;
+    }
+    if (len1 > l_ext) l_ext = len1;
+    if (len2 > r_ext) r_ext = len2;
+    total_len += l_ext + r_ext;  // :244
+    if (total_len > INT32_MAX) return HC_SR_EDGE_BAD_GEOMETRY;
+    if (!(total_len > list.back().pos)) return HC_SR_EDGE_BAD_GEOMETRY;  // :246
+    const int64_t min = list.front().pos;  // :248-252
+    if (min < 0)
+        for (ListEntry& e : list) e.pos -= min;
+    if (list.front().pos != 0 || list.front().len > total_len) return HC_SR_EDGE_BAD_GEOMETRY;  // :256, :259
+    int64_t c_pos = 0;
+    for (size_t i = 1; i < list.size(); i++) {  // :261-284
+        const int64_t n_pos = list[i].pos;
+        if (n_pos < 0 || c_pos > n_pos || n_pos > INT32_MAX || n_pos + list[i].len > total_len) return HC_SR_EDGE_BAD_GEOMETRY;
+        c_pos = n_pos;
+    }
+    return HC_SR_EDGE_OK;
+}
+
+// calcSubreadInfo (src/SRBuilder.cpp:536-595); `info` is keyed by the pair's two vertices
+void subread_info(int32_t trim_pos1, int32_t trim_pos2, const std::vector<ListEntry>& list1, const std::vector<ListEntry>& list2, uint64_t va,
+                  hc_sr_subread_info* info) {
+    bool present[2] = {false, false};
+    for (const ListEntry& e : list1) {
+        const int which = e.vertex == va ? 0 : 1;
+        hc_sr_subread_info& s = info[which];
+        const int32_t pos = (int32_t)e.pos;
+        if (present[which]) {  // :544-558
+            if (trim_pos1 > pos) {
+                s.startpos2 = trim_pos1 - pos;
+                s.index2 = 0;
+            } else {
+                s.startpos2 = 0;
+                s.index2 = pos - trim_pos1;
+            }
+        } else {  // :559-572
+            if (trim_pos1 > pos) {
+                s.startpos1 = trim_pos1 - pos;
+                s.index1 = 0;
+            } else {
+                s.startpos1 = 0;
+                s.index1 = pos - trim_pos1;
+            }
+            s.index2 = -1;
+            s.startpos2 = -1;
+            present[which] = true;
+        }
+    }
+    if (trim_pos2 >= 0) {  // :575-593
+        for (const ListEntry& e : list2) {
+            hc_sr_subread_info& s = info[e.vertex == va ? 0 : 1];
+            const int32_t pos = (int32_t)e.pos;
+            if (trim_pos2 > pos) {
+                s.startpos2 = trim_pos2 - pos;
+                s.index2 = 0;
+            } else {
+                s.startpos2 = 0;
+                s.index2 = pos - trim_pos2;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, const uint64_t* seq_off,
+                                  const uint32_t* read_first_seq, uint32_t n_reads, const uint32_t* pairs, uint64_t n_pairs,
+                                  const uint32_t* vertex_read, const uint8_t* vertex_fwd, const hc_sr_settings* settings, uint32_t* pair_status,
+                                  uint64_t* first_layout, hc_sr_layout* layouts, hc_sr_member* members, const int32_t* ret,
+                                  hc_sr_subread_info* subreads) {
+    const char* me = "hc_host_sr_edge_merge_layouts: ";
+    if (!out_off || !seq_off || !read_first_seq || !settings || !first_layout || (n_vertices && (!vertex_read || !vertex_fwd)) ||
+        (n_pairs && (!pairs || !pair_status || !layouts || !members)) || (n_vertices && out_off[n_vertices] && !edges) || (ret && n_pairs && !subreads))
+        return hc::set_last_error(HC_ERR_ARG, std::string(me) + "null argument");
+    if (settings->min_clique_size == 0)
+        return hc::set_last_error(HC_ERR_ARG, std::string(me) + "min_clique_size == 0 sends a two-vertex clique through filter_subreads "
+                                                                "(src/SRBuilder.cpp:721), which is not built");
+    const EdgeGraph G{edges, out_off, n_vertices, seq_off, read_first_seq, n_reads, vertex_read, vertex_fwd};
+    uint64_t n_layouts = 0, n_members = 0;
+    std::vector<ListEntry> list1, list2;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        first_layout[i] = n_layouts;
+        const uint64_t v = pairs[2 * i], w = pairs[2 * i + 1];
+        uint32_t st = HC_SR_EDGE_OK;
+        if (v >= n_vertices || w >= n_vertices || v == w || vertex_read[v] >= n_reads || vertex_read[w] >= n_reads) st = HC_SR_EDGE_BAD_VERTEX;
+        const uint64_t va = std::min(v, w), vb = std::max(v, w);  // :658
+        char type = 'p';
+        int64_t len1 = 0, len2 = 0;
+        if (st == HC_SR_EDGE_OK) {
+            uint64_t base_node = va;  // :669-679
+            for (uint64_t x : {va, vb})
+                if (type == 'p' && !G.paired(vertex_read[x])) {
+                    base_node = x;
+                    type = 's';
+                }
+            if (type == 'p') {  // :691-698
+                st = sort_two(G, 'l', va, vb, list1, len1);
+                if (st == HC_SR_EDGE_OK) st = sort_two(G, 'r', va, vb, list2, len2);
+            } else {
+                st = sort_two(G, 's', base_node, base_node == va ? vb : va, list1, len1);
+            }
+        }
+        pair_status[i] = st;
+        if (subreads) subreads[2 * i] = subreads[2 * i + 1] = hc_sr_subread_info{-1, -1, -1, -1};
+        if (st != HC_SR_EDGE_OK) continue;
+        const uint64_t l0 = n_layouts;
+        for (int k = 0; k < (type == 'p' ? 2 : 1); k++) {
+            const std::vector<ListEntry>& L = k ? list2 : list1;
+            layouts[n_layouts].first_member = n_members;
+            layouts[n_layouts].n_members = (uint32_t)L.size();
+            layouts[n_layouts].total_len = (int32_t)(k ? len2 : len1);
+            for (const ListEntry& e : L) {
+                hc_sr_member m = e.m;
+                m.pos = (int32_t)e.pos;
+                members[n_members++] = m;
+            }
+            n_layouts++;
+        }
+        if (ret && subreads) {
+            if (type != 'p') list2.clear();
+            subread_info(ret[l0], type == 'p' ? ret[l0 + 1] : -1, list1, list2, va, &subreads[2 * i]);
+        }
+    }
+    first_layout[n_pairs] = n_layouts;
     return HC_OK;
 }
 

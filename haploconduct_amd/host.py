@@ -474,3 +474,21 @@ def sr_edge_layouts(edges, reads):
     from . import consensus as SR
 
     return SR.edge_layouts(edges, reads)
+
+
+def graph_merge_pairs(edges, out_off):
+    """hc_host_graph_merge_pairs: OverlapGraph::getEdgesForMerging (src/GraphAlgos.cpp:112-148) on a caller's records; (n, 2) vertex ids."""
+    from . import consensus as SR
+
+    e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    oo = np.ascontiguousarray(out_off, dtype=np.uint64)
+    return SR.merge_pairs(lambda p, cap, n: N.lib.hc_host_graph_merge_pairs(e.ctypes.data if e.size else None, oo.ctypes.data, oo.size - 1, p, cap, n),
+                          oo.size - 1)
+
+
+def sr_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fwd, ret=None, min_clique_size=2):
+    """hc_host_sr_edge_merge_layouts: the host mirror of EdgeScorer.sr_edge_merge's layouts and subread infos (sort_vertices and
+    calcSubreadInfo, src/SRBuilder.cpp:33-285, 536-595).  ret: the layouts' consensus return values, for the subread infos."""
+    from . import consensus as SR
+
+    return SR.host_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fwd, SR.make_settings(min_clique_size=min_clique_size), ret)

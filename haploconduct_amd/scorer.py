@@ -67,6 +67,26 @@ class EdgeScorer:
         st = SR.make_self_settings(min_score, min_qual, min_overlap, n_threads)
         return SR.run_self(lambda *a: N.lib.hc_sr_merge_self_overlaps(self._ctx, *a), seq, qual, pairs, st, count_first)
 
+    # -- edge merges on the device graph (include/hcsr.h) -----------------------
+    def graph_merge_pairs(self, with_stats=False):
+        """hc_graph_merge_pairs: OverlapGraph::getEdgesForMerging (src/GraphAlgos.cpp:112-148) on the device graph; (n, 2) vertex ids in
+        the order taken (with_stats: and the hc_merge_pairs_stats as a dict)."""
+        from . import consensus as SR
+
+        st = N.hc_merge_pairs_stats()
+        V, _ = self._graph_size()
+        pairs = SR.merge_pairs(lambda p, cap, n: N.lib.hc_graph_merge_pairs(self._ctx, p, cap, n, C.byref(st)), V)
+        return (pairs, {k: getattr(st, k) for k, _ in st._fields_}) if with_stats else pairs
+
+    def sr_edge_merge(self, pairs, vertex_read, vertex_fwd, min_qual=0.99, min_clique_size=2, error_correction=False, subreads_needed=False,
+                      n_threads=16, cap=None):
+        """hc_sr_edge_merge: SRBuilder::mergeAlongEdges' layouts (sort_vertices, src/SRBuilder.cpp:33-285), consensus and calcSubreadInfo
+        (:536-595) for pairs of vertices of the device graph.  Returns a consensus.SrEdgeLayouts with .result (a consensus.SrResult)."""
+        from . import consensus as SR
+
+        st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
+        return SR.edge_merge(self._ctx, pairs, vertex_read, vertex_fwd, st, cap)
+
     # -- the next iteration's store from super-reads (include/hcsr.h) -----------
     def sr_keep_device(self, on=True):
         """hc_sr_keep_device: set_reads keeps its raw arrays and sr_consensus its output on the device (off by default)."""

@@ -216,7 +216,8 @@ int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint
 int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads);
 int hc_host_graph_free(hc_host_graph* g);
 
-/* Super-read consensus on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts): include/hcsr.h,
+/* Super-read consensus and edge merges on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts,
+ * hc_host_graph_merge_pairs, hc_host_sr_edge_merge_layouts): include/hcsr.h,
  * which includes this header's records. */
 
 #ifdef __cplusplus

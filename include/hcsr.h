@@ -6,6 +6,7 @@
  *
  * A LAYOUT is what sort_vertices (src/SRBuilder.cpp:33-285) hands to consensus: total_len and the members in list order
  * (positions ascending, the first is 0).  A MEMBER names a stored sequence instead of carrying strings.
+ * Layouts of cliques of more than two vertices are left to the caller; those of edge merges: hc_sr_edge_merge.
  */
 #ifndef HCSR_H_
 #define HCSR_H_
@@ -102,9 +103,99 @@ int hc_host_sr_table(double min_qual, uint32_t n_q, uint8_t* table);
  * extensions (:236-243).  rev = the vertex is the reverse one (OverlapGraph::getOrientation false).
  * seq_len_by_read[r] = length of single-end read r, paired[r] != 0 marks a paired read (may be NULL: none is).
  * Writes layouts[i] (first_member = 2 i) and members[2 i], members[2 i + 1].  An edge that names a paired read, a read
- * index >= n_reads or read1 == read2 is refused: HC_ERR_BAD_OVERLAP, *first_bad = its index (paired members are not built). */
+ * index >= n_reads or read1 == read2 is refused: HC_ERR_BAD_OVERLAP, *first_bad = its index (paired members are not built
+ * by THIS call: hc_sr_edge_merge / hc_host_sr_edge_merge_layouts below lay out every combination of read types). */
 int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const uint32_t* seq_len_by_read, const uint8_t* paired,
                             uint32_t n_reads, hc_sr_layout* layouts, hc_sr_member* members, uint64_t* first_bad);
+
+/* ---- edge merges on the device graph: SRBuilder::mergeAlongEdges (src/SRBuilder.cpp:1238-1253) --------------------------
+ *
+ * mergeAlongEdges takes the cleaned graph, picks the edges to merge (OverlapGraph::getEdgesForMerging,
+ * src/GraphAlgos.cpp:112-148) and hands every picked pair of vertices, as a clique of two, to constructSuperread
+ * (src/SRBuilder.cpp:654-698), which lays it out with sort_vertices (:33-285) and calls consensus.  The calls of this section
+ * do that on the graph the context holds (hc_graph_resolve / hc_graph_load and the cleaning calls), for every combination of
+ * single-end and paired reads.
+ * Left to the caller: cliques of more than two vertices and filter_subreads (:597-651), clique enumeration, the
+ * original-index maps (:750-843) and subreads.txt, the `visited` marks and the trivial-entry list of :1260-1373. */
+
+typedef struct hc_merge_pairs_stats {
+    double ms_kernel; /* device call only: the target-column kernel, by events on the context's stream */
+    double ms_copy;   /* device call only: the copy of the targets and out_off to the host             */
+    double ms_walk;   /* the host's walk                                                                */
+} hc_merge_pairs_stats; /* 24 bytes */
+
+/* OverlapGraph::getEdgesForMerging (src/GraphAlgos.cpp:112-148) on the context's graph: the sequential greedy matching over the
+ * records in (source vertex, list position) order — a vertex that is not marked yet takes its first record whose target is
+ * not marked either, and both are marked.  pairs[2 i], pairs[2 i + 1] = (v, w) of the i-th pair taken, in the order taken
+ * (the order of process_cliques' input).  cap = pairs the array has room for (n_vertices / 2 always suffices); *n_pairs is
+ * always filled; with cap too small (or pairs NULL) nothing is written and HC_ERR_ARG is returned (count, then fetch).
+ * The device writes the target column of its out-records as packed 32-bit ids in list order; that array and out_off come
+ * back (12 bytes per edge less than the records) and the host walks them: the walk's dependency chain is as long as a path
+ * whose ids ascend along it, which is what a cleaned graph looks like.  A graph with tied lists (hc_graph_counts) is
+ * refused as by the cleaning calls: HC_ERR_STATE.  stats may be NULL. */
+int hc_graph_merge_pairs(hc_ctx* ctx, uint32_t* pairs, uint64_t cap, uint64_t* n_pairs, hc_merge_pairs_stats* stats);
+
+/* The same walk on a caller's records (hc_graph_fetch's edges / out_off; only v2 is read).  A target >= n_vertices:
+ * HC_ERR_BAD_OVERLAP. */
+int hc_host_graph_merge_pairs(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, uint32_t* pairs, uint64_t cap,
+                              uint64_t* n_pairs);
+
+/* Per-pair status of an edge merge: which of the reference's exits the pair took.  Anything but OK: the pair owns no layout. */
+enum {
+    HC_SR_EDGE_OK = 0,
+    HC_SR_EDGE_NO_EDGE = 1,        /* neither base -> node nor node -> base: "Edge not found. Exiting.", src/OverlapGraph.cpp:280   */
+    HC_SR_EDGE_BAD_VERTEX = 2,     /* refused: a vertex id >= n_vertices, v == w, or a read index (vertex_read's or the record's)
+                                      beyond the store                                                                             */
+    HC_SR_EDGE_READ_MISMATCH = 3,  /* neither read of the record is the base's read (assert, src/SRBuilder.cpp:108); or a paired
+                                      layout whose record names a single-end read for the other vertex (assert, src/Read.h:145-149) */
+    HC_SR_EDGE_PAIRED_NEG_POS = 4, /* a paired member's mate-2 position is negative (assert, :227)                                  */
+    HC_SR_EDGE_BAD_GEOMETRY = 5    /* the asserts of :246, :259, :264, :281, or a position / total_len beyond int                   */
+};
+
+/* SubreadInfo (src/Types.h:77-82) in the order calcSubreadInfo's caller reads it. */
+typedef struct hc_sr_subread_info {
+    int32_t index1, startpos1, index2, startpos2;
+} hc_sr_subread_info; /* 16 bytes */
+
+/* constructSuperread (src/SRBuilder.cpp:654-698: order, type, base), sort_vertices (:33-285), consensus (:413-535) and
+ * calcSubreadInfo (:536-595) for every pair (v, w) = (pairs[2 i], pairs[2 i + 1]) of vertices of the context's graph.
+ * Needs hc_set_reads and a graph without tied lists (HC_ERR_STATE otherwise); min_clique_size == 0 is refused with
+ * HC_ERR_ARG: the reference then sends a two-vertex clique through filter_subreads (:721), which this call does not build.
+ * vertex_read[x] = store index of OverlapGraph::vertex_to_read[x]; vertex_fwd[x] = OverlapGraph::getOrientation(x)
+ * (src/OverlapGraph.cpp:83-86); n_vertices must be the graph's.
+ * The two vertices are sorted (:658).  Both reads paired: type 'p', TWO layouts ('l', then 'r'), base = the smaller vertex.
+ * Otherwise type 's', ONE layout, base = the first single-end read in sorted order (:672-679).  The record is
+ * getEdgeInfo(base, node) (src/OverlapGraph.cpp:263-282): the FIRST base -> node of adj_out[base] in list order, else the first
+ * node -> base of adj_out[node]; the record's read ids, not its vertices, say whether the base is read 1 (:101-110).
+ * Members (:47-76, :114-188): the base takes seq 1 forward / seq 2 reverse-complemented ('l'), seq 2 / seq 1 ('r'), seq 0
+ * ('s'); the other vertex likewise by its own orientation, both mates (mate 1, then mate 2) for a paired read in an 's'
+ * layout.  new_pos = +-pos1 by whether the base is read 1 ('s', 'l', mate 1); pos2 for mate 2, and for 'r' pos2 when (base is
+ * read 1 and ord == '1') or (base is read 2 and ord == '2'), else -pos2.  Every insertion goes in front of the first entry
+ * whose position is not smaller (:198-222): the order is (position ascending, insertion number descending).  total_len:
+ * :225-244; the shift by -min: :247-252.
+ * Outputs.  pair_status[i] = HC_SR_EDGE_*; the layouts of pair i are [first_layout[i], first_layout[i + 1]) (n_pairs + 1
+ * entries; n_layouts = first_layout[n_pairs]); layouts (room for 2 n_pairs) and members (room for 6 n_pairs) are packed in pair
+ * order, as hc_sr_consensus takes them.  ret / status / out_off (room for 2 n_pairs, 2 n_pairs and 2 n_pairs + 1) / cons_seq /
+ * cons_qual / cap / *n_bytes / stats: hc_sr_consensus' outputs for those layouts, by the same code from the device arrays on
+ * (with hc_sr_keep_device on, the bytes stay for hc_sr_set_next_reads exactly as after hc_sr_consensus); cap too small:
+ * HC_ERR_ARG with everything but the bytes filled.  subreads[2 i], subreads[2 i + 1] = calcSubreadInfo's entries of the
+ * smaller and the larger vertex of pair i, with trim_pos1 = ret of the pair's first layout and trim_pos2 = ret of its 'r'
+ * layout or -1; a dummy is -1 (:569-570); a paired member of an 's' layout is listed twice, its first entry in list order
+ * gives index1 / startpos1 and its second index2 / startpos2; a pair without layouts has all four -1. */
+int hc_sr_edge_merge(hc_ctx* ctx, const uint32_t* pairs, uint64_t n_pairs, const uint32_t* vertex_read, const uint8_t* vertex_fwd,
+                     uint64_t n_vertices, const hc_sr_settings* settings, uint32_t* pair_status, uint64_t* first_layout,
+                     hc_sr_layout* layouts, hc_sr_member* members, hc_sr_subread_info* subreads, int32_t* ret, uint32_t* status,
+                     uint64_t* out_off, uint8_t* cons_seq, uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_stats* stats);
+
+/* The layouts and subread infos of hc_sr_edge_merge on the host (no device, no context): a graph as hc_graph_fetch returns it
+ * (edges, out_off) and the read table as hc_set_reads takes it (seq_off, read_first_seq); it walks the lists and inserts
+ * into a position list as the reference does.  ret (per layout, what a consensus call returned for them) is an INPUT of the
+ * subread infos; with ret NULL subreads is not written — call once for the layouts, run the consensus, call again. */
+int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, const uint64_t* seq_off,
+                                  const uint32_t* read_first_seq, uint32_t n_reads, const uint32_t* pairs, uint64_t n_pairs,
+                                  const uint32_t* vertex_read, const uint8_t* vertex_fwd, const hc_sr_settings* settings,
+                                  uint32_t* pair_status, uint64_t* first_layout, hc_sr_layout* layouts, hc_sr_member* members,
+                                  const int32_t* ret, hc_sr_subread_info* subreads);
 
 /* ---- self-overlapping paired super-reads: SRBuilder::merge_self_overlap (src/SRBuilder.cpp:872-955) --------------------
  *
@@ -192,9 +283,9 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
  * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
  * context's read store by the result.
- * Left to the caller: the subread / original-index maps and subreads.txt; ignore_inclusions and the tip handling of
- * mergeAlongEdges (:1298-1311: the caller omits those vertices); the FASTQ text itself; a device-input form of
- * hc_sr_merge_self_overlaps. */
+ * Left to the caller: the original-index maps and subreads.txt (the subread infos of an edge merge: hc_sr_edge_merge);
+ * ignore_inclusions and the tip handling of mergeAlongEdges (:1298-1311: the caller omits those vertices); the FASTQ text
+ * itself; a device-input form of hc_sr_merge_self_overlaps. */
 
 /* Off by default: every other call then behaves and allocates as it does without this section.  While it is on, hc_set_reads
  * keeps its device copies of the raw base, quality and offset arrays (trivial super-reads are copied from them: the encoded
