@@ -136,6 +136,10 @@ _sig = {
     "hc_host_sr_next_reads": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64] + _sr_next_tail + [_vp, _vp, C.c_uint64, _u64p, _vp, _vp]),
     "hc_sr_merge_self_overlaps": (C.c_int, [_vp] + _sr_self_tail),
     "hc_host_sr_merge_self_overlaps": (C.c_int, [C.POINTER(hc_settings)] + _sr_self_tail),
+    "hc_sr_merge_self_overlaps_kept": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(hc_sr_self_settings), _vp, _vp, _vp, _vp, _u64p,
+                                                 C.POINTER(hc_sr_self_stats)]),
+    "hc_sr_kept_load": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "hc_sr_kept_fetch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, _vp, _u64p]),
     "hc_sr_consensus": (C.c_int, [_vp] + _sr_tail),
     "hc_host_sr_consensus": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32] + _sr_tail),
     "hc_host_sr_column": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_double, _vp]),

@@ -1,7 +1,8 @@
 """Super-read consensus (include/hcsr.h): SRBuilder::consensus / consensus_pos (reference src/SRBuilder.cpp:289-535)
 for a batch of layouts.  Record views, the result type and the plumbing shared by EdgeScorer.sr_consensus (device)
 and host.sr_consensus (the host mirror); the same for the merge of self-overlapping paired super-reads
-(SRBuilder::merge_self_overlap, src/SRBuilder.cpp:872-955): EdgeScorer.sr_merge_self_overlaps / host.sr_merge_self_overlaps."""
+(SRBuilder::merge_self_overlap, src/SRBuilder.cpp:872-955): EdgeScorer.sr_merge_self_overlaps / host.sr_merge_self_overlaps, and
+EdgeScorer.sr_merge_self_overlaps_kept, which reads its mates from the consensus bytes kept on the device and appends to them."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -265,3 +266,66 @@ def run_self(call, seq, qual, pairs, settings, count_first=True):
     nb = int(n_out.value)
     return SrSelfResult(pos, score, status, out_off, mseq[:nb], mqual[:nb], int(stats.n_merged), int(stats.n_host_pairs), int(stats.n_offsets),
                         float(stats.ms_device), float(stats.ms_host))
+
+
+# ---- the same from the kept consensus bytes (hc_sr_merge_self_overlaps_kept, hc_sr_kept_load, hc_sr_kept_fetch) -------------
+def kept_load(ctx, seq, qual):
+    """hc_sr_kept_load: the caller's packed bytes become the kept consensus bytes of the context."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    if seq.size != qual.size:
+        raise ValueError("seq and qual differ in length")
+    N.check(N.lib.hc_sr_kept_load(ctx, _ptr(seq), _ptr(qual), seq.size), "sr_kept_load")
+
+
+def kept_size(ctx):
+    n = C.c_uint64(0)
+    N.check(N.lib.hc_sr_kept_fetch(ctx, 0, 0, None, None, C.byref(n)), "sr_kept_fetch")
+    return int(n.value)
+
+
+def kept_fetch(ctx, off=0, n=None):
+    """hc_sr_kept_fetch: (seq, qual) = bytes [off, off + n) of the kept consensus bytes; n = None: from off to the end."""
+    if n is None:
+        n = kept_size(ctx) - int(off)
+    seq, qual = np.zeros(max(int(n), 0), np.uint8), np.zeros(max(int(n), 0), np.uint8)
+    kept = C.c_uint64(0)
+    N.check(N.lib.hc_sr_kept_fetch(ctx, int(off), int(n), _ptr(seq), _ptr(qual), C.byref(kept)), "sr_kept_fetch")
+    return seq, qual
+
+
+@dataclass
+class SrSelfKeptResult(SrSelfResult):
+    """out_off holds ABSOLUTE offsets into the kept bytes (out_off[0] = the kept size before the call); merged_seq / merged_qual are
+    empty: the merged reads stay on the device.  merged(i) and relative() read them back with hc_sr_kept_fetch."""
+    ctx: object = None
+
+    def merged(self, i):
+        a, b = int(self.out_off[i]), int(self.out_off[i + 1])
+        s, q = kept_fetch(self.ctx, a, b - a)
+        return s.tobytes(), q.tobytes()
+
+    def relative(self):
+        """The result in the host-input call's form: offsets from 0 and the appended bytes on the host, in one fetch."""
+        base = int(self.out_off[0])
+        s, q = kept_fetch(self.ctx, base, int(self.out_off[-1]) - base)
+        return SrSelfResult(self.overlap_pos, self.score, self.status, self.out_off - np.uint64(base), s, q, self.n_merged, self.n_host_pairs,
+                            self.n_offsets, self.ms_device, self.ms_host)
+
+
+def run_self_kept(ctx, pairs, settings):
+    """hc_sr_merge_self_overlaps_kept on the context's kept consensus bytes.  Returns an SrSelfKeptResult."""
+    pairs = np.ascontiguousarray(pairs, dtype=SR_PAIR_DTYPE)
+    n = pairs.size
+    pos = np.zeros(n, np.int32)
+    score = np.zeros(n, np.float64)
+    status = np.zeros(n, np.uint32)
+    out_off = np.zeros(n + 1, np.uint64)
+    n_out = C.c_uint64(0)
+    stats = N.hc_sr_self_stats()
+    N.check(N.lib.hc_sr_merge_self_overlaps_kept(ctx, _ptr(pairs), n, C.byref(settings), _ptr(pos), _ptr(score), _ptr(status), out_off.ctypes.data,
+                                                 C.byref(n_out), C.byref(stats)), "sr_merge_self_overlaps_kept")
+    assert int(out_off[-1] - out_off[0]) == int(n_out.value)
+    empty = np.zeros(0, np.uint8)
+    return SrSelfKeptResult(pos, score, status, out_off, empty, empty, int(stats.n_merged), int(stats.n_host_pairs), int(stats.n_offsets),
+                            float(stats.ms_device), float(stats.ms_host), ctx)

@@ -4,8 +4,9 @@
 // decide by comparisons come back as four sums that host threads finish with the reference's expressions (host/SrConsensus.h).
 // hc_sr_consensus is in parts (hc_ctx.h: sr_consensus_begin / _room / _run) so that hc_sr_edge_merge (hc_api_sr_edge.cpp), whose layouts are
 // on the device already, runs the same code from there on.
-// hc_sr_merge_self_overlaps: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end of this file.  Both calls build
-// their consensus tables with sr_tables and run their host loops with in_blocks (host/InBlocks.h).
+// hc_sr_merge_self_overlaps and hc_sr_merge_self_overlaps_kept: SRBuilder::merge_self_overlap (:872-955) for a batch of pairs, at the end
+// of this file, with hc_sr_kept_load / hc_sr_kept_fetch.  All calls build their consensus tables with sr_tables and run their host loops
+// with in_blocks (host/InBlocks.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -246,28 +247,216 @@ int hc::sr_consensus_run(hc_ctx* c, const char* me, uint64_t n_layouts, uint64_t
 }
 
 // --------------------------------------------------------------------------------------------------------------------------------------
-// hc_sr_merge_self_overlaps: the host checks the pairs and builds what depends on libm (the log p table of the batch's quality values, by
-// the scoring path's own builder; 1.0 / n; the consensus table), the scan kernel finds every pair's offset, the host decides the offsets
-// inside the guard band (host/SrSelfOverlap.h), the merge kernel writes the merged reads at the offsets of an exclusive sum.
+// hc_sr_merge_self_overlaps / hc_sr_merge_self_overlaps_kept: the pairs are checked and the batch's quality values collected — by host
+// threads on the caller's arrays, or by sr_self_check_kernel on the bytes the context keeps —, the host builds what depends on libm (the
+// log p table of the batch's quality values, by the scoring path's own builder; 1.0 / n; the consensus table), the scan kernel finds every
+// pair's offset, the host decides the offsets inside the guard band (host/SrSelfOverlap.h), the merge kernel writes the merged reads at the
+// offsets of an exclusive sum.  From the check on the two calls run the same functions (self_scan, self_host_pairs, self_merge): what
+// differs is where the mates lie and where the merged reads go.
+namespace {
+
+struct SelfBatch {  // what the check leaves of a batch, over its valid pairs
+    std::vector<uint32_t> skip;  // the pairs' statuses before the scan: 0 = scanned
+    uint8_t qs_seen[96] = {0};   // the quality values byte - 33 that occur
+    uint32_t max_len = 0, max_first = 0;
+    uint64_t n_offsets = 0, n_valid = 0;
+};
+
+struct SelfWork {  // what the scan and the host's share leave for the merge
+    std::vector<uint64_t> len;  // n_pairs + 1: the merged reads' lengths, the last 0
+    std::vector<int32_t> mpos;  // the offset of a pair the merge kernel writes, -1: not the device's columns
+    // pairs the host finishes: (pair, the offset its scan goes on from)
+    std::vector<std::pair<uint64_t, uint32_t>> host_pairs;
+    struct Out {
+        std::vector<uint8_t> seq, qual;
+    };
+    std::vector<Out> host_out;  // their merged reads
+    float ms_scan = 0, ms_merge = 0;
+    double ms_host = 0;
+};
+
+void self_begin(const SelfBatch& B, uint64_t n_pairs, int32_t* overlap_pos, double* score, uint32_t* status, SelfWork& W) {
+    W.len.assign(n_pairs + 1, 0);
+    W.mpos.assign(n_pairs, -1);
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        overlap_pos[i] = -1;
+        score[i] = 0;
+        status[i] = B.skip[i];
+    }
+}
+
+// The tables, the scan of the pairs on the device (S.pairs, S.skip) over d_seq / d_qual, and the scan's verdicts: a pair the device
+// decided gets its outputs, the others join W.host_pairs.  Runs only for a batch with an offset to try.
+int self_scan(hc_ctx* c, const std::string& me, const SelfBatch& B, const uint8_t* d_seq, const uint8_t* d_qual, const hc_sr_pair* pairs,
+              uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score, uint32_t* status, SelfWork& W) {
+    hc_ctx::SrSelf& S = c->sr_self;
+    hipStream_t s = c->stream;
+    int rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    // tables: log p by the scoring path's builder for the batch's values (row = rank of the value), 1.0 / n, the consensus table
+    std::vector<int> phred;
+    uint8_t qmap[256], q_of[hc::sr::kQDim];
+    memset(qmap, 0, sizeof qmap);
+    memset(q_of, 255, sizeof q_of);
+    for (uint32_t q = 0; q < hc::srself::kQ; q++) {
+        if (!B.qs_seen[q]) continue;
+        qmap[q + 33] = (uint8_t)phred.size();
+        phred.push_back((int)q);
+        q_of[q] = (uint8_t)q;
+    }
+    std::vector<double> lut;
+    if (!hc::build_log_table_u16(phred, c->settings.mismatch, lut)) return fail(HC_ERR_STATE, me + "the log table is not symmetric");
+    std::vector<double> inv_n((size_t)B.max_len + 1, 0.0);
+    for (uint32_t k = 1; k <= B.max_len; k++) inv_n[k] = 1.0 / (double)k;  // :137
+    if ((rc = sr_tables(c, S.tables, q_of, settings->min_qual))) return rc;
+    hc::SrSelfParams prm;
+    int log2_width = -49;
+    if (const char* e = getenv("HC_SR_SELF_BAND_LOG2")) {  // test knob: a wider guard band, so that the host-decided path runs
+        const int v = atoi(e);
+        if (v >= -60 && v <= -2) log2_width = v;
+    }
+    prm.band = hc::threshold_band(settings->min_score, log2_width);
+    prm.always = settings->min_score < 0 ? 1u : 0u;
+    prm.min_overlap = settings->min_overlap;
+    prm.min_read_len = c->settings.min_read_len;
+    prm.K = (uint32_t)phred.size();
+    prm.lut_doubles = (uint32_t)lut.size();
+    prm.inv_len = (uint32_t)inv_n.size();
+    if ((rc = S.qmap.ensure(256)) || (rc = S.lut.ensure(lut.size() * sizeof(double))) || (rc = S.inv_n.ensure(inv_n.size() * sizeof(double))) ||
+        (rc = S.res.ensure(n_pairs * sizeof(hc::SrSelfScan))))
+        return rc;
+    W.ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HC_HIP(hipMemcpyAsync(S.qmap.p, qmap, 256, hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemcpyAsync(S.lut.p, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemcpyAsync(S.inv_n.p, inv_n.data(), inv_n.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    const uint32_t lanes = 64u * std::max(1u, std::min(hc::kSelfMaxChunk / 64u, (B.max_first + 63u) / 64u));
+    std::vector<hc::SrSelfScan> res(n_pairs);
+    HC_HIP(hipEventRecord(c->ev0, s));
+    HC_HIP(hc::sr_self_launch_scan(c->n_cu, lanes, d_seq, d_qual, S.pairs.as<hc_sr_pair>(), S.skip.as<uint32_t>(), n_pairs, S.qmap.as<uint8_t>(),
+                                   S.lut.as<double>(), S.inv_n.as<double>(), prm, S.res.as<hc::SrSelfScan>(), s));
+    HC_HIP(hipEventRecord(c->ev1, s));
+    HC_HIP(hipMemcpyAsync(res.data(), S.res.p, n_pairs * sizeof(hc::SrSelfScan), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipStreamSynchronize(s));
+    HC_HIP(hipEventElapsedTime(&W.ms_scan, c->ev0, c->ev1));
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (B.skip[i] || res[i].p < 0) continue;
+        if (res[i].kind == hc::kSelfHit && !S.tables.has_nan) {
+            overlap_pos[i] = res[i].p;
+            score[i] = exp(res[i].x);  // :138
+            status[i] = HC_SR_SELF_MERGED;
+            W.len[i] = (uint64_t)pairs[i].len2 + (uint32_t)res[i].p;  // :890
+            W.mpos[i] = res[i].p;
+        } else {
+            W.host_pairs.emplace_back(i, (uint32_t)res[i].p);
+        }
+    }
+    return HC_OK;
+}
+
+// The host's share: the scan of W.host_pairs[k] goes on from the offset in the band with the host's libm, as the mirror walks it, on
+// the mates M[k] in host memory.
+void self_host_pairs(hc_ctx* c, const hc_sr_self_settings* settings, const std::vector<hc::srself::Mates>& M, int32_t* overlap_pos, double* score,
+                     uint32_t* status, SelfWork& W) {
+    W.host_out.resize(W.host_pairs.size());
+    if (W.host_pairs.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hc::srself::Tables T(c->settings.mismatch, c->settings.min_read_len);
+    hc::in_blocks(W.host_pairs.size(), 1, std::max(1u, settings->n_threads), [&](uint64_t a, uint64_t b) {
+        for (uint64_t k = a; k < b; k++) {
+            const uint64_t i = W.host_pairs[k].first;
+            overlap_pos[i] = hc::srself::scan_pair(T, M[k], W.host_pairs[k].second, *settings, &score[i], W.host_out[k].seq, W.host_out[k].qual);
+            if (overlap_pos[i] < 0) continue;
+            status[i] = HC_SR_SELF_MERGED;
+            W.len[i] = W.host_out[k].seq.size();
+        }
+    });
+    W.ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// out_off[i] = base + the bytes of the pairs before i; returns the bytes of all
+uint64_t self_offsets(const SelfWork& W, uint64_t n_pairs, uint64_t base, const uint32_t* status, uint64_t* out_off, hc_sr_self_stats* stats,
+                      uint64_t n_offsets) {
+    uint64_t total = 0, n_merged = 0;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        out_off[i] = base + total;
+        total += W.len[i];
+        n_merged += status[i] == HC_SR_SELF_MERGED;
+    }
+    out_off[n_pairs] = base + total;
+    if (stats) {
+        stats->n_merged = n_merged;
+        stats->n_host_pairs = W.host_pairs.size();
+        stats->n_offsets = n_offsets;
+        stats->ms_device = W.ms_scan;
+        stats->ms_host = W.ms_host;
+    }
+    return total;
+}
+
+// The merged reads of the pairs the device decided: offsets by an exclusive sum on the device, one lane per column, into d_out_seq /
+// d_out_qual (room for `total` bytes).  Enqueues and records the events; the caller waits and reads W.ms_merge with self_merge_ms.
+int self_merge(hc_ctx* c, const uint8_t* d_seq, const uint8_t* d_qual, uint64_t n_pairs, const SelfWork& W, uint64_t total, uint8_t* d_out_seq,
+               uint8_t* d_out_qual) {
+    hc_ctx::SrSelf& S = c->sr_self;
+    hipStream_t s = c->stream;
+    const size_t scan_bytes = hc::prims::scan_temp_bytes(n_pairs + 1, sizeof(uint64_t));
+    int rc;
+    if ((rc = S.len.ensure((n_pairs + 1) * sizeof(uint64_t))) || (rc = S.off.ensure((n_pairs + 1) * sizeof(uint64_t))) ||
+        (rc = S.mpos.ensure(n_pairs * sizeof(int32_t))) || (rc = S.temp.ensure(scan_bytes ? scan_bytes : 16)))
+        return rc;
+    HC_HIP(hipMemcpyAsync(S.len.p, W.len.data(), (n_pairs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemcpyAsync(S.mpos.p, W.mpos.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HC_HIP(hipEventRecord(c->ev0, s));
+    HC_HIP(hc::prims::exclusive_sum(S.temp.p, S.temp.cap, S.len.as<uint64_t>(), S.off.as<uint64_t>(), n_pairs + 1, s));
+    HC_HIP(hc::sr_self_launch_merge(d_seq, d_qual, S.pairs.as<hc_sr_pair>(), n_pairs, S.mpos.as<int32_t>(), S.off.as<uint64_t>(), total,
+                                    S.tables.terms.as<double>(), S.tables.table.as<uint8_t>(), d_out_seq, d_out_qual, s));
+    HC_HIP(hipEventRecord(c->ev1, s));
+    return HC_OK;
+}
+
+int self_merge_ms(hc_ctx* c, SelfWork& W, hc_sr_self_stats* stats) {
+    HC_HIP(hipEventElapsedTime(&W.ms_merge, c->ev0, c->ev1));
+    if (stats) stats->ms_device = (double)W.ms_scan + W.ms_merge;
+    return HC_OK;
+}
+
+// The kept consensus bytes get room for `bytes` and the check kernel's padding behind them, their contents preserved: a new block, a
+// device-to-device copy, a swap.  (hc_scratch::ensure keeps nothing, and its headroom of an eighth is less than the padding for a small block.)
+int kept_reserve(hc_ctx* c, uint64_t bytes) {
+    hc_ctx::Sr& K = c->sr;
+    for (hc_scratch* b : {&K.seq, &K.qual}) {
+        if (b->p && b->cap >= bytes + hc::kSelfPad) continue;
+        hc_scratch nb;
+        int rc = nb.ensure(bytes + hc::kSelfPad);
+        if (rc) return rc;
+        if (K.kept_bytes && b->p) HC_HIP(hipMemcpyAsync(nb.p, b->p, K.kept_bytes, hipMemcpyDeviceToDevice, c->stream));
+        HC_HIP(hipStreamSynchronize(c->stream));  // (the old block is freed by the swap's temporary)
+        b->swap(nb);
+    }
+    return HC_OK;
+}
+
+}  // namespace
+
 extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair* pairs,
                                          uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score,
                                          uint32_t* status, uint64_t* out_off, uint8_t* merged_seq, uint8_t* merged_qual, uint64_t cap,
                                          uint64_t* n_out, hc_sr_self_stats* stats) {
-    const char* me = "hc_sr_merge_self_overlaps: ";
+    const std::string me = "hc_sr_merge_self_overlaps: ";
     if (!c || !settings || !out_off || !n_out || (n_pairs && (!pairs || !overlap_pos || !score || !status)) || (n_bytes && (!seq || !qual)))
-        return fail(HC_ERR_ARG, std::string(me) + "null argument");
-    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, std::string(me) + "min_qual is NaN");
-    if (n_pairs >= (1ull << 32) - 1) return fail(HC_ERR_ARG, std::string(me) + "more than 2^32 - 2 pairs");
+        return fail(HC_ERR_ARG, me + "null argument");
+    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, me + "min_qual is NaN");
+    if (n_pairs >= (1ull << 32) - 1) return fail(HC_ERR_ARG, me + "more than 2^32 - 2 pairs");
     if (stats) memset(stats, 0, sizeof *stats);
     *n_out = 0;
     out_off[0] = 0;
     if (n_pairs == 0) return HC_OK;
     HC_HIP(hipSetDevice(c->device));
     const auto t_host0 = std::chrono::steady_clock::now();
-    double ms_host = 0;
     const unsigned n_thr = std::max(1u, settings->n_threads);
     // the pairs' checks and the quality values of the batch
-    std::vector<uint32_t> skip(n_pairs);
+    SelfBatch B;
+    B.skip.resize(n_pairs);
     const uint64_t check_block = 1024, n_check_blocks = (n_pairs + check_block - 1) / check_block;
     std::vector<std::array<uint8_t, 128>> seen(n_check_blocks);
     std::vector<uint32_t> block_max(n_check_blocks, 0);
@@ -276,8 +465,8 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
         sn.fill(0);
         uint32_t mx = 0;
         for (uint64_t i = a; i < b; i++) {
-            skip[i] = hc::srself::check_pair(seq, qual, n_bytes, pairs[i]);
-            if (skip[i]) continue;
+            B.skip[i] = hc::srself::check_pair(seq, qual, n_bytes, pairs[i]);
+            if (B.skip[i]) continue;
             const hc_sr_pair& P = pairs[i];
             for (uint32_t k = 0; k < P.len1; k++) sn[qual[P.off1 + k] & 127u] = 1;
             for (uint32_t k = 0; k < P.len2; k++) sn[qual[P.off2 + k] & 127u] = 1;
@@ -285,156 +474,201 @@ extern "C" int hc_sr_merge_self_overlaps(hc_ctx* c, const uint8_t* seq, const ui
         }
         block_max[a / check_block] = mx;
     });
-    uint32_t max_len = 0, max_first = 0;
-    uint64_t n_offsets = 0, n_valid = 0;
-    uint8_t qs_seen[96] = {0};
     for (uint64_t b = 0; b < n_check_blocks; b++) {
-        max_len = std::max(max_len, block_max[b]);
-        for (uint32_t q = 33; q <= 126; q++) qs_seen[q - 33] |= seen[b][q];
+        B.max_len = std::max(B.max_len, block_max[b]);
+        for (uint32_t q = 33; q <= 126; q++) B.qs_seen[q - 33] |= seen[b][q];
     }
     for (uint64_t i = 0; i < n_pairs; i++) {
-        overlap_pos[i] = -1;
-        score[i] = 0;
-        status[i] = skip[i];
-        if (skip[i]) continue;
-        n_valid++;
+        if (B.skip[i]) continue;
+        B.n_valid++;
         const uint32_t f = hc::srself::first_offset(pairs[i].len1, settings->min_overlap);
-        n_offsets += f;
-        max_first = std::max(max_first, f);
+        B.n_offsets += f;
+        B.max_first = std::max(B.max_first, f);
     }
-    if (stats) stats->n_offsets = n_offsets;
+    if (stats) stats->n_offsets = B.n_offsets;
     hc_ctx::SrSelf& S = c->sr_self;
     hipStream_t s = c->stream;
-    std::vector<hc::SrSelfScan> res(n_pairs);
-    std::vector<uint64_t> len(n_pairs + 1, 0);
-    std::vector<int32_t> mpos(n_pairs, -1);
-    // pairs the host finishes: (pair, the offset its scan goes on from)
-    std::vector<std::pair<uint64_t, uint32_t>> host_pairs;
-    float ms_scan = 0, ms_merge = 0;
+    SelfWork W;
+    self_begin(B, n_pairs, overlap_pos, score, status, W);
+    W.ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
     int rc = HC_OK;
-    if (n_valid && max_first) {
-        // tables: log p by the scoring path's builder for the batch's values (row = rank of the value), 1.0 / n, the consensus table
-        std::vector<int> phred;
-        uint8_t qmap[256], q_of[hc::sr::kQDim];
-        memset(qmap, 0, sizeof qmap);
-        memset(q_of, 255, sizeof q_of);
-        for (uint32_t q = 0; q < hc::srself::kQ; q++) {
-            if (!qs_seen[q]) continue;
-            qmap[q + 33] = (uint8_t)phred.size();
-            phred.push_back((int)q);
-            q_of[q] = (uint8_t)q;
-        }
-        std::vector<double> lut;
-        if (!hc::build_log_table_u16(phred, c->settings.mismatch, lut)) return fail(HC_ERR_STATE, std::string(me) + "the log table is not symmetric");
-        std::vector<double> inv_n((size_t)max_len + 1, 0.0);
-        for (uint32_t k = 1; k <= max_len; k++) inv_n[k] = 1.0 / (double)k;  // :137
-        if ((rc = sr_tables(c, S.tables, q_of, settings->min_qual))) return rc;
-        hc::SrSelfParams prm;
-        int log2_width = -49;
-        if (const char* e = getenv("HC_SR_SELF_BAND_LOG2")) {  // test knob: a wider guard band, so that the host-decided path runs
-            const int v = atoi(e);
-            if (v >= -60 && v <= -2) log2_width = v;
-        }
-        prm.band = hc::threshold_band(settings->min_score, log2_width);
-        prm.always = settings->min_score < 0 ? 1u : 0u;
-        prm.min_overlap = settings->min_overlap;
-        prm.min_read_len = c->settings.min_read_len;
-        prm.K = (uint32_t)phred.size();
-        prm.lut_doubles = (uint32_t)lut.size();
-        prm.inv_len = (uint32_t)inv_n.size();
-        const size_t scan_bytes = hc::prims::scan_temp_bytes(n_pairs + 1, sizeof(uint64_t));
+    if (B.n_valid && B.max_first) {
         if ((rc = S.seq.ensure(n_bytes)) || (rc = S.qual.ensure(n_bytes)) || (rc = S.pairs.ensure(n_pairs * sizeof(hc_sr_pair))) ||
-            (rc = S.skip.ensure(n_pairs * sizeof(uint32_t))) || (rc = S.qmap.ensure(256)) || (rc = S.lut.ensure(lut.size() * sizeof(double))) ||
-            (rc = S.inv_n.ensure(inv_n.size() * sizeof(double))) || (rc = S.res.ensure(n_pairs * sizeof(hc::SrSelfScan))) ||
-            (rc = S.len.ensure((n_pairs + 1) * sizeof(uint64_t))) || (rc = S.off.ensure((n_pairs + 1) * sizeof(uint64_t))) ||
-            (rc = S.mpos.ensure(n_pairs * sizeof(int32_t))) || (rc = S.temp.ensure(scan_bytes ? scan_bytes : 16)))
+            (rc = S.skip.ensure(n_pairs * sizeof(uint32_t))))
             return rc;
-        ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
         HC_HIP(hipMemcpyAsync(S.seq.p, seq, n_bytes, hipMemcpyHostToDevice, s));
         HC_HIP(hipMemcpyAsync(S.qual.p, qual, n_bytes, hipMemcpyHostToDevice, s));
         HC_HIP(hipMemcpyAsync(S.pairs.p, pairs, n_pairs * sizeof(hc_sr_pair), hipMemcpyHostToDevice, s));
-        HC_HIP(hipMemcpyAsync(S.skip.p, skip.data(), n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HC_HIP(hipMemcpyAsync(S.qmap.p, qmap, 256, hipMemcpyHostToDevice, s));
-        HC_HIP(hipMemcpyAsync(S.lut.p, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        HC_HIP(hipMemcpyAsync(S.inv_n.p, inv_n.data(), inv_n.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        const uint32_t lanes = 64u * std::max(1u, std::min(hc::kSelfMaxChunk / 64u, (max_first + 63u) / 64u));
-        HC_HIP(hipEventRecord(c->ev0, s));
-        HC_HIP(hc::sr_self_launch_scan(c->n_cu, lanes, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), S.pairs.as<hc_sr_pair>(), S.skip.as<uint32_t>(), n_pairs,
-                                       S.qmap.as<uint8_t>(), S.lut.as<double>(), S.inv_n.as<double>(), prm, S.res.as<hc::SrSelfScan>(), s));
-        HC_HIP(hipEventRecord(c->ev1, s));
-        HC_HIP(hipMemcpyAsync(res.data(), S.res.p, n_pairs * sizeof(hc::SrSelfScan), hipMemcpyDeviceToHost, s));
-        HC_HIP(hipStreamSynchronize(s));
-        HC_HIP(hipEventElapsedTime(&ms_scan, c->ev0, c->ev1));
-        for (uint64_t i = 0; i < n_pairs; i++) {
-            if (skip[i] || res[i].p < 0) continue;
-            if (res[i].kind == hc::kSelfHit && !S.tables.has_nan) {
-                overlap_pos[i] = res[i].p;
-                score[i] = exp(res[i].x);  // :138
-                status[i] = HC_SR_SELF_MERGED;
-                len[i] = (uint64_t)pairs[i].len2 + (uint32_t)res[i].p;  // :890
-                mpos[i] = res[i].p;
-            } else {
-                host_pairs.emplace_back(i, (uint32_t)res[i].p);
-            }
-        }
+        HC_HIP(hipMemcpyAsync(S.skip.p, B.skip.data(), n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if ((rc = self_scan(c, me, B, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), pairs, n_pairs, settings, overlap_pos, score, status, W))) return rc;
     }
-    // the host's share: the scan goes on from the offset in the band with the host's libm, as the mirror walks it
-    struct HostOut {
-        std::vector<uint8_t> seq, qual;
-    };
-    std::vector<HostOut> host_out(host_pairs.size());
-    if (!host_pairs.empty()) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const hc::srself::Tables T(c->settings.mismatch, c->settings.min_read_len);
-        hc::in_blocks(host_pairs.size(), 1, n_thr, [&](uint64_t a, uint64_t b) {
-            for (uint64_t k = a; k < b; k++) {
-                const uint64_t i = host_pairs[k].first;
-                const hc_sr_pair& P = pairs[i];
-                const hc::srself::Mates M{seq + P.off1, qual + P.off1, seq + P.off2, qual + P.off2, P.len1, P.len2};
-                overlap_pos[i] = hc::srself::scan_pair(T, M, host_pairs[k].second, *settings, &score[i], host_out[k].seq, host_out[k].qual);
-                if (overlap_pos[i] < 0) continue;
-                status[i] = HC_SR_SELF_MERGED;
-                len[i] = host_out[k].seq.size();
-            }
-        });
-        ms_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<hc::srself::Mates> mates(W.host_pairs.size());
+    for (size_t k = 0; k < mates.size(); k++) {
+        const hc_sr_pair& P = pairs[W.host_pairs[k].first];
+        mates[k] = hc::srself::Mates{seq + P.off1, qual + P.off1, seq + P.off2, qual + P.off2, P.len1, P.len2};
     }
-    uint64_t total = 0, n_merged = 0;
-    for (uint64_t i = 0; i < n_pairs; i++) {
-        out_off[i] = total;
-        total += len[i];
-        n_merged += status[i] == HC_SR_SELF_MERGED;
-    }
-    out_off[n_pairs] = total;
+    self_host_pairs(c, settings, mates, overlap_pos, score, status, W);
+    const uint64_t total = self_offsets(W, n_pairs, 0, status, out_off, stats, B.n_offsets);
     *n_out = total;
-    if (stats) {
-        stats->n_merged = n_merged;
-        stats->n_host_pairs = host_pairs.size();
-        stats->ms_device = ms_scan;
-        stats->ms_host = ms_host;
-    }
     if ((rc = hc::sr::check_room("hc_sr_merge_self_overlaps", "merged_seq / merged_qual", "n_out", total, cap, merged_seq, merged_qual))) return rc;
     if (total == 0) return HC_OK;
-    // the merged reads: offsets by an exclusive sum on the device, one lane per column
     if ((rc = S.out_seq.ensure(total)) || (rc = S.out_qual.ensure(total))) return rc;
-    HC_HIP(hipMemcpyAsync(S.len.p, len.data(), (n_pairs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HC_HIP(hipMemcpyAsync(S.mpos.p, mpos.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HC_HIP(hipEventRecord(c->ev0, s));
-    HC_HIP(hc::prims::exclusive_sum(S.temp.p, S.temp.cap, S.len.as<uint64_t>(), S.off.as<uint64_t>(), n_pairs + 1, s));
-    HC_HIP(hc::sr_self_launch_merge(S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), S.pairs.as<hc_sr_pair>(), n_pairs, S.mpos.as<int32_t>(),
-                                    S.off.as<uint64_t>(), total, S.tables.terms.as<double>(), S.tables.table.as<uint8_t>(), S.out_seq.as<uint8_t>(),
-                                    S.out_qual.as<uint8_t>(), s));
-    HC_HIP(hipEventRecord(c->ev1, s));
+    if ((rc = self_merge(c, S.seq.as<uint8_t>(), S.qual.as<uint8_t>(), n_pairs, W, total, S.out_seq.as<uint8_t>(), S.out_qual.as<uint8_t>()))) return rc;
     HC_HIP(hipMemcpyAsync(merged_seq, S.out_seq.p, total, hipMemcpyDeviceToHost, s));
     HC_HIP(hipMemcpyAsync(merged_qual, S.out_qual.p, total, hipMemcpyDeviceToHost, s));
     HC_HIP(hipStreamSynchronize(s));
-    HC_HIP(hipEventElapsedTime(&ms_merge, c->ev0, c->ev1));
-    for (size_t k = 0; k < host_pairs.size(); k++) {  // the host's pairs are spliced in
-        const uint64_t i = host_pairs[k].first;
-        if (host_out[k].seq.empty()) continue;
-        memcpy(merged_seq + out_off[i], host_out[k].seq.data(), host_out[k].seq.size());
-        memcpy(merged_qual + out_off[i], host_out[k].qual.data(), host_out[k].qual.size());
+    if ((rc = self_merge_ms(c, W, stats))) return rc;
+    for (size_t k = 0; k < W.host_pairs.size(); k++) {  // the host's pairs are spliced in
+        const uint64_t i = W.host_pairs[k].first;
+        if (W.host_out[k].seq.empty()) continue;
+        memcpy(merged_seq + out_off[i], W.host_out[k].seq.data(), W.host_out[k].seq.size());
+        memcpy(merged_qual + out_off[i], W.host_out[k].qual.data(), W.host_out[k].qual.size());
     }
-    if (stats) stats->ms_device = (double)ms_scan + ms_merge;
+    return HC_OK;
+}
+
+// The same from the consensus bytes the context keeps (hc_sr_keep_device): the check runs on the device, the mates of the pairs the host
+// decides come back packed in one copy, and the merged reads are appended to the kept bytes without crossing the link.
+extern "C" int hc_sr_merge_self_overlaps_kept(hc_ctx* c, const hc_sr_pair* pairs, uint64_t n_pairs, const hc_sr_self_settings* settings,
+                                              int32_t* overlap_pos, double* score, uint32_t* status, uint64_t* out_off, uint64_t* n_out,
+                                              hc_sr_self_stats* stats) {
+    const std::string me = "hc_sr_merge_self_overlaps_kept: ";
+    if (!c || !settings || !out_off || !n_out || (n_pairs && (!pairs || !overlap_pos || !score || !status)))
+        return fail(HC_ERR_ARG, me + "null argument");
+    if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, me + "min_qual is NaN");
+    if (n_pairs >= (1ull << 32) - 1) return fail(HC_ERR_ARG, me + "more than 2^32 - 2 pairs");
+    if (!c->srn.keep) return fail(HC_ERR_STATE, me + "hc_sr_keep_device is off");
+    hc_ctx::Sr& K = c->sr;
+    if (!K.kept_valid) return fail(HC_ERR_STATE, me + "no kept consensus bytes (hc_sr_consensus, hc_sr_edge_merge or hc_sr_kept_load first)");
+    if (stats) memset(stats, 0, sizeof *stats);
+    const uint64_t base = K.kept_bytes;
+    *n_out = 0;
+    out_off[0] = base;
+    if (n_pairs == 0) return HC_OK;
+    HC_HIP(hipSetDevice(c->device));
+    hc_ctx::SrSelf& S = c->sr_self;
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = kept_reserve(c, base)) || (rc = S.pairs.ensure(n_pairs * sizeof(hc_sr_pair))) || (rc = S.skip.ensure(n_pairs * sizeof(uint32_t))) ||
+        (rc = S.check.ensure(sizeof(hc::SrSelfCheckCounters))))
+        return rc;
+    // the pairs' checks and the quality values of the batch, on the device
+    SelfBatch B;
+    B.skip.resize(n_pairs);
+    hc::SrSelfCheckCounters cnt;
+    float ms_check = 0;
+    HC_HIP(hipMemcpyAsync(S.pairs.p, pairs, n_pairs * sizeof(hc_sr_pair), hipMemcpyHostToDevice, s));
+    HC_HIP(hipMemsetAsync(S.check.p, 0, sizeof cnt, s));
+    HC_HIP(hipEventRecord(c->ev0, s));
+    HC_HIP(hc::sr_self_launch_check(K.seq.as<uint8_t>(), K.qual.as<uint8_t>(), base, S.pairs.as<hc_sr_pair>(), n_pairs, settings->min_overlap,
+                                    S.skip.as<uint32_t>(), S.check.as<hc::SrSelfCheckCounters>(), s));
+    HC_HIP(hipEventRecord(c->ev1, s));
+    HC_HIP(hipMemcpyAsync(B.skip.data(), S.skip.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipMemcpyAsync(&cnt, S.check.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HC_HIP(hipStreamSynchronize(s));
+    HC_HIP(hipEventElapsedTime(&ms_check, c->ev0, c->ev1));
+    for (uint32_t q = 33; q <= 126; q++) B.qs_seen[q - 33] = (cnt.qmask[q >> 5] >> (q & 31u)) & 1u;
+    B.max_len = cnt.max_len;
+    B.max_first = cnt.max_first;
+    B.n_offsets = cnt.sum_first;
+    B.n_valid = cnt.n_valid;
+    if (stats) stats->n_offsets = B.n_offsets;
+    SelfWork W;
+    self_begin(B, n_pairs, overlap_pos, score, status, W);
+    if (B.n_valid && B.max_first &&
+        (rc = self_scan(c, me, B, K.seq.as<uint8_t>(), K.qual.as<uint8_t>(), pairs, n_pairs, settings, overlap_pos, score, status, W)))
+        return rc;
+    W.ms_scan += ms_check;
+    // the pairs the host decides: their mates, packed by the copy kernel, in one copy each for bases and qualities
+    const size_t n_host = W.host_pairs.size();
+    std::vector<hc::SrSelfSeg> segs(n_host);
+    std::vector<uint8_t> h_seq, h_qual;
+    std::vector<hc::srself::Mates> mates(n_host);
+    if (n_host) {
+        uint64_t at = 0;
+        for (size_t k = 0; k < n_host; k++) {
+            const hc_sr_pair& P = pairs[W.host_pairs[k].first];
+            segs[k] = hc::SrSelfSeg{P.off1, P.off2, at, P.len1, P.len2};
+            at += (uint64_t)P.len1 + P.len2;
+        }
+        h_seq.resize(at);
+        h_qual.resize(at);
+        if ((rc = S.segs.ensure(n_host * sizeof(hc::SrSelfSeg))) || (rc = S.stage_seq.ensure(at)) || (rc = S.stage_qual.ensure(at))) return rc;
+        HC_HIP(hipMemcpyAsync(S.segs.p, segs.data(), n_host * sizeof(hc::SrSelfSeg), hipMemcpyHostToDevice, s));
+        HC_HIP(hc::sr_self_launch_copy(S.segs.as<hc::SrSelfSeg>(), n_host, K.seq.as<uint8_t>(), K.qual.as<uint8_t>(), S.stage_seq.as<uint8_t>(),
+                                       S.stage_qual.as<uint8_t>(), s));
+        HC_HIP(hipMemcpyAsync(h_seq.data(), S.stage_seq.p, at, hipMemcpyDeviceToHost, s));
+        HC_HIP(hipMemcpyAsync(h_qual.data(), S.stage_qual.p, at, hipMemcpyDeviceToHost, s));
+        HC_HIP(hipStreamSynchronize(s));
+        for (size_t k = 0; k < n_host; k++) {
+            const hc::SrSelfSeg& g = segs[k];
+            mates[k] = hc::srself::Mates{h_seq.data() + g.dst, h_qual.data() + g.dst, h_seq.data() + g.dst + g.len1, h_qual.data() + g.dst + g.len1,
+                                         g.len1, g.len2};
+        }
+    }
+    self_host_pairs(c, settings, mates, overlap_pos, score, status, W);
+    const uint64_t total = self_offsets(W, n_pairs, base, status, out_off, stats, B.n_offsets);
+    if (total == 0) return HC_OK;
+    // the kept bytes grow, and the merged reads are written straight behind them
+    if ((rc = kept_reserve(c, base + total))) return rc;
+    if ((rc = self_merge(c, K.seq.as<uint8_t>(), K.qual.as<uint8_t>(), n_pairs, W, total, K.seq.as<uint8_t>() + base, K.qual.as<uint8_t>() + base)))
+        return rc;
+    // the host's pairs are spliced in: their merged reads go up packed, and the copy kernel puts them in place
+    uint64_t n_up = 0, up_bytes = 0;
+    for (size_t k = 0; k < n_host; k++) {
+        const uint64_t n = W.host_out[k].seq.size();
+        if (!n) continue;
+        memcpy(h_seq.data() + up_bytes, W.host_out[k].seq.data(), n);  // (a merged read is shorter than its mates together: it fits)
+        memcpy(h_qual.data() + up_bytes, W.host_out[k].qual.data(), n);
+        segs[n_up++] = hc::SrSelfSeg{up_bytes, 0, out_off[W.host_pairs[k].first], (uint32_t)n, 0};
+        up_bytes += n;
+    }
+    if (n_up) {
+        HC_HIP(hipMemcpyAsync(S.segs.p, segs.data(), n_up * sizeof(hc::SrSelfSeg), hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.stage_seq.p, h_seq.data(), up_bytes, hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(S.stage_qual.p, h_qual.data(), up_bytes, hipMemcpyHostToDevice, s));
+        HC_HIP(hc::sr_self_launch_copy(S.segs.as<hc::SrSelfSeg>(), n_up, S.stage_seq.as<uint8_t>(), S.stage_qual.as<uint8_t>(), K.seq.as<uint8_t>(),
+                                       K.qual.as<uint8_t>(), s));
+    }
+    HC_HIP(hipStreamSynchronize(s));
+    if ((rc = self_merge_ms(c, W, stats))) return rc;
+    K.kept_bytes = base + total;
+    *n_out = total;
+    return HC_OK;
+}
+
+extern "C" int hc_sr_kept_load(hc_ctx* c, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes) {
+    const std::string me = "hc_sr_kept_load: ";
+    if (!c || (n_bytes && (!seq || !qual))) return fail(HC_ERR_ARG, me + "null argument");
+    if (!c->srn.keep) return fail(HC_ERR_STATE, me + "hc_sr_keep_device is off");
+    HC_HIP(hipSetDevice(c->device));
+    hc_ctx::Sr& K = c->sr;
+    K.kept_valid = false;
+    K.kept_bytes = 0;
+    int rc = kept_reserve(c, n_bytes);
+    if (rc) return rc;
+    if (n_bytes) {
+        HC_HIP(hipMemcpyAsync(K.seq.p, seq, n_bytes, hipMemcpyHostToDevice, c->stream));
+        HC_HIP(hipMemcpyAsync(K.qual.p, qual, n_bytes, hipMemcpyHostToDevice, c->stream));
+        HC_HIP(hipStreamSynchronize(c->stream));
+    }
+    K.kept_bytes = n_bytes;
+    K.kept_valid = true;
+    return HC_OK;
+}
+
+extern "C" int hc_sr_kept_fetch(hc_ctx* c, uint64_t off, uint64_t n, uint8_t* seq, uint8_t* qual, uint64_t* n_kept) {
+    const std::string me = "hc_sr_kept_fetch: ";
+    if (!c || !n_kept) return fail(HC_ERR_ARG, me + "null argument");
+    const hc_ctx::Sr& K = c->sr;
+    *n_kept = (c->srn.keep && K.kept_valid) ? K.kept_bytes : 0;
+    if (!c->srn.keep || !K.kept_valid) return fail(HC_ERR_STATE, me + "no kept consensus bytes (hc_sr_keep_device, then hc_sr_consensus or hc_sr_kept_load)");
+    if (off > K.kept_bytes || n > K.kept_bytes - off) return fail(HC_ERR_ARG, me + "the range does not lie inside the kept bytes");
+    if (n == 0) return HC_OK;
+    if (!seq || !qual) return fail(HC_ERR_ARG, me + "null buffer");
+    HC_HIP(hipSetDevice(c->device));
+    HC_HIP(hipMemcpyAsync(seq, K.seq.as<uint8_t>() + off, n, hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipMemcpyAsync(qual, K.qual.as<uint8_t>() + off, n, hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipStreamSynchronize(c->stream));
     return HC_OK;
 }

@@ -308,7 +308,8 @@ struct hc_ctx {
     struct Sr {
         hc_scratch layouts, members, mem, info, len, off, temp, seq, qual, late, host_cols, counter;
         SrTables tables;
-        // hc_sr_keep_device: seq / qual hold the last call's bytes in their final form (kept_bytes of them), patched by `patches`
+        // hc_sr_keep_device: seq / qual hold the last call's bytes in their final form (kept_bytes of them), patched by `patches`;
+        // hc_sr_merge_self_overlaps_kept appends to them and hc_sr_kept_load replaces them (hc_api_sr.cpp)
         hc_scratch patches;
         bool kept_valid = false;
         uint64_t kept_bytes = 0;
@@ -329,6 +330,8 @@ struct hc_ctx {
     // the batch's quality values change (term index = the value itself)
     struct SrSelf {
         hc_scratch seq, qual, pairs, skip, qmap, lut, inv_n, res, len, off, mpos, temp, out_seq, out_qual;
+        // hc_sr_merge_self_overlaps_kept: the check kernel's counters; the host-decided pairs' copy records and staging block
+        hc_scratch check, segs, stage_seq, stage_qual;
         SrTables tables;
     } sr_self;
     // edge merge (hc_api_sr_edge.cpp: hc_graph_merge_pairs, hc_sr_edge_merge): grow-only scratch — the target column; the call's pairs and

@@ -14,11 +14,22 @@
 // sr_self_merge_kernel: one lane per output column of the merged pairs: consensus() of {mate 1 at 0, mate 2 at p} (:890-903), the
 // quality from the host-built table of one- and two-member columns, the base from the exact sums by comparison (hc_sr_column.h).
 // No transcendental function runs on the device.
+//
+// hc_sr_merge_self_overlaps_kept, whose mates are the consensus bytes the context keeps on the device, has two kernels more.
+// sr_self_check_kernel: one wave per pair, what the host-input call's host loop does (the tests of host/SrSelfCheck.h and the batch's
+//   quality values).  The range test comes first, is wave-uniform, and nothing is read for a pair it refuses.  Each mate is read in
+//   16-byte loads from the 16-byte boundary at or before its first byte on; the bytes of a load that lie outside the mate are masked,
+//   so the buffers hold kSelfPad bytes behind the last one.  Validity is decided on packed bytes, four to a word.  A lane keeps the
+//   quality bytes it saw as a 128-bit mask; the wave ORs the lanes' masks, adds them to its own only when the pair is valid (as the
+//   host does), and at its end the workgroup folds its waves' masks and counters in LDS into a handful of vector atomics.
+// sr_self_copy_kernel: one wave per record, 16 bytes a lane and step.  It packs the mates of the pairs the host decides into a staging
+//   block, and later writes those pairs' merged reads, uploaded packed, behind the kept bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hc_sr_column.h"
 #include "hc_sr_self.h"
+#include "host/SrSelfCheck.h"
 
 namespace hc {
 namespace {
@@ -163,7 +174,152 @@ __global__ __launch_bounds__(256) void sr_self_merge_kernel(const uint8_t* __res
     sr_put(entry, col.nuc(col.max_sum()), out_seq[g], out_qual[g]);
 }
 
+// This lane's share of the mate [off, off + len) of seq / qual (both 16-byte aligned, readable up to the 16-byte boundary behind the mate):
+// bad |= a refused symbol; q_lo / q_hi |= the quality bytes seen, bit (byte & 127)
+__device__ inline void lane_check_mate(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, uint64_t off, uint32_t len, uint32_t lane,
+                                       uint32_t& bad, uint64_t& q_lo, uint64_t& q_hi) {
+    const uint64_t v0 = off >> 4, v1 = (off + len + 15u) >> 4;  // the 16-byte vectors [v0, v1) cover the mate
+    const uint4* sv = (const uint4*)seq;
+    const uint4* qv = (const uint4*)qual;
+    for (uint64_t v = v0 + lane; v < v1; v += 64) {
+        const uint4 b = sv[v], q = qv[v];
+        const uint32_t bw[4] = {b.x, b.y, b.z, b.w}, qw[4] = {q.x, q.y, q.z, q.w};
+        const int64_t lo = (int64_t)off - (int64_t)(v << 4), hi = (int64_t)(off + len) - (int64_t)(v << 4);  // the mate's bytes of this vector: [lo, hi)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t in = srself::bytes_between(lo - 4 * k, hi - 4 * k);
+            bad |= srself::bytes_bad(bw[k], qw[k]) & in;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t qb = (qw[k] >> (8 * j)) & 127u;
+                const uint64_t bit = ((in >> (8 * j + 7)) & 1u) ? 1ull << (qb & 63u) : 0ull;
+                q_lo |= (qb & 64u) ? 0ull : bit;
+                q_hi |= (qb & 64u) ? bit : 0ull;
+            }
+        }
+    }
+}
+
+__device__ inline uint32_t wave_or(uint32_t v) {
+    for (int o = 32; o; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void sr_self_check_kernel(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, uint64_t n_bytes,
+                                                            const hc_sr_pair* __restrict__ pairs, uint64_t n_pairs, uint32_t min_overlap,
+                                                            uint32_t* __restrict__ status, SrSelfCheckCounters* __restrict__ counters) {
+    __shared__ uint32_t w_mask[4][4], w_max_len[4], w_max_first[4];
+    __shared__ unsigned long long w_sum_first[4], w_valid[4];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    // the wave's share over its valid pairs (the same in every lane)
+    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0, max_len = 0, max_first = 0;
+    unsigned long long sum_first = 0, n_valid = 0;
+    for (uint64_t i = wave; i < n_pairs; i += n_waves) {
+        const hc_sr_pair P = pairs[i];
+        uint32_t st = HC_SR_SELF_BAD_PAIR;
+        if (srself::pair_in_range(n_bytes, P)) {  // (wave-uniform)
+            uint32_t bad = 0;
+            uint64_t q_lo = 0, q_hi = 0;
+            lane_check_mate(seq, qual, P.off1, P.len1, lane, bad, q_lo, q_hi);
+            lane_check_mate(seq, qual, P.off2, P.len2, lane, bad, q_lo, q_hi);
+            if (wave_or(bad)) {
+                st = HC_SR_SELF_BAD_SYMBOL;
+            } else {
+                st = HC_SR_SELF_NONE;
+                m0 |= wave_or((uint32_t)q_lo);
+                m1 |= wave_or((uint32_t)(q_lo >> 32));
+                m2 |= wave_or((uint32_t)q_hi);
+                m3 |= wave_or((uint32_t)(q_hi >> 32));
+                const uint32_t f = srself::first_offset(P.len1, min_overlap);
+                max_len = max(max_len, max(P.len1, P.len2));
+                max_first = max(max_first, f);
+                sum_first += f;
+                n_valid++;
+            }
+        }
+        if (lane == 0) status[i] = st;
+    }
+    if (lane == 0) {
+        w_mask[wv][0] = m0;
+        w_mask[wv][1] = m1;
+        w_mask[wv][2] = m2;
+        w_mask[wv][3] = m3;
+        w_max_len[wv] = max_len;
+        w_max_first[wv] = max_first;
+        w_sum_first[wv] = sum_first;
+        w_valid[wv] = n_valid;
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    if (t < 4) {
+        const uint32_t m = w_mask[0][t] | w_mask[1][t] | w_mask[2][t] | w_mask[3][t];
+        if (m) atomicOr(&counters->qmask[t], m);
+    } else if (t == 4) {
+        const unsigned long long v = w_valid[0] + w_valid[1] + w_valid[2] + w_valid[3];
+        if (v) {
+            atomicAdd((unsigned long long*)&counters->n_valid, v);
+            atomicAdd((unsigned long long*)&counters->sum_first, w_sum_first[0] + w_sum_first[1] + w_sum_first[2] + w_sum_first[3]);
+            atomicMax(&counters->max_len, max(max(w_max_len[0], w_max_len[1]), max(w_max_len[2], w_max_len[3])));
+            atomicMax(&counters->max_first, max(max(w_max_first[0], w_max_first[1]), max(w_max_first[2], w_max_first[3])));
+        }
+    }
+}
+
+// d[0, len) = s[0, len) by one wave: stores on 16-byte boundaries of d, loads wherever s starts
+__device__ inline void wave_copy_bytes(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, uint32_t len, uint32_t lane) {
+    uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
+    if (head > len) head = len;
+    if (lane < head) d[lane] = s[lane];
+    const uint32_t nvec = (len - head) >> 4;
+    for (uint32_t v = lane; v < nvec; v += 64) {
+        const uint32_t i0 = head + (v << 4);  // i0 + 16 <= len
+        uint4 w;
+        __builtin_memcpy(&w, s + i0, 16);
+        *(uint4*)(d + i0) = w;
+    }
+    const uint32_t t0 = head + (nvec << 4);
+    if (lane < len - t0) d[t0 + lane] = s[t0 + lane];
+}
+
+__global__ __launch_bounds__(256) void sr_self_copy_kernel(const SrSelfSeg* __restrict__ segs, uint64_t n, const uint8_t* __restrict__ src_seq,
+                                                           const uint8_t* __restrict__ src_qual, uint8_t* __restrict__ dst_seq,
+                                                           uint8_t* __restrict__ dst_qual) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t i = wave; i < n; i += n_waves) {
+        const SrSelfSeg g = segs[i];
+        wave_copy_bytes(dst_seq + g.dst, src_seq + g.src1, g.len1, lane);
+        wave_copy_bytes(dst_qual + g.dst, src_qual + g.src1, g.len1, lane);
+        wave_copy_bytes(dst_seq + g.dst + g.len1, src_seq + g.src2, g.len2, lane);
+        wave_copy_bytes(dst_qual + g.dst + g.len1, src_qual + g.src2, g.len2, lane);
+    }
+}
+
+inline uint32_t self_wave_grid(uint64_t n) {  // one wave per item in workgroups of four, at most 2^16 workgroups (the kernels stride)
+    const uint64_t g = (n + 3) / 4;
+    return (uint32_t)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
+
 }  // namespace
+
+hipError_t sr_self_launch_check(const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair* pairs, uint64_t n_pairs,
+                                uint32_t min_overlap, uint32_t* status, SrSelfCheckCounters* counters, hipStream_t s) {
+    if (n_pairs == 0) return hipSuccess;
+    if (((uintptr_t)seq | (uintptr_t)qual) & 15u) return hipErrorInvalidValue;
+    // at most 2,048 workgroups, which stride: every workgroup ends in up to eight atomics on the same eight words
+    const uint32_t grid = self_wave_grid(n_pairs) < 2048u ? self_wave_grid(n_pairs) : 2048u;
+    hipLaunchKernelGGL(sr_self_check_kernel, dim3(grid), dim3(256), 0, s, seq, qual, n_bytes, pairs, n_pairs, min_overlap, status,
+                       counters);
+    return hipGetLastError();
+}
+
+hipError_t sr_self_launch_copy(const SrSelfSeg* segs, uint64_t n, const uint8_t* src_seq, const uint8_t* src_qual, uint8_t* dst_seq,
+                               uint8_t* dst_qual, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(sr_self_copy_kernel, dim3(self_wave_grid(n)), dim3(256), 0, s, segs, n, src_seq, src_qual, dst_seq, dst_qual);
+    return hipGetLastError();
+}
 
 hipError_t sr_self_launch_scan(uint32_t n_cu, uint32_t lanes, const uint8_t* seq, const uint8_t* qual, const hc_sr_pair* pairs, const uint32_t* skip,
                                uint64_t n_pairs, const uint8_t* qmap, const double* lut, const double* inv_n, const SrSelfParams& prm, SrSelfScan* out,

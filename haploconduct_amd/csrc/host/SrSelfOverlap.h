@@ -17,6 +17,7 @@
 #include "../../../include/hcsr.h"
 #include "LogP.h"
 #include "SrConsensus.h"
+#include "SrSelfCheck.h"
 
 namespace hc {
 namespace srself {
@@ -42,13 +43,12 @@ struct Mates {
 
 // HC_SR_SELF_BAD_PAIR / HC_SR_SELF_BAD_SYMBOL, or HC_SR_SELF_NONE for a pair the scan may read (hcsr.h)
 inline uint32_t check_pair(const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes, const hc_sr_pair& P) {
-    if (P.len1 == 0 || P.len2 == 0 || (uint64_t)P.len1 + P.len2 > (uint64_t)INT32_MAX) return HC_SR_SELF_BAD_PAIR;
-    if (P.off1 > n_bytes || P.len1 > n_bytes - P.off1 || P.off2 > n_bytes || P.len2 > n_bytes - P.off2) return HC_SR_SELF_BAD_PAIR;
+    if (!pair_in_range(n_bytes, P)) return HC_SR_SELF_BAD_PAIR;  // (SrSelfCheck.h: shared with the device's check)
     for (int mate = 0; mate < 2; mate++) {
         const uint64_t off = mate ? P.off2 : P.off1;
         const uint32_t len = mate ? P.len2 : P.len1;
         for (uint32_t i = 0; i < len; i++)
-            if (code_of(seq[off + i]) > kCodeN || qual[off + i] < 33 || qual[off + i] > 126) return HC_SR_SELF_BAD_SYMBOL;
+            if (symbol_bad(seq[off + i], qual[off + i])) return HC_SR_SELF_BAD_SYMBOL;
     }
     return HC_SR_SELF_NONE;
 }
@@ -101,8 +101,7 @@ inline bool merge_at(const Tables& T, const Mates& M, uint32_t p, double min_qua
     return true;
 }
 
-// the first offset the scan tries (:879-882), 0 = none
-inline uint32_t first_offset(uint32_t len1, uint32_t min_overlap) { return len1 > min_overlap ? len1 - min_overlap : 0u; }
+// (first_offset, the first offset the scan tries, :879-882: SrSelfCheck.h)
 
 // the scan of :879-953 from offset `from` downwards.  Returns the offset taken (seq / qual hold the merged read, *score its score) or -1.
 inline int32_t scan_pair(const Tables& T, const Mates& M, uint32_t from, const hc_sr_self_settings& st, double* score, std::vector<uint8_t>& seq,

@@ -67,6 +67,26 @@ class EdgeScorer:
         st = SR.make_self_settings(min_score, min_qual, min_overlap, n_threads)
         return SR.run_self(lambda *a: N.lib.hc_sr_merge_self_overlaps(self._ctx, *a), seq, qual, pairs, st, count_first)
 
+    def sr_merge_self_overlaps_kept(self, pairs, min_score=0.99, min_qual=0.99, min_overlap=15, n_threads=16):
+        """hc_sr_merge_self_overlaps_kept: the same merge with the mates read from the consensus bytes kept on the device (sr_keep_device,
+        then sr_consensus / sr_edge_merge / sr_kept_load) and the merged reads appended to them.  pairs index the kept bytes.  Returns a
+        consensus.SrSelfKeptResult: out_off holds absolute kept offsets, which sr_set_next_reads takes as SR_SRC_CONSENSUS."""
+        from . import consensus as SR
+
+        return SR.run_self_kept(self._ctx, pairs, SR.make_self_settings(min_score, min_qual, min_overlap, n_threads))
+
+    def sr_kept_load(self, seq, qual):
+        """hc_sr_kept_load: packed bytes of the caller's become the kept consensus bytes."""
+        from . import consensus as SR
+
+        SR.kept_load(self._ctx, seq, qual)
+
+    def sr_kept_fetch(self, off=0, n=None):
+        """hc_sr_kept_fetch: (seq, qual) = bytes [off, off + n) of the kept consensus bytes (n = None: to their end)."""
+        from . import consensus as SR
+
+        return SR.kept_fetch(self._ctx, off, n)
+
     # -- edge merges on the device graph (include/hcsr.h) -----------------------
     def graph_merge_pairs(self, with_stats=False):
         """hc_graph_merge_pairs: OverlapGraph::getEdgesForMerging (src/GraphAlgos.cpp:112-148) on the device graph; (n, 2) vertex ids in

@@ -258,7 +258,7 @@ typedef struct hc_sr_self_stats {
  * unmerged pair owns no bytes).  cap / *n_out: as hc_sr_consensus' cap / *n_bytes, cap = 0 with NULL buffers is the count of
  * count-then-fetch (HC_ERR_ARG, everything but the bytes filled).  stats may be NULL.
  * Left to the caller: index2 += p in the subread map and in the original indexes and the re-sort of the clique by
- * index (:911-949), and Read::test_N_rate (src/Read.h:214-234).
+ * index (:911-949), and Read::test_N_rate (src/Read.h:214-234).  (The mates on the device already: hc_sr_merge_self_overlaps_kept.)
  * Numerics (DESIGN.md "Self-overlap merge"): the device adds host-built log p terms, one lane per offset, in position order;
  * score > min_score is decided on x = (1.0 / n) * sum against the x-space image of min_score, an offset inside the guard band
  * goes to the host's libm; the merged bytes come from hc_host_sr_table.  The result is the reference's, byte for byte. */
@@ -266,6 +266,47 @@ int hc_sr_merge_self_overlaps(hc_ctx* ctx, const uint8_t* seq, const uint8_t* qu
                               uint64_t n_pairs, const hc_sr_self_settings* settings, int32_t* overlap_pos, double* score,
                               uint32_t* status, uint64_t* out_off, uint8_t* merged_seq, uint8_t* merged_qual, uint64_t cap,
                               uint64_t* n_out, hc_sr_self_stats* stats);
+
+/* ---- the same merge from the consensus bytes the context keeps ------------------------------------------------------------
+ *
+ * Between hc_sr_consensus / hc_sr_edge_merge with hc_sr_keep_device on, which leave their bytes on the device, and
+ * hc_sr_set_next_reads, which builds the next store from them, sits process_cliques' self-overlap test
+ * (src/SRBuilder.cpp:982-996).  The calls below run it without bringing the bytes to the host and back. */
+
+/* merge_self_overlap (src/SRBuilder.cpp:872-955) for every pair, the mates read from the KEPT consensus bytes and the merged
+ * reads APPENDED to them.  The contract is hc_sr_merge_self_overlaps' word for word — the offsets tried and their order
+ * (:879-888), the early exit at the first offset above min_score, the merge (:890-903, going on at :904 where consensus() comes
+ * back empty), the statuses including the stated tightening of HC_SR_SELF_BAD_SYMBOL, the guard band and the host's exp — with
+ * two differences: off1 / off2 index the kept bytes as they stand when the call starts, and n_bytes is the kept size.
+ * Outputs per pair: overlap_pos / score / status as there.  The merged bytes of pair i are written to the kept buffers at
+ * [out_off[i], out_off[i + 1]): ABSOLUTE offsets into the kept bytes, out_off[0] = the kept size on entry, n_pairs + 1 entries.
+ * *n_out = bytes appended.  The kept size grows by *n_out on success and is untouched on any error.  A second call appends
+ * behind the first, and its pairs may name bytes the first appended; hc_sr_set_next_reads names the merged reads as
+ * HC_SR_SRC_CONSENSUS at out_off[i]; the next hc_sr_consensus / hc_sr_edge_merge replaces the kept bytes as it does without
+ * this call, the appended region included.
+ * HC_ERR_STATE: hc_sr_keep_device is off, or nothing is kept.  n_pairs == 0: HC_OK, out_off[0] = the kept size.
+ * The pairs are checked on the device (the range test is the host's own function, and nothing is read for an
+ * HC_SR_SELF_BAD_PAIR); stats->ms_host counts only the tables and the host-decided pairs, stats->ms_device the check kernel too.
+ * Nothing of the mates or the merged reads crosses the link but the mates of the pairs the host decides.  stats may be NULL.
+ * Left to the caller, as with hc_sr_merge_self_overlaps: index2 += p in the subread map and in the original indexes and the
+ * re-sort of the clique by index (src/SRBuilder.cpp:911-949), and Read::test_N_rate (src/Read.h:214-234; hc_sr_set_next_reads
+ * applies it). */
+int hc_sr_merge_self_overlaps_kept(hc_ctx* ctx, const hc_sr_pair* pairs, uint64_t n_pairs, const hc_sr_self_settings* settings,
+                                   int32_t* overlap_pos, double* score, uint32_t* status, uint64_t* out_off, uint64_t* n_out,
+                                   hc_sr_self_stats* stats);
+
+/* Makes the caller's bytes the kept consensus bytes (n_bytes each; 0 is allowed: kept, and empty), as if the last
+ * hc_sr_consensus had written them: for super-reads that come from somewhere other than this context's last consensus call —
+ * process_cliques (src/SRBuilder.cpp:958-1029) takes its super-reads from whichever constructSuperread made them.
+ * HC_ERR_STATE: hc_sr_keep_device is off.  Left to the caller: that the bytes are super-reads at all; nothing is checked here,
+ * the calls that read them check what they read. */
+int hc_sr_kept_load(hc_ctx* ctx, const uint8_t* seq, const uint8_t* qual, uint64_t n_bytes);
+
+/* Copies [off, off + n) of the kept consensus bytes out — the merged reads of hc_sr_merge_self_overlaps_kept for whoever
+ * writes them as text (src/SRBuilder.cpp:1416-1556), off the critical path.  *n_kept = the kept size, always filled (0 when
+ * nothing is kept: HC_ERR_STATE).  A range that does not lie inside the kept bytes: HC_ERR_ARG, nothing copied.  n = 0 asks for
+ * the size alone.  Left to the caller: the FASTQ text itself. */
+int hc_sr_kept_fetch(hc_ctx* ctx, uint64_t off, uint64_t n, uint8_t* seq, uint8_t* qual, uint64_t* n_kept);
 
 /* The same contract on the host (no device, no context): overlap_score (src/EdgeCalculator.cpp:26-139) offset by offset and
  * consensus_pos column by column, as the reference walks them, on settings->n_threads threads.  Of hc_settings only
@@ -285,7 +326,8 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * context's read store by the result.
  * Left to the caller: the original-index maps and subreads.txt (the subread infos of an edge merge: hc_sr_edge_merge);
  * ignore_inclusions and the tip handling of mergeAlongEdges (:1298-1311: the caller omits those vertices); the FASTQ text
- * itself; a device-input form of hc_sr_merge_self_overlaps. */
+ * itself; the index shifts and the re-sort of a clique that merge_self_overlap merged (:911-949).  (The self-overlap test
+ * between the consensus call and this one runs on the kept bytes: hc_sr_merge_self_overlaps_kept.) */
 
 /* Off by default: every other call then behaves and allocates as it does without this section.  While it is on, hc_set_reads
  * keeps its device copies of the raw base, quality and offset arrays (trivial super-reads are copied from them: the encoded
