@@ -121,7 +121,7 @@ static int create_ctx(hc_ctx* c, const hc_settings* settings) {
     HC_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HC_HIP(hipEventCreate(&c->ev0));
     HC_HIP(hipEventCreate(&c->ev1));
-    HC_HIP(hipMalloc((void**)&c->d_totals, 2 * sizeof(unsigned long long)));
+    if (const int rc = c->d_totals.ensure_exact(2 * sizeof(unsigned long long))) return rc;
     HC_HIP(hc::set_score_kernel_lds_limit());
     apply_settings(c, settings);
     return HC_OK;
@@ -146,38 +146,12 @@ int hc_create(hc_ctx** out, const hc_settings* settings) {
     return HC_OK;
 }
 
-// scratch_too = false (hc_reset: the resident process, a caller's stage after stage on parked devices): the grow-only scratch of the finder and
-// of the SFO ingest — gigabytes at config 3's size — stays with the context for the next read set.  Giving it back and asking for it again
-// every stage stalled the next stage's first kernels by 0.3 - 0.4 s on this pool (round 6: profiles/r06_stage_a_from_store.md).
-static void free_store(hc_ctx* c, bool scratch_too = true) {
-    if (scratch_too) {
-        for (auto& sl : c->finder_scratch) {
-            if (sl.p) (void)hipFree(sl.p);
-            sl.p = nullptr;
-            sl.cap = 0;
-        }
-        for (auto& sl : c->ingest_scratch) {
-            if (sl.p) (void)hipFree(sl.p);
-            sl.p = nullptr;
-            sl.cap = 0;
-        }
-        if (c->d_found_lines) (void)hipFree(c->d_found_lines);
-        c->d_found_lines = nullptr;
-        c->found_lines_cap = 0;
-        if (c->d_found) (void)hipFree(c->d_found);
-        c->d_found = nullptr;
-        c->found_cap = 0;
-    }
+// The read store goes; the grow-only scratch of the finder and of the SFO ingest, d_found and d_found_lines stay with the context for the
+// next read set (hc_ctx.h).
+static void free_store(hc_ctx* c) {
     c->n_found = 0;
     c->found_valid = false;
-    if (c->d_sym) (void)hipFree(c->d_sym);
-    if (c->d_reads) (void)hipFree(c->d_reads);
-    if (c->d_lut) (void)hipFree(c->d_lut);
-    if (c->d_inv_n) (void)hipFree(c->d_inv_n);
-    c->d_inv_n = nullptr;
-    c->d_sym = nullptr;
-    c->d_reads = nullptr;
-    c->d_lut = nullptr;
+    for (hc_scratch* b : {&c->d_sym, &c->d_reads, &c->d_lut, &c->d_inv_n}) b->release();
     c->have_reads = false;
     c->store_bytes = 0;
     c->loc_reads = 0;
@@ -187,30 +161,15 @@ int hc_destroy(hc_ctx* c) {
     if (!c) return HC_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_store(c);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_totals) (void)hipFree(c->d_totals);
-    if (c->d_started) (void)hipFree(c->d_started);
-    if (c->d_sort) (void)hipFree(c->d_sort);
-    if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
-    if (c->d_compact_tmp) (void)hipFree(c->d_compact_tmp);
-    if (c->d_compact_idx) (void)hipFree(c->d_compact_idx);
-    if (c->d_compact_res) (void)hipFree(c->d_compact_res);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->scratch_done) (void)hipEventDestroy(c->scratch_done);
-    for (int t = 0; t < 2; t++) {
-        if (c->graph.h_stage[t]) (void)hipHostFree(c->graph.h_stage[t]);
-        if (c->h_ingest[t]) (void)hipHostFree(c->h_ingest[t]);
-        if (c->graph.stage_free[t]) (void)hipEventDestroy(c->graph.stage_free[t]);
-    }
-    for (void* h : c->h_sfo_text)
-        if (h) (void)hipHostFree(h);
+    for (hipEvent_t e : c->graph.stage_free)
+        if (e) (void)hipEventDestroy(e);
     for (hipStream_t s : c->text_copy_stream)
         if (s) (void)hipStreamDestroy(s);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (the memory goes with its members)
     return HC_OK;
 }
 
@@ -270,7 +229,7 @@ bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting,
 
 extern "C++" {
 namespace hc {
-void release_store(hc_ctx* c) { free_store(c, false); }
+void release_store(hc_ctx* c) { free_store(c); }
 
 // (b) of hc_set_reads: everything that follows from the byte histograms of the qualities (hist) and the bases (base_hist), the sequence
 // lengths (P.seq_len, P.total: filled by the caller) and which reads are pairs — the quality map with its frequency dealing and wide
@@ -409,26 +368,20 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
     const std::vector<double>& lut = P.lut;
     const uint8_t* qmap = P.qmap;
     const bool any_bad_base = P.any_bad_base;
-    struct Tmp {  // freed on every return path
-        void* p = nullptr;
-        ~Tmp() {
-            if (p) (void)hipFree(p);
-        }
-    } t_qmap, t_seq_bad, t_seq_off, t_rc_delta;
+    hc_scratch t_qmap, t_seq_bad, t_seq_off, t_rc_delta;  // this call's own
     const uint64_t sym_bytes_total = (nsym ? nsym : 1) * symbytes;
-    HC_HIP(hipMalloc(&c->d_sym, sym_bytes_total));
-    HC_HIP(hipMalloc((void**)&c->d_reads, sizeof(hc::ReadDesc) * (n_reads ? n_reads : 1)));
-    HC_HIP(hipMalloc((void**)&c->d_lut, sizeof(double) * lut.size()));
-    HC_HIP(hipMalloc(&t_seq_off.p, sizeof(uint64_t) * (n_seq ? n_seq : 1)));
-    HC_HIP(hipMalloc(&t_seq_bad.p, (n_seq ? n_seq : 1)));
-    HC_HIP(hipMalloc(&t_qmap.p, 256));
-    HC_HIP(hipMalloc(&t_rc_delta.p, sizeof(uint32_t) * (n_seq ? n_seq : 1)));
-    uint8_t *d_qmap = (uint8_t*)t_qmap.p, *d_seq_bad = (uint8_t*)t_seq_bad.p;
-    uint64_t* d_seq_off = (uint64_t*)t_seq_off.p;
+    int rc;
+    if ((rc = c->d_sym.ensure_exact(sym_bytes_total)) || (rc = c->d_reads.ensure_exact(sizeof(hc::ReadDesc) * (n_reads ? n_reads : 1))) ||
+        (rc = c->d_lut.ensure_exact(sizeof(double) * lut.size())) || (rc = t_seq_off.ensure_exact(sizeof(uint64_t) * (n_seq ? n_seq : 1))) ||
+        (rc = t_seq_bad.ensure_exact(n_seq ? n_seq : 1)) || (rc = t_qmap.ensure_exact(256)) ||
+        (rc = t_rc_delta.ensure_exact(sizeof(uint32_t) * (n_seq ? n_seq : 1))))
+        return rc;
+    uint8_t *d_qmap = t_qmap.as<uint8_t>(), *d_seq_bad = t_seq_bad.as<uint8_t>();
+    uint64_t* d_seq_off = t_seq_off.as<uint64_t>();
     HC_HIP(hipMemcpyAsync(d_qmap, qmap, 256, hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(d_seq_off, sym_off.data(), sizeof(uint64_t) * n_seq, hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(t_rc_delta.p, rc_delta.data(), sizeof(uint32_t) * n_seq, hipMemcpyHostToDevice, c->stream));
-    HC_HIP(hipMemcpyAsync(c->d_lut, lut.data(), sizeof(double) * lut.size(), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(c->d_lut.p, lut.data(), sizeof(double) * lut.size(), hipMemcpyHostToDevice, c->stream));
     // 1.0 / n for every count a sub-overlap can reach (n <= positions rounded up to 16 <= the longest sequence + 15): the reference's
     // `1.0/total_len` (:137) as the host's IEEE division — the same quotient the device's gives — read by the kernel instead of divided
     uint32_t longest = 0;
@@ -436,10 +389,10 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
     std::vector<double> inv_n((size_t)longest + 17);
     inv_n[0] = std::numeric_limits<double>::infinity();
     for (size_t k = 1; k < inv_n.size(); k++) inv_n[k] = 1.0 / (double)k;
-    HC_HIP(hipMalloc((void**)&c->d_inv_n, sizeof(double) * inv_n.size()));
-    HC_HIP(hipMemcpyAsync(c->d_inv_n, inv_n.data(), sizeof(double) * inv_n.size(), hipMemcpyHostToDevice, c->stream));
-    HC_HIP(hc::launch_encode(symbytes, d_bases, d_quals, d_raw_off, d_seq_off, (const uint32_t*)t_rc_delta.p, d_qmap, n_seq, K, c->d_sym, d_seq_bad,
-                             d_first, n_reads, c->d_reads, slot_align, c->stream));
+    if ((rc = c->d_inv_n.ensure_exact(sizeof(double) * inv_n.size()))) return rc;
+    HC_HIP(hipMemcpyAsync(c->d_inv_n.p, inv_n.data(), sizeof(double) * inv_n.size(), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hc::launch_encode(symbytes, d_bases, d_quals, d_raw_off, d_seq_off, t_rc_delta.as<uint32_t>(), d_qmap, n_seq, K, c->d_sym.p, d_seq_bad,
+                             d_first, n_reads, c->d_reads.as<hc::ReadDesc>(), slot_align, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
 
     {  // SFO ids: singles, then every /1 mate, then every /2 mate (s_p1_p2.fasta, savage.py:643-664)
@@ -466,14 +419,14 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
             }
         }
     }
-    c->view.sym = c->d_sym;
-    c->view.reads = c->d_reads;
+    c->view.sym = c->d_sym.p;
+    c->view.reads = c->d_reads.as<hc::ReadDesc>();
     c->view.n_reads = n_reads;
     c->view.n_seq = n_seq;
     c->view.K = K;
     c->view.symbytes = symbytes;
     c->view.lut_bytes = (uint32_t)(lut.size() * sizeof(double));
-    c->view.inv_n = c->d_inv_n;
+    c->view.inv_n = c->d_inv_n.as<double>();
     c->view.inv_len = (uint32_t)inv_n.size();
     c->store_bytes = sym_bytes_total;
     c->view.store_bytes = sym_bytes_total;
@@ -492,7 +445,7 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
     if (c->view.regular && n_reads > 1) {  // the locality order of the reads (hc_locality.hip); only regular stores take the locality launch
         const size_t tmp = hc::locality_order_temp_bytes(n_reads);
         const size_t keys_bytes = 2 * sizeof(uint64_t) * (size_t)n_reads, idx_bytes = sizeof(uint32_t) * (((size_t)n_reads + 3) & ~(size_t)3);
-        int rc = c->loc_tmp.ensure(keys_bytes + idx_bytes + tmp);
+        rc = c->loc_tmp.ensure(keys_bytes + idx_bytes + tmp);
         if (rc == HC_OK) rc = c->loc_order.ensure(sizeof(uint32_t) * (size_t)n_reads);
         if (rc) return rc;
         uint64_t* keys = c->loc_tmp.as<uint64_t>();
@@ -650,18 +603,16 @@ static bool host_batch_is_ordered(const void* in, size_t rec_bytes, uint64_t n) 
     return share * 2 >= samples;
 }
 
+// the (key, index) radix sort's four arrays and its temporary storage, for n candidates: both new when the arrays are too small
 static int ensure_sort_workspace(hc_ctx* c, uint64_t n) {
-    if (n <= c->sort_cap) return HC_OK;
-    if (c->d_sort) (void)hipFree(c->d_sort);
-    if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
-    c->d_sort = nullptr;
-    c->d_sort_tmp = nullptr;
-    c->sort_cap = 0;
-    c->sort_tmp_bytes = hc::reorder_temp_bytes((uint32_t)n);
-    HC_HIP(hipMalloc((void**)&c->d_sort, 4 * n * sizeof(uint32_t)));
-    HC_HIP(hipMalloc(&c->d_sort_tmp, c->sort_tmp_bytes ? c->sort_tmp_bytes : 16));
-    c->sort_cap = n;
-    return HC_OK;
+    if (4 * n * sizeof(uint32_t) <= c->d_sort.cap) return HC_OK;
+    c->d_sort.release();
+    c->d_sort_tmp.release();
+    const size_t tmp = hc::reorder_temp_bytes((uint32_t)n);
+    int rc = c->d_sort.ensure_exact(4 * n * sizeof(uint32_t));
+    if (rc == HC_OK) rc = c->d_sort_tmp.ensure_exact(tmp ? tmp : 16);
+    if (rc) c->d_sort.release();  // (both or neither)
+    return rc;
 }
 
 }  // extern "C"
@@ -703,12 +654,13 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
     if (want_perm) {
         int rc = ensure_sort_workspace(c, n);
         if (rc) return rc;
-        uint32_t* keys_in = c->d_sort;
-        uint32_t* keys_out = c->d_sort + c->sort_cap;
-        uint32_t* idx_in = c->d_sort + 2 * c->sort_cap;
-        uint32_t* perm_out = c->d_sort + 3 * c->sort_cap;
-        HC_HIP(hc::launch_reorder(c->view.n_reads, fmt, d_in, (uint32_t)n, keys_in, keys_out, idx_in, perm_out, c->d_sort_tmp,
-                                  c->sort_tmp_bytes, s));
+        const size_t sort_cap = c->d_sort.cap / (4 * sizeof(uint32_t));
+        uint32_t* keys_in = c->d_sort.as<uint32_t>();
+        uint32_t* keys_out = keys_in + sort_cap;
+        uint32_t* idx_in = keys_in + 2 * sort_cap;
+        uint32_t* perm_out = keys_in + 3 * sort_cap;
+        HC_HIP(hc::launch_reorder(c->view.n_reads, fmt, d_in, (uint32_t)n, keys_in, keys_out, idx_in, perm_out, c->d_sort_tmp.p,
+                                  c->d_sort_tmp.cap, s));
         perm = perm_out;
     }
     const uint32_t* order_off = nullptr;
@@ -734,7 +686,7 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
     prm.n_dev = n_dev;
     prm.order_off = order_off;
     hc::ScoreBuffers buf{rows, row_count, cap, base_index, lines_in, lines_out};
-    buf.started = (rows && !lines_in) ? c->d_started : nullptr;  // workgroup starts counted for hc_comm_gate_device
+    buf.started = (rows && !lines_in) ? c->d_started.as<unsigned long long>() : nullptr;  // workgroup starts counted for hc_comm_gate_device
     if (plan.bucketed) {  // mixed sequence lengths: the launch buckets its candidates by length first
         hc_bucket_ws* ws = bucket ? bucket : &c->bucket;
         int rc = ws->ensure(n);
@@ -762,7 +714,7 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
         buf.spill_turn = &c->sink_turn;
     }
     uint32_t started_groups = 0;
-    const hipError_t le = hc::launch_score(plan, c->view, prm, c->d_lut, d_in, n, (hc_result_rec*)d_out, perm, buf, s, &started_groups);
+    const hipError_t le = hc::launch_score(plan, c->view, prm, c->d_lut.as<double>(), d_in, n, (hc_result_rec*)d_out, perm, buf, s, &started_groups);
     if (le != hipSuccess) {
         if (plan.segmented) c->sink_dirty = true;
         return hc::set_last_error(HC_ERR_HIP, std::string("launch_score: ") + hipGetErrorString(le));
@@ -837,15 +789,8 @@ int hc_synchronize(hc_ctx* c) {
 }
 
 static int ensure_workspace(hc_ctx* c, uint64_t n) {
-    if (n <= c->ws_cap) return HC_OK;
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_out) (void)hipFree(c->d_out);
-    c->d_in = c->d_out = nullptr;
-    c->ws_cap = 0;
-    HC_HIP(hipMalloc(&c->d_in, n * sizeof(hc_overlap_rec)));
-    HC_HIP(hipMalloc(&c->d_out, n * sizeof(hc_result_rec)));
-    c->ws_cap = n;
-    return HC_OK;
+    const int rc = c->d_in.ensure_exact(n * sizeof(hc_overlap_rec));
+    return rc ? rc : c->d_out.ensure_exact(n * sizeof(hc_result_rec));
 }
 
 static int score_host(hc_ctx* c, const char* who, uint32_t fmt, const void* in, uint64_t n, hc_result_rec* out) {
@@ -857,12 +802,12 @@ static int score_host(hc_ctx* c, const char* who, uint32_t fmt, const void* in, 
     int rc = ensure_workspace(c, n);
     if (rc) return rc;
     const size_t rb = fmt == HC_REC_COMPACT ? sizeof(hc_cand_rec) : sizeof(hc_overlap_rec);
-    HC_HIP(hipMemcpyAsync(c->d_in, in, n * rb, hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(c->d_in.p, in, n * rb, hipMemcpyHostToDevice, c->stream));
     bool reorder = c->reorder_mode == HC_REORDER_ALWAYS;
     if (c->reorder_mode == HC_REORDER_AUTO && n >= 4096) reorder = !host_batch_is_ordered(in, rb, n);
-    rc = hc_ctx_score(c, fmt, c->d_in, n, c->d_out, c->stream, reorder, nullptr, nullptr, 0, 0);
+    rc = hc_ctx_score(c, fmt, c->d_in.p, n, c->d_out.p, c->stream, reorder, nullptr, nullptr, 0, 0);
     if (rc) return rc;
-    HC_HIP(hipMemcpyAsync(out, c->d_out, n * sizeof(hc_result_rec), hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipMemcpyAsync(out, c->d_out.p, n * sizeof(hc_result_rec), hipMemcpyDeviceToHost, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
     return HC_OK;
 }
@@ -890,25 +835,10 @@ int hc_host_free(hc_ctx* c, void* ptr) {
 }
 
 static int ensure_compact_workspace(hc_ctx* c, uint64_t n, bool with_buffers) {
-    const size_t need = hc::compact_temp_bytes((uint32_t)n);
-    if (need > c->compact_tmp_bytes) {
-        if (c->d_compact_tmp) (void)hipFree(c->d_compact_tmp);
-        c->d_compact_tmp = nullptr;
-        c->compact_tmp_bytes = 0;
-        HC_HIP(hipMalloc(&c->d_compact_tmp, need));
-        c->compact_tmp_bytes = need;
-    }
-    if (with_buffers && n > c->compact_cap) {
-        if (c->d_compact_idx) (void)hipFree(c->d_compact_idx);
-        if (c->d_compact_res) (void)hipFree(c->d_compact_res);
-        c->d_compact_idx = nullptr;
-        c->d_compact_res = nullptr;
-        c->compact_cap = 0;
-        HC_HIP(hipMalloc((void**)&c->d_compact_idx, n * sizeof(uint32_t)));
-        HC_HIP(hipMalloc((void**)&c->d_compact_res, n * sizeof(hc_result_rec)));
-        c->compact_cap = n;
-    }
-    return HC_OK;
+    int rc = c->d_compact_tmp.ensure_exact(hc::compact_temp_bytes((uint32_t)n));
+    if (rc == HC_OK && with_buffers) rc = c->d_compact_idx.ensure_exact(n * sizeof(uint32_t));
+    if (rc == HC_OK && with_buffers) rc = c->d_compact_res.ensure_exact(n * sizeof(hc_result_rec));
+    return rc;
 }
 
 int hc_reset(hc_ctx* c, const hc_settings* settings) {
@@ -916,7 +846,7 @@ int hc_reset(hc_ctx* c, const hc_settings* settings) {
     if (settings->device != c->device) return fail(HC_ERR_ARG, "hc_reset: a context stays on its device");
     HC_HIP(hipSetDevice(c->device));
     HC_HIP(hipDeviceSynchronize());  // nothing of the previous stage is in flight
-    free_store(c, false);            // the read store, the finder's results, the id table's validity: as after hc_create (the scratch stays)
+    free_store(c);                   // the read store, the finder's results, the id table's validity: as after hc_create (the scratch stays)
     c->have_ids = false;
     c->reorder_mode = HC_REORDER_AUTO;
     c->graph.valid = false;
@@ -929,9 +859,9 @@ int hc_set_comm_reserve(hc_ctx* c, uint32_t cus) {
     if (!c) return fail(HC_ERR_ARG, "hc_set_comm_reserve: null context");
     if (cus >= c->n_cu) return fail(HC_ERR_ARG, "hc_set_comm_reserve: more CUs than the device has");
     HC_HIP(hipSetDevice(c->device));
-    if (cus && !c->d_started) {
-        HC_HIP(hipMalloc((void**)&c->d_started, sizeof(unsigned long long)));
-        HC_HIP(hipMemset(c->d_started, 0, sizeof(unsigned long long)));
+    if (cus && !c->d_started.p) {
+        if (const int rc = c->d_started.ensure_exact(sizeof(unsigned long long))) return rc;
+        HC_HIP(hipMemset(c->d_started.p, 0, sizeof(unsigned long long)));
         c->started_target = 0;
     }
     c->comm_reserve = cus;
@@ -940,9 +870,9 @@ int hc_set_comm_reserve(hc_ctx* c, uint32_t cus) {
 
 int hc_comm_gate_device(hc_ctx* c, void* hip_stream, uint32_t timeout_us) {
     if (!c) return fail(HC_ERR_ARG, "hc_comm_gate_device: null context");
-    if (!c->d_started) return HC_OK;  // nothing is counted: nothing to wait for
+    if (!c->d_started.p) return HC_OK;  // nothing is counted: nothing to wait for
     HC_HIP(hipSetDevice(c->device));
-    HC_HIP(hc::launch_comm_gate(c->d_started, c->started_target, timeout_us ? timeout_us : 2000u, hip_stream ? (hipStream_t)hip_stream : c->stream));
+    HC_HIP(hc::launch_comm_gate(c->d_started.as<unsigned long long>(), c->started_target, timeout_us ? timeout_us : 2000u, hip_stream ? (hipStream_t)hip_stream : c->stream));
     return HC_OK;
 }
 
@@ -959,7 +889,7 @@ int hc_compact_device(hc_ctx* c, const void* d_results, uint64_t n, void* d_indi
     int rc = ensure_compact_workspace(c, n, false);
     if (rc) return rc;
     HC_HIP(hc::launch_compact((const hc_result_rec*)d_results, (uint32_t)n, (uint32_t*)d_indices, (unsigned long long*)d_count,
-                              c->d_compact_tmp, c->compact_tmp_bytes, s));
+                              c->d_compact_tmp.p, c->d_compact_tmp.cap, s));
     return HC_OK;
 }
 
@@ -1023,23 +953,24 @@ int hc_score_batch_compact(hc_ctx* c, const hc_overlap_rec* in, uint64_t n, uint
     if (rc) return rc;
     rc = ensure_compact_workspace(c, n, true);
     if (rc) return rc;
-    HC_HIP(hipMemcpyAsync(c->d_in, in, n * sizeof(hc_overlap_rec), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(c->d_in.p, in, n * sizeof(hc_overlap_rec), hipMemcpyHostToDevice, c->stream));
     bool reorder = c->reorder_mode == HC_REORDER_ALWAYS;
     if (c->reorder_mode == HC_REORDER_AUTO && n >= 4096) reorder = !host_batch_is_ordered(in, sizeof(hc_overlap_rec), n);
-    rc = hc_ctx_score(c, HC_REC_FULL, c->d_in, n, c->d_out, c->stream, reorder, nullptr, nullptr, 0, 0);
+    rc = hc_ctx_score(c, HC_REC_FULL, c->d_in.p, n, c->d_out.p, c->stream, reorder, nullptr, nullptr, 0, 0);
     if (rc) return rc;
-    HC_HIP(hc::launch_compact((const hc_result_rec*)c->d_out, (uint32_t)n, c->d_compact_idx, c->d_totals, c->d_compact_tmp,
-                              c->compact_tmp_bytes, c->stream));
-    HC_HIP(hc::launch_gather_results((const hc_result_rec*)c->d_out, c->d_compact_idx, c->d_totals, c->d_compact_res, c->n_cu,
-                                     c->stream));
+    unsigned long long* d_k = c->d_totals.as<unsigned long long>();
+    HC_HIP(hc::launch_compact(c->d_out.as<hc_result_rec>(), (uint32_t)n, c->d_compact_idx.as<uint32_t>(), d_k, c->d_compact_tmp.p,
+                              c->d_compact_tmp.cap, c->stream));
+    HC_HIP(hc::launch_gather_results(c->d_out.as<hc_result_rec>(), c->d_compact_idx.as<uint32_t>(), d_k, c->d_compact_res.as<hc_result_rec>(),
+                                     c->n_cu, c->stream));
     unsigned long long k = 0;
-    HC_HIP(hipMemcpyAsync(&k, c->d_totals, sizeof k, hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipMemcpyAsync(&k, d_k, sizeof k, hipMemcpyDeviceToHost, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
     *n_out = k;
     if (k > cap) return fail(HC_ERR_ARG, "hc_score_batch_compact: output capacity too small");
     if (k) {
-        HC_HIP(hipMemcpyAsync(idx_out, c->d_compact_idx, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HC_HIP(hipMemcpyAsync(res_out, c->d_compact_res, k * sizeof(hc_result_rec), hipMemcpyDeviceToHost, c->stream));
+        HC_HIP(hipMemcpyAsync(idx_out, c->d_compact_idx.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HC_HIP(hipMemcpyAsync(res_out, c->d_compact_res.p, k * sizeof(hc_result_rec), hipMemcpyDeviceToHost, c->stream));
         HC_HIP(hipStreamSynchronize(c->stream));
     }
     return HC_OK;
@@ -1068,10 +999,10 @@ int hc_count_positions_device(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_
         return fail(HC_ERR_ARG, "hc_count_positions_device: bad argument");
     if (!c->have_reads) return fail(HC_ERR_STATE, "hc_count_positions_device: hc_set_reads has not been called");
     HC_HIP(hipSetDevice(c->device));
-    HC_HIP(hipMemsetAsync(c->d_totals, 0, 2 * sizeof(unsigned long long), c->stream));
-    HC_HIP(hc::launch_count_positions(c->view, c->params.min_read_len, fmt, d_in, n, c->d_totals, c->stream));
+    HC_HIP(hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    HC_HIP(hc::launch_count_positions(c->view, c->params.min_read_len, fmt, d_in, n, c->d_totals.as<unsigned long long>(), c->stream));
     unsigned long long h[2] = {0, 0};
-    HC_HIP(hipMemcpyAsync(h, c->d_totals, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipMemcpyAsync(h, c->d_totals.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
     *total_positions = h[0];
     *total_subs = h[1];

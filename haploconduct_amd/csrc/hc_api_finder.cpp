@@ -33,14 +33,10 @@ static int fail(int status, const std::string& what) { return hc::set_last_error
 namespace {
 // A view of one of the context's grow-only scratch slots (hc_ctx::finder_scratch).  The overlap finder needs
 // gigabytes of scratch per call; allocating and freeing them every call (hipMalloc/hipFree or the stream-ordered
-// pool alike) costs several times its kernels, so the blocks stay with the context until the store is replaced.
+// pool alike) costs several times its kernels, so the blocks stay with the context.
 struct DevBuf {
     void* p = nullptr;
-    hc_ctx::Scratch* slot = nullptr;
-    void* own = nullptr;  // a block that is not a slot (the result, which outlives the call)
-    ~DevBuf() {
-        if (own) (void)hipFree(own);
-    }
+    hc_scratch* slot = nullptr;
     template <typename T>
     T* as() const { return (T*)p; }
 };
@@ -50,14 +46,9 @@ struct DevBuf {
 // the second set is full.
 struct IngestScratch {
     hc_ctx* c;
-    std::vector<hc_ctx::Scratch*> idle;
-    std::vector<void*> mine;  // freed with the pool
+    std::vector<hc_scratch*> idle;
+    std::vector<hc_scratch> mine;  // freed with the pool
     unsigned n_own = 0;
-    IngestScratch(const IngestScratch&) = delete;
-    IngestScratch& operator=(const IngestScratch&) = delete;
-    ~IngestScratch() {
-        for (void* q : mine) (void)hipFree(q);
-    }
     explicit IngestScratch(hc_ctx* ctx) : c(ctx) {
         for (auto& sl : c->finder_scratch)
             if (sl.p) idle.push_back(&sl);
@@ -82,7 +73,7 @@ struct IngestScratch {
             return hipSuccess;
         }
         while (n_own < 12 && c->ingest_scratch[n_own].p) n_own++;  // an empty slot of the second set
-        hc_ctx::Scratch* sl = nullptr;
+        hc_scratch* sl = nullptr;
         how = "a new block of the second set";
         if (n_own < 12) {
             sl = &c->ingest_scratch[n_own];
@@ -94,62 +85,27 @@ struct IngestScratch {
                     (small < 0 || idle[i]->cap < idle[(size_t)small]->cap))
                     small = (int)i;
             if (small < 0) {  // (every block of the second set is handed out: a block of this call's own)
-                void* q = nullptr;
-                const hipError_t e = hipMalloc(&q, need);
+                hc_scratch q;
+                const hipError_t e = q.alloc(need);
                 if (e != hipSuccess) return e;
-                mine.push_back(q);
-                *p = q;
+                *p = q.p;
+                mine.push_back(std::move(q));
                 how = "a block of this call's own (hipMalloc + hipFree)";
                 return hipSuccess;
             }
             sl = idle[(size_t)small];
             idle[(size_t)small] = nullptr;
             how = "the smallest idle block of the second set regrown (hipFree + hipMalloc)";
-            (void)hipFree(sl->p);
-            sl->p = nullptr;
-            sl->cap = 0;
         }
-        const hipError_t e = hipMalloc(&sl->p, need);
-        if (e != hipSuccess) {
-            sl->p = nullptr;
-            return e;
-        }
-        sl->cap = need;
+        const hipError_t e = sl->alloc(need);
         *p = sl->p;
-        return hipSuccess;
+        return e;
     }
 };
 }  // namespace
 
-#define HC_ALLOC(buf, bytes)                                                                  \
-    do {                                                                                      \
-        hc_ctx::Scratch& sl__ = c->finder_scratch[n_slots++];                                 \
-        const size_t need__ = (bytes) ? (size_t)(bytes) : 16;                                 \
-        if (sl__.cap < need__) {                                                              \
-            if (sl__.p) (void)hipFree(sl__.p);                                                \
-            sl__.p = nullptr;                                                                 \
-            sl__.cap = 0;                                                                     \
-            HC_HIP(hipMalloc(&sl__.p, need__ + need__ / 8));                                  \
-            sl__.cap = need__ + need__ / 8;                                                   \
-        }                                                                                     \
-        (buf).slot = &sl__;                                                                   \
-        (buf).p = sl__.p;                                                                     \
-    } while (0)
-
-// the temporary storage of the library calls: the slot keeps what earlier calls grew it to
-#define HC_GROW_TMP(bytes)                                        \
-    do {                                                          \
-        if ((bytes) > d_tmp.slot->cap) {                          \
-            HC_HIP(hipStreamSynchronize(st));                     \
-            (void)hipFree(d_tmp.slot->p);                         \
-            d_tmp.slot->p = nullptr;                              \
-            d_tmp.slot->cap = 0;                                  \
-            HC_HIP(hipMalloc(&d_tmp.slot->p, (bytes)));           \
-            d_tmp.slot->cap = (bytes);                            \
-            d_tmp.p = d_tmp.slot->p;                              \
-        }                                                         \
-        tmp_bytes = d_tmp.slot->cap;                              \
-    } while (0)
+// room for `records` found records in the context's grow-only result block (contents are not kept)
+static int found_room(hc_ctx* c, uint64_t records) { return c->d_found.ensure_exact(records * sizeof(hc_sfo_rec)); }
 
 extern "C" {
 
@@ -190,14 +146,13 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     if (!recompute && c->found_valid && c->found_err == err_rate && c->found_min == min_overlap && c->found_flags == flags) {
         *n_out = c->n_found;
         const uint64_t take = c->n_found < cap ? c->n_found : cap;
-        if (take) HC_HIP(hipMemcpy(out, c->d_found, take * sizeof(hc_sfo_rec), hipMemcpyDeviceToHost));
+        if (take) HC_HIP(hipMemcpy(out, c->d_found.p, take * sizeof(hc_sfo_rec), hipMemcpyDeviceToHost));
         return HC_OK;
     }
     c->n_found = 0;  // (the previous result's buffer stays: grow-only — asking the driver for 2 GB per call cost 0.3 - 0.4 s from the second call on)
     c->found_valid = false;
     lap("free previous result");
-    auto remember = [&](hc_sfo_rec* d, uint64_t n) {
-        if (d) c->d_found = d;
+    auto remember = [&](uint64_t n) {
         c->n_found = n;
         c->found_err = err_rate;
         c->found_min = min_overlap;
@@ -218,7 +173,14 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     const uint32_t n_ori = (flags & HC_FIND_REVERSALS) ? 2u : 1u;
     const bool wide = c->view.symbytes == 1 && hc::lut_lg(c->view.K) >= 6;
     hipStream_t st = c->stream;
-    unsigned n_slots = 0;  // HC_ALLOC takes the context's scratch slots in order
+    unsigned n_slots = 0;
+    int rc;
+    auto alloc = [&](DevBuf& buf, size_t bytes) {  // the context's scratch slots, in order, with an eighth of headroom when one has to grow
+        buf.slot = &c->finder_scratch[n_slots++];
+        const int r = buf.slot->ensure(bytes ? bytes : 16);
+        buf.p = buf.slot->p;
+        return r;
+    };
 
     // host-side layout of the index and of the seeds
     std::vector<uint64_t> pos_start(n_seq + 1, 0), seed_start(n_seq + 1, 0);
@@ -233,12 +195,12 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     if (P >= (1ull << 31) || S >= (1ull << 31)) return fail(HC_ERR_ARG, "hc_find_overlaps: read set too large for one call (2^31 positions)");
 
     DevBuf d_idlen, d_seqs, d_by_sfo, d_pos_start, d_seed_start, d_k0, d_k1, d_v0, d_v1, d_tmp, d_lo, d_cnt, d_off, d_count;
-    HC_ALLOC(d_seqs, n_seq * sizeof(hc::SeqRef));
-    HC_ALLOC(d_by_sfo, n_seq * sizeof(hc::SeqRef));
-    HC_ALLOC(d_idlen, n_seq * sizeof(uint2));
-    HC_ALLOC(d_pos_start, (n_seq + 1) * sizeof(uint64_t));
-    HC_ALLOC(d_seed_start, (n_seq + 1) * sizeof(uint64_t));
-    HC_ALLOC(d_count, sizeof(unsigned long long));
+    if ((rc = alloc(d_seqs, n_seq * sizeof(hc::SeqRef)))) return rc;
+    if ((rc = alloc(d_by_sfo, n_seq * sizeof(hc::SeqRef)))) return rc;
+    if ((rc = alloc(d_idlen, n_seq * sizeof(uint2)))) return rc;
+    if ((rc = alloc(d_pos_start, (n_seq + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = alloc(d_seed_start, (n_seq + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = alloc(d_count, sizeof(unsigned long long)))) return rc;
     HC_HIP(hipMemcpyAsync(d_seqs.p, c->seq_refs.data(), n_seq * sizeof(hc::SeqRef), hipMemcpyHostToDevice, st));
     HC_HIP(hipMemcpyAsync(d_by_sfo.p, by_sfo.data(), n_seq * sizeof(hc::SeqRef), hipMemcpyHostToDevice, st));
     std::vector<uint2> idlen(n_seq);  // what a seed hit asks of the indexed sequence: 8 bytes instead of a SeqRef
@@ -248,35 +210,45 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     HC_HIP(hipMemcpyAsync(d_seed_start.p, seed_start.data(), (n_seq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 
     // 1. index: (k-mer, sequence|position) of every forward position, sorted by k-mer
-    HC_ALLOC(d_k0, P * 8);
-    HC_ALLOC(d_k1, P * 8);
-    HC_ALLOC(d_v0, P * 8);
-    HC_ALLOC(d_v1, P * 8);
-    HC_HIP(hc::finder_index(c->d_sym, c->view.symbytes, wide, d_seqs.as<hc::SeqRef>(), d_pos_start.as<uint64_t>(), n_seq, k, d_k0.as<uint64_t>(),
+    if ((rc = alloc(d_k0, P * 8))) return rc;
+    if ((rc = alloc(d_k1, P * 8))) return rc;
+    if ((rc = alloc(d_v0, P * 8))) return rc;
+    if ((rc = alloc(d_v1, P * 8))) return rc;
+    HC_HIP(hc::finder_index(c->d_sym.p, c->view.symbytes, wide, d_seqs.as<hc::SeqRef>(), d_pos_start.as<uint64_t>(), n_seq, k, d_k0.as<uint64_t>(),
                             d_v0.as<uint64_t>(), st));
     size_t tmp_bytes = 0;
+    // the temporary storage of the library calls: the slot keeps what earlier calls grew it to
+    auto grow_tmp = [&](size_t bytes) -> int {
+        if (bytes > d_tmp.slot->cap) {
+            HC_HIP(hipStreamSynchronize(st));  // (the old block is in use until then)
+            if (const int r = d_tmp.slot->ensure_exact(bytes)) return r;
+            d_tmp.p = d_tmp.slot->p;
+        }
+        tmp_bytes = d_tmp.slot->cap;
+        return HC_OK;
+    };
     HC_HIP(hc::finder_sort_pairs(nullptr, tmp_bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), d_v0.as<uint64_t>(), d_v1.as<uint64_t>(), P, 64, st));
-    HC_ALLOC(d_tmp, tmp_bytes);
+    if ((rc = alloc(d_tmp, tmp_bytes))) return rc;
     tmp_bytes = d_tmp.slot->cap;
     HC_HIP(hc::finder_sort_pairs(d_tmp.p, tmp_bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), d_v0.as<uint64_t>(), d_v1.as<uint64_t>(), P, 64, st));
     lap("index + sort");
     // 2. seeds: range of every seed k-mer in the index
-    HC_ALLOC(d_lo, S * 8);
-    HC_ALLOC(d_cnt, (S + 1) * 8);
-    HC_ALLOC(d_off, (S + 1) * 8);
+    if ((rc = alloc(d_lo, S * 8))) return rc;
+    if ((rc = alloc(d_cnt, (S + 1) * 8))) return rc;
+    if ((rc = alloc(d_off, (S + 1) * 8))) return rc;
     HC_HIP(hipMemsetAsync(d_cnt.p, 0, (S + 1) * 8, st));
-    HC_HIP(hc::finder_seeds(c->d_sym, c->view.symbytes, wide, d_seqs.as<hc::SeqRef>(), d_seed_start.as<uint64_t>(), n_seq, k, s, n_ori,
+    HC_HIP(hc::finder_seeds(c->d_sym.p, c->view.symbytes, wide, d_seqs.as<hc::SeqRef>(), d_seed_start.as<uint64_t>(), n_seq, k, s, n_ori,
                             d_k1.as<uint64_t>(), P, d_lo.as<uint64_t>(), d_cnt.as<uint64_t>(), st));
     // only hits whose indexed sequence has the lower id become candidates: count those, and lay the keys out by them
     DevBuf d_val;
-    HC_ALLOC(d_val, (S + 1) * 8);
+    if ((rc = alloc(d_val, (S + 1) * 8))) return rc;
     HC_HIP(hipMemsetAsync(d_val.p, 0, (S + 1) * 8, st));
     HC_HIP(hc::finder_count_valid(d_seqs.as<hc::SeqRef>(), d_idlen.as<uint2>(), d_seed_start.as<uint64_t>(), n_seq, k, s, n_ori, d_v1.as<uint64_t>(),
                                   d_lo.as<uint64_t>(), d_cnt.as<uint64_t>(), min_overlap, flags, d_val.as<uint64_t>(), st));
     {
         size_t b = 0;
         HC_HIP(hc::finder_scan(nullptr, b, d_val.as<uint64_t>(), d_off.as<uint64_t>(), S + 1, st));
-        HC_GROW_TMP(b);
+        if ((rc = grow_tmp(b))) return rc;
         HC_HIP(hc::finder_scan(d_tmp.p, b, d_val.as<uint64_t>(), d_off.as<uint64_t>(), S + 1, st));
     }
     uint64_t H = 0;  // number of candidate hits = last element of the exclusive scan over S + 1 counts (the extra one is 0)
@@ -284,7 +256,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     HC_HIP(hipStreamSynchronize(st));
     lap("seeds + scan");
     if (H == 0) {
-        remember(nullptr, 0);
+        remember(0);
         return HC_OK;
     }
     // 3./4. in batches of seed sequences, so that the hits in flight stay bounded whatever the coverage of the data:
@@ -294,7 +266,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     std::vector<uint64_t> h_bound(n_seq + 1);  // candidate hits before sequence q = off[seed_start[q]]
     {
         DevBuf d_bound;
-        HC_ALLOC(d_bound, (n_seq + 1) * 8);
+        if ((rc = alloc(d_bound, (n_seq + 1) * 8))) return rc;
         HC_HIP(hc::finder_boundaries(d_off.as<uint64_t>(), d_seed_start.as<uint64_t>(), n_seq + 1, d_bound.as<uint64_t>(), st));
         HC_HIP(hipMemcpyAsync(h_bound.data(), d_bound.p, (n_seq + 1) * 8, hipMemcpyDeviceToHost, st));
         HC_HIP(hipStreamSynchronize(st));
@@ -324,11 +296,11 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
         q0 = q1;
     }
     DevBuf d_h0, d_h1, d_kout, d_flag, d_pos, d_r1;
-    HC_ALLOC(d_h0, Hmax * 8);
-    HC_ALLOC(d_h1, Hmax * 8);
-    HC_ALLOC(d_kout, Hmax * 4);
-    HC_ALLOC(d_flag, (Hmax + 1) * 4);
-    HC_ALLOC(d_pos, (Hmax + 1) * 4);
+    if ((rc = alloc(d_h0, Hmax * 8))) return rc;
+    if ((rc = alloc(d_h1, Hmax * 8))) return rc;
+    if ((rc = alloc(d_kout, Hmax * 4))) return rc;
+    if ((rc = alloc(d_flag, (Hmax + 1) * 4))) return rc;
+    if ((rc = alloc(d_pos, (Hmax + 1) * 4))) return rc;
     {
         size_t b = 0, b2 = 0, b3 = 0;
         HC_HIP(hc::finder_sort_keys(nullptr, b, d_h0.as<uint64_t>(), d_h1.as<uint64_t>(), Hmax, st));
@@ -336,7 +308,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
         HC_HIP(hc::finder_scan32(nullptr, b3, d_flag.as<uint32_t>(), d_pos.as<uint32_t>(), Hmax + 1, st));
         b = b2 > b ? b2 : b;
         b = b3 > b ? b3 : b;
-        HC_GROW_TMP(b);
+        if ((rc = grow_tmp(b))) return rc;
     }
     HC_HIP(hipStreamSynchronize(st));
     lap("scratch for the batches");
@@ -344,8 +316,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     // the records of the batches collect in one more grow-only slot (growing keeps what is in it); the result that
     // outlives the call is allocated once, at the end, at its size: one hipMalloc and (for the previous result) one hipFree
     // per call — allocating and freeing gigabytes per batch and for the final sort cost more than the kernels on some hosts
-    hc_ctx::Scratch& acc = c->finder_scratch[n_slots++];
-    size_t res_cap = acc.cap / sizeof(hc_sfo_rec);  // records
+    hc_scratch& acc = c->finder_scratch[n_slots++];
     for (const Batch& bt : batches) {
         const uint64_t Hb = bt.hits;
         HC_HIP(hc::finder_expand(d_seqs.as<hc::SeqRef>(), d_idlen.as<uint2>(), d_seed_start.as<uint64_t>(), bt.q0, bt.q1, bt.base, k, s, n_ori, d_v1.as<uint64_t>(),
@@ -359,7 +330,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
         HC_HIP(hipStreamSynchronize(st));
         if (M == 0) continue;
         HC_HIP(hipMemsetAsync(d_flag.as<uint32_t>() + M, 0, 4, st));
-        HC_HIP(hc::finder_verify(c->d_sym, c->view.symbytes, wide, d_by_sfo.as<hc::SeqRef>(), d_h0.as<uint64_t>(), M, err_rate, min_overlap, flags,
+        HC_HIP(hc::finder_verify(c->d_sym.p, c->view.symbytes, wide, d_by_sfo.as<hc::SeqRef>(), d_h0.as<uint64_t>(), M, err_rate, min_overlap, flags,
                                  d_kout.as<uint32_t>(), d_flag.as<uint32_t>(), st));
         bs = tmp_bytes;
         HC_HIP(hc::finder_scan32(d_tmp.p, bs, d_flag.as<uint32_t>(), d_pos.as<uint32_t>(), M + 1, st));
@@ -367,18 +338,11 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
         HC_HIP(hipMemcpyAsync(&Rb, d_pos.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost, st));
         HC_HIP(hipStreamSynchronize(st));
         if (Rb == 0) continue;
-        if (R + Rb > res_cap) {
+        if (const size_t res_cap = acc.cap / sizeof(hc_sfo_rec); R + Rb > res_cap) {  // (records)
             size_t want = res_cap ? res_cap * 2 : (size_t)Rb;
             if (want < R + Rb) want = R + Rb;
             if (batches.size() == 1) want = Rb;
-            void* bigger = nullptr;
-            HC_HIP(hipMalloc(&bigger, want * sizeof(hc_sfo_rec)));
-            if (R) HC_HIP(hipMemcpyAsync(bigger, acc.p, R * sizeof(hc_sfo_rec), hipMemcpyDeviceToDevice, st));
-            HC_HIP(hipStreamSynchronize(st));
-            if (acc.p) (void)hipFree(acc.p);
-            acc.p = bigger;
-            acc.cap = want * sizeof(hc_sfo_rec);
-            res_cap = want;
+            if ((rc = acc.grow_keep(want * sizeof(hc_sfo_rec), R * sizeof(hc_sfo_rec), st))) return rc;
         }
         HC_HIP(hc::finder_emit(d_by_sfo.as<hc::SeqRef>(), d_h0.as<uint64_t>(), d_kout.as<uint32_t>(), d_flag.as<uint32_t>(), d_pos.as<uint32_t>(), M,
                                (hc_sfo_rec*)acc.p + R, st));
@@ -387,28 +351,23 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     HC_HIP(hipStreamSynchronize(st));
     lap("expand/sort/unique/verify/emit");
     if (R == 0) {
-        remember(nullptr, 0);
+        remember(0);
         return HC_OK;
     }
     if (R >= (1ull << 31)) return fail(HC_ERR_ARG, "hc_find_overlaps: more than 2^31 overlaps");
-    if (!c->d_found || c->found_cap < R) {  // the result: the context's until the next call (grow-only)
-        if (c->d_found) (void)hipFree(c->d_found);
-        c->d_found = nullptr;
-        c->found_cap = 0;
-        HC_HIP(hipMalloc((void**)&c->d_found, (R + R / 8) * sizeof(hc_sfo_rec)));
-        c->found_cap = R + R / 8;
-    }
-    d_r1.p = c->d_found;
+    // the result: the context's until the next call (grow-only, with an eighth of headroom when it has to grow)
+    if (c->d_found.cap < R * sizeof(hc_sfo_rec) && (rc = found_room(c, R + R / 8))) return rc;
+    d_r1.p = c->d_found.p;
     if (batches.size() > 1) {  // every batch is sorted; one more sort (key, position) + gather for the global order
         // the batches' buffers are idle now: they hold the keys and positions of this sort when they are large enough
-        DevBuf own[4];  // what they cannot hold; freed on every return path
-        auto room = [&](const DevBuf& idle, size_t bytes, DevBuf& fallback, void** p) -> hipError_t {
+        hc_scratch own[4];  // what they cannot hold; freed on every return path
+        auto room = [&](const DevBuf& idle, size_t bytes, hc_scratch& fallback, void** p) -> hipError_t {
             if (idle.slot && idle.slot->cap >= bytes) {
                 *p = idle.slot->p;
                 return hipSuccess;
             }
-            const hipError_t e = hipMalloc(&fallback.own, bytes ? bytes : 16);
-            *p = fallback.own;
+            const hipError_t e = fallback.alloc(bytes ? bytes : 16);
+            *p = fallback.p;
             return e;
         };
         void *sk0 = nullptr, *sk1 = nullptr, *si0 = nullptr, *si1 = nullptr, *stmp = nullptr;
@@ -423,7 +382,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
             stmp = d_pos.slot->p;
         } else {  // (a gigabyte at config 3's size: one more grow-only slot, not a block of this call's own)
             DevBuf d_stmp;
-            HC_ALLOC(d_stmp, b);
+            if ((rc = alloc(d_stmp, b))) return rc;
             stmp = d_stmp.p;
         }
         HC_HIP(hc::finder_sort_pairs(stmp, b, (uint64_t*)sk0, (uint64_t*)sk1, (uint64_t*)si0, (uint64_t*)si1, R, 64, st));
@@ -438,7 +397,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     const uint64_t take = R < cap ? R : cap;
     if (take) HC_HIP(hc::copy_to_pageable_host(out, d_r1.p, take * sizeof(hc_sfo_rec)));
     lap("copy to host");
-    remember((hc_sfo_rec*)d_r1.p, R);
+    remember(R);
     return HC_OK;
 }
 
@@ -486,7 +445,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
             HC_HIP(hipMemsetAsync(d_status, 0, 8, st));
             HC_HIP(hipStreamSynchronize(st));
             const double t_alloc = now();
-            HC_HIP(hc::sfo_flip(c->d_found, n, num_singles, num_pairs, d_flip, d_k[0], d_k[1], d_k[2], d_pa, d_status, st));
+            HC_HIP(hc::sfo_flip(c->d_found.as<hc_sfo_rec>(), n, num_singles, num_pairs, d_flip, d_k[0], d_k[1], d_k[2], d_pa, d_status, st));
             uint32_t *perm = d_pa, *perm_next = d_pb;
             for (int ch = 0; ch < 3; ch++) {  // least significant 64 bits first; every sort is stable
                 const uint64_t* keys = d_k[ch];
@@ -531,10 +490,8 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
             const uint64_t ring = 2u << 20;  // records per buffer of the ring: 64 MiB
             uint64_t chunk = ring;            // records per copy (HC_SFO_CHUNK: test knob, small chunks on small inputs)
             if (const char* e = getenv("HC_SFO_CHUNK")) chunk = std::min<uint64_t>(ring, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-            if (!c->h_ingest[0]) {
-                for (int t = 0; t < 2; t++) HC_HIP(hipHostMalloc(&c->h_ingest[t], ring * sizeof(hc::SfoFlipped), hipHostMallocDefault));
-                c->h_ingest_cap = ring * sizeof(hc::SfoFlipped);
-            }
+            for (hc_scratch& h : c->h_ingest)
+                if (const int rc = h.ensure_exact(ring * sizeof(hc::SfoFlipped))) return rc;
             HC_HIP(hipStreamSynchronize(st));
             const double t1 = now();
             if (!status) {
@@ -542,13 +499,13 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
                 hc::SfoSortedMatcher matcher((long)num_singles, (long)num_pairs);
                 const uint64_t n_chunks = (n_out + chunk - 1) / chunk;
                 auto count_of = [&](uint64_t j) { return std::min(chunk, n_out - j * chunk); };
-                if (n_out) HC_HIP(hipMemcpyAsync(c->h_ingest[0], d_send, count_of(0) * sizeof(hc::SfoFlipped), hipMemcpyDeviceToHost, st));
+                if (n_out) HC_HIP(hipMemcpyAsync(c->h_ingest[0].p, d_send, count_of(0) * sizeof(hc::SfoFlipped), hipMemcpyDeviceToHost, st));
                 for (uint64_t j = 0; j < n_chunks; j++) {
                     HC_HIP(hipStreamSynchronize(st));  // chunk j has arrived
                     if (j + 1 < n_chunks)
-                        HC_HIP(hipMemcpyAsync(c->h_ingest[(j + 1) & 1], d_send + (j + 1) * chunk, count_of(j + 1) * sizeof(hc::SfoFlipped),
+                        HC_HIP(hipMemcpyAsync(c->h_ingest[(j + 1) & 1].p, d_send + (j + 1) * chunk, count_of(j + 1) * sizeof(hc::SfoFlipped),
                                               hipMemcpyDeviceToHost, st));
-                    matcher.feed((const hc::SfoFlipped*)c->h_ingest[j & 1], count_of(j));
+                    matcher.feed(c->h_ingest[j & 1].as<hc::SfoFlipped>(), count_of(j));
                 }
                 const double t2 = now();
                 text = matcher.finish(k);
@@ -561,7 +518,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
         if (!sorted_on_device) {  // nothing found, an id or a number the device's keys do not hold: the host path sorts, and reports
             mem.host = malloc(n ? n * sizeof(hc_sfo_rec) : 16);
             if (!mem.host) return fail(HC_ERR_NOMEM, "hc_found_to_overlaps: out of host memory");
-            if (n) HC_HIP(hipMemcpy(mem.host, c->d_found, n * sizeof(hc_sfo_rec), hipMemcpyDeviceToHost));
+            if (n) HC_HIP(hipMemcpy(mem.host, c->d_found.p, n * sizeof(hc_sfo_rec), hipMemcpyDeviceToHost));
             text = hc::sfo_records_to_overlaps((const hc_sfo_rec*)mem.host, n, (long)num_singles, (long)num_pairs, k);
         }
         if (n_lines) *n_lines = k;
@@ -613,7 +570,7 @@ int hc_found_to_lines_device(hc_ctx* c, uint64_t num_singles, uint64_t num_pairs
     HC_HIP(dmalloc(tmp_bytes, &d_tmp));
     HC_HIP(hipMemsetAsync(d_status, 0, 64, st));
     // flip + the script's sort (three stable radix sorts over the 192-bit key), as hc_found_to_overlaps does
-    HC_HIP(hc::sfo_flip(c->d_found, n, num_singles, num_pairs, d_flip, d_k[0], d_k[1], d_k[2], d_pa, d_status, st));
+    HC_HIP(hc::sfo_flip(c->d_found.as<hc_sfo_rec>(), n, num_singles, num_pairs, d_flip, d_k[0], d_k[1], d_k[2], d_pa, d_status, st));
     uint32_t *perm = d_pa, *perm_next = d_pb;
     for (int ch = 0; ch < 3; ch++) {
         const uint64_t* keys = d_k[ch];
@@ -656,13 +613,8 @@ int hc_found_to_lines_device(hc_ctx* c, uint64_t num_singles, uint64_t num_pairs
     HC_HIP(hipStreamSynchronize(st));
     if (host[0]) return fail(HC_ERR_NOT_ON_DEVICE, "hc_found_to_lines_device: not on the device (an assert of the script's matching, or thousands of lines for one pair of reads)");
     const uint64_t total = total32;
-    if (total > c->found_lines_cap) {
-        if (c->d_found_lines) (void)hipFree(c->d_found_lines);
-        c->d_found_lines = nullptr;
-        c->found_lines_cap = 0;
-        HC_HIP(hipMalloc((void**)&c->d_found_lines, (total + total / 16 + 1024) * sizeof(hc_line_rec)));
-        c->found_lines_cap = total + total / 16 + 1024;
-    }
+    if (total * sizeof(hc_line_rec) > c->d_found_lines.cap)
+        if (const int rc = c->d_found_lines.ensure_exact((total + total / 16 + 1024) * sizeof(hc_line_rec))) return rc;
     if (total == 0) return HC_OK;
     // the lines go to scratch first (the sorted records' keys are spent), the script's last `uniq` decides what stays
     hc_line_rec* d_raw = nullptr;
@@ -684,15 +636,15 @@ int hc_found_to_lines_device(hc_ctx* c, uint64_t num_singles, uint64_t num_pairs
         HC_HIP(hipMemcpyAsync(host + 5, d_status + 5, 8, hipMemcpyDeviceToHost, st));
         HC_HIP(hipStreamSynchronize(st));
         kept = host[5];
-        HC_HIP(hc::sfo_gather_lines(d_raw, d_kidx, kept, c->d_found_lines, st));
+        HC_HIP(hc::sfo_gather_lines(d_raw, d_kidx, kept, c->d_found_lines.as<hc_line_rec>(), st));
     } else {
-        HC_HIP(hipMemcpyAsync(c->d_found_lines, d_raw, total * sizeof(hc_line_rec), hipMemcpyDeviceToDevice, st));
+        HC_HIP(hipMemcpyAsync(c->d_found_lines.p, d_raw, total * sizeof(hc_line_rec), hipMemcpyDeviceToDevice, st));
     }
     HC_HIP(hipStreamSynchronize(st));
     if (timing)
         fprintf(stderr, "hc_found_to_lines_device: %llu SFO records -> %llu grouped, %llu groups -> %llu lines (%llu equal neighbours dropped) in %.3f s, all on the device\n",
                 (unsigned long long)n, (unsigned long long)m, (unsigned long long)G, (unsigned long long)kept, (unsigned long long)(total - kept), now() - t0);
-    *d_lines = c->d_found_lines;
+    *d_lines = c->d_found_lines.as<hc_line_rec>();
     *n_lines = kept;
     return HC_OK;
 }
@@ -706,14 +658,8 @@ int hc_set_found_records(hc_ctx* c, const hc_sfo_rec* recs, uint64_t n) {
     c->n_found = 0;
     c->found_valid = false;
     if (n) {
-        if (!c->d_found || c->found_cap < n) {
-            if (c->d_found) (void)hipFree(c->d_found);
-            c->d_found = nullptr;
-            c->found_cap = 0;
-            HC_HIP(hipMalloc((void**)&c->d_found, n * sizeof(hc_sfo_rec)));
-            c->found_cap = n;
-        }
-        HC_HIP(hipMemcpy(c->d_found, recs, n * sizeof(hc_sfo_rec), hipMemcpyHostToDevice));
+        if (const int rc = found_room(c, n)) return rc;
+        HC_HIP(hipMemcpy(c->d_found.p, recs, n * sizeof(hc_sfo_rec), hipMemcpyHostToDevice));
     }
     c->n_found = n;
     c->found_err = -1;  // (no finder arguments describe these records: the next hc_find_overlaps computes)
@@ -748,13 +694,8 @@ int hc_set_found_from_sfo_text(hc_ctx* c, const char* text, uint64_t n_bytes, ui
         c->found_valid = true;
         return HC_OK;
     }
-    if (!c->d_found || c->found_cap < lines) {
-        if (c->d_found) (void)hipFree(c->d_found);
-        c->d_found = nullptr;
-        c->found_cap = 0;
-        HC_HIP(hipMalloc((void**)&c->d_found, lines * sizeof(hc_sfo_rec)));
-        c->found_cap = lines;
-    }
+    int rc = found_room(c, lines);
+    if (rc) return rc;
     // Chunks of 32 MiB, three stations (a page-locked host buffer the context keeps, a device buffer, line-start arrays, counters, events):
     // the host's threads copy chunk k out of the caller's (pageable, usually mapped-file) memory into station k % 3's page-locked buffer —
     // in parallel slices: one thread through the runtime's own staging moved 27 GB/s at config 3's size —, the copy stream takes it to the
@@ -764,44 +705,35 @@ int hc_set_found_from_sfo_text(hc_ctx* c, const char* text, uint64_t n_bytes, ui
     const uint32_t max_lines = (uint32_t)(C / 16 + 2);  // (a canonical line has 16 bytes and more; a chunk with more lines is not canonical: overflow -> status)
     const uint32_t n_tiles = (uint32_t)(C / 4096 + 2);
     const uint64_t n_chunks_max = n_bytes / (C / 2) + 2;
-    for (int k = 0; k < kStations; k++)
-        if (!c->h_sfo_text[k]) HC_HIP(hipHostMalloc(&c->h_sfo_text[k], C + 64, hipHostMallocDefault));
-    struct Bufs {
-        char* text[kStations] = {};
-        uint32_t *tile_cnt[kStations] = {}, *tile_off[kStations] = {}, *line_start[kStations] = {};
-        unsigned long long *counters[kStations] = {}, *chain = nullptr, *status = nullptr;
+    for (hc_scratch& h : c->h_sfo_text)
+        if ((rc = h.ensure_exact(C + 64))) return rc;
+    struct Bufs {  // this call's own
+        hc_scratch text[kStations], tile_cnt[kStations], tile_off[kStations], line_start[kStations], counters[kStations], chain_mem, status_mem;
         hipEvent_t copied[kStations] = {}, parsed[kStations] = {};
         hipStream_t copy = nullptr;
         ~Bufs() {
             for (int k = 0; k < kStations; k++) {
-                if (text[k]) (void)hipFree(text[k]);
-                if (tile_cnt[k]) (void)hipFree(tile_cnt[k]);
-                if (tile_off[k]) (void)hipFree(tile_off[k]);
-                if (line_start[k]) (void)hipFree(line_start[k]);
-                if (counters[k]) (void)hipFree(counters[k]);
                 if (copied[k]) (void)hipEventDestroy(copied[k]);
                 if (parsed[k]) (void)hipEventDestroy(parsed[k]);
             }
-            if (chain) (void)hipFree(chain);
-            if (status) (void)hipFree(status);
             if (copy) (void)hipStreamDestroy(copy);
         }
     } b;
     for (int k = 0; k < kStations; k++) {
-        HC_HIP(hipMalloc((void**)&b.text[k], C + 64));
-        HC_HIP(hipMalloc((void**)&b.tile_cnt[k], (size_t)n_tiles * 4));
-        HC_HIP(hipMalloc((void**)&b.tile_off[k], (size_t)n_tiles * 4));
-        HC_HIP(hipMalloc((void**)&b.line_start[k], ((size_t)max_lines + 2) * 4));
-        HC_HIP(hipMalloc((void**)&b.counters[k], hc::kTextCounters * sizeof(unsigned long long)));
+        if ((rc = b.text[k].ensure_exact(C + 64)) || (rc = b.tile_cnt[k].ensure_exact((size_t)n_tiles * 4)) ||
+            (rc = b.tile_off[k].ensure_exact((size_t)n_tiles * 4)) || (rc = b.line_start[k].ensure_exact(((size_t)max_lines + 2) * 4)) ||
+            (rc = b.counters[k].ensure_exact(hc::kTextCounters * sizeof(unsigned long long))))
+            return rc;
         HC_HIP(hipEventCreateWithFlags(&b.copied[k], hipEventDisableTiming));
         HC_HIP(hipEventCreateWithFlags(&b.parsed[k], hipEventDisableTiming));
     }
-    HC_HIP(hipMalloc((void**)&b.chain, (n_chunks_max + 1) * sizeof(unsigned long long)));
-    HC_HIP(hipMalloc((void**)&b.status, sizeof(unsigned long long)));
+    if ((rc = b.chain_mem.ensure_exact((n_chunks_max + 1) * sizeof(unsigned long long))) || (rc = b.status_mem.ensure_exact(sizeof(unsigned long long))))
+        return rc;
+    unsigned long long *const d_chain = b.chain_mem.as<unsigned long long>(), *const d_status = b.status_mem.as<unsigned long long>();
     HC_HIP(hipStreamCreateWithFlags(&b.copy, hipStreamNonBlocking));
     hipStream_t st = c->stream;
-    HC_HIP(hipMemsetAsync(b.chain, 0, sizeof(unsigned long long), st));
-    HC_HIP(hipMemsetAsync(b.status, 0, sizeof(unsigned long long), st));
+    HC_HIP(hipMemsetAsync(d_chain, 0, sizeof(unsigned long long), st));
+    HC_HIP(hipMemsetAsync(d_status, 0, sizeof(unsigned long long), st));
     HC_HIP(hipStreamSynchronize(st));
     // the copiers: T - 1 threads beside the caller's, one slice of the chunk each (HC_SFO_COPY_THREADS; 1: the caller's thread alone)
     struct Copiers {
@@ -882,22 +814,25 @@ int hc_set_found_from_sfo_text(hc_ctx* c, const char* text, uint64_t n_bytes, ui
         if (k >= n_chunks_max) return fail(HC_ERR_NOT_ON_DEVICE, "hc_set_found_from_sfo_text: not on the device (more chunks than planned)");
         const int j = (int)(k % kStations);
         if (k >= (uint64_t)kStations) HC_HIP(hipEventSynchronize(b.copied[j]));  // the station's host buffer has left for the device
-        copiers.copy(text + pos, (char*)c->h_sfo_text[j], (size_t)len);
+        char* const d_text = b.text[j].as<char>();
+        uint32_t *const tile_cnt = b.tile_cnt[j].as<uint32_t>(), *const tile_off = b.tile_off[j].as<uint32_t>(), *const line_start = b.line_start[j].as<uint32_t>();
+        unsigned long long* const counters = b.counters[j].as<unsigned long long>();
+        copiers.copy(text + pos, c->h_sfo_text[j].as<char>(), (size_t)len);
         if (k >= (uint64_t)kStations) HC_HIP(hipStreamWaitEvent(b.copy, b.parsed[j], 0));  // the station's device buffer has been read
-        HC_HIP(hipMemcpyAsync(b.text[j], c->h_sfo_text[j], len, hipMemcpyHostToDevice, b.copy));
+        HC_HIP(hipMemcpyAsync(d_text, c->h_sfo_text[j].p, len, hipMemcpyHostToDevice, b.copy));
         HC_HIP(hipEventRecord(b.copied[j], b.copy));
         HC_HIP(hipStreamWaitEvent(st, b.copied[j], 0));
-        HC_HIP(hc::launch_text_count(b.text[j], len, b.tile_cnt[j], st));
-        HC_HIP(hc::launch_text_scan(b.text[j], len, b.tile_cnt[j], b.tile_off[j], max_lines, b.line_start[j], b.counters[j], b.chain + k, b.chain + k + 1, st));
-        HC_HIP(hc::launch_text_line_starts(b.text[j], len, b.tile_off[j], max_lines, b.line_start[j], st));
-        HC_HIP(hc::sfo_parse_text(b.text[j], b.line_start[j], max_lines, b.counters[j], b.chain + k, c->d_found, lines, b.status, st));
+        HC_HIP(hc::launch_text_count(d_text, len, tile_cnt, st));
+        HC_HIP(hc::launch_text_scan(d_text, len, tile_cnt, tile_off, max_lines, line_start, counters, d_chain + k, d_chain + k + 1, st));
+        HC_HIP(hc::launch_text_line_starts(d_text, len, tile_off, max_lines, line_start, st));
+        HC_HIP(hc::sfo_parse_text(d_text, line_start, max_lines, counters, d_chain + k, c->d_found.as<hc_sfo_rec>(), lines, d_status, st));
         HC_HIP(hipEventRecord(b.parsed[j], st));
         pos += len;
         k++;
     }
     unsigned long long status = 0, total = 0;
-    HC_HIP(hipMemcpyAsync(&status, b.status, sizeof status, hipMemcpyDeviceToHost, st));
-    HC_HIP(hipMemcpyAsync(&total, b.chain + k, sizeof total, hipMemcpyDeviceToHost, st));
+    HC_HIP(hipMemcpyAsync(&status, d_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HC_HIP(hipMemcpyAsync(&total, d_chain + k, sizeof total, hipMemcpyDeviceToHost, st));
     HC_HIP(hipStreamSynchronize(st));
     HC_HIP(hipStreamSynchronize(b.copy));
     if (status || total > lines) return fail(HC_ERR_NOT_ON_DEVICE, "hc_set_found_from_sfo_text: not on the device (a line that is not canonical)");

@@ -17,33 +17,29 @@
 #include "hc_hostcopy.h"
 #include "hc_overlap_finder.h"
 #include "hc_prims.h"
+#include "hc_scratch.h"
 #include "host/Types.h"
 
 namespace hc {
 namespace {
 
 struct DeviceBuffers {  // freed on every way out
-    std::vector<void*> all;
-    ~DeviceBuffers() {
-        for (void* p : all)
-            if (p) (void)hipFree(p);
-    }
+    std::vector<hc_scratch> all;
     void release(void* p) {  // early, for buffers that are spent
         if (!p) return;
-        for (void*& q : all)
-            if (q == p) {
-                (void)hipFree(p);
-                q = nullptr;
+        for (hc_scratch& q : all)
+            if (q.p == p) {
+                q.release();
                 return;
             }
     }
     template <typename T>
     T* get(uint64_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<uint64_t>(count, 1) * sizeof(T));
+        hc_scratch b;
+        const hipError_t e = b.alloc(std::max<uint64_t>(count, 1) * sizeof(T));
         if (e != hipSuccess) throw FatalError{HC_ERR_NOMEM, std::string("find-next-overlaps on the device: hipMalloc: ") + hipGetErrorString(e)};
-        all.push_back(p);
-        return (T*)p;
+        all.push_back(std::move(b));
+        return all.back().as<T>();
     }
 };
 void hip_check(hipError_t e, const char* what) {

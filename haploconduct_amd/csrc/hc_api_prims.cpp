@@ -6,19 +6,13 @@
 #include <string>
 
 #include "../../include/hcedge.h"
-#include "hc_ctx.h"
+#include "hc_scratch.h"
 #include "hc_prims.h"
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
 
 namespace {
-struct Dev {  // a device buffer freed on every return path
-    void* p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
+size_t or_16(size_t bytes) { return bytes ? bytes : 16; }  // (no bytes: a block all the same)
 int pick_device() {
     const char* e = getenv("HC_DEVICE");
     return e ? atoi(e) : 0;
@@ -34,13 +28,13 @@ int hc_dev_radix_sort(uint32_t key_bytes, uint32_t val_bytes, const void* keys, 
     if (n && (!keys || !keys_out || (val_bytes && (!vals || !vals_out)))) return fail(HC_ERR_ARG, "hc_dev_radix_sort: null buffer");
     if (n == 0) return HC_OK;
     HC_HIP(hipSetDevice(pick_device()));
-    Dev k0, k1, v0, v1, tmp;
+    hc_scratch k0, k1, v0, v1, tmp;  // this call's own, here and below
     const size_t tb = hc::prims::sort_temp_bytes(n, key_bytes, val_bytes);
     HC_HIP(k0.alloc(n * key_bytes));
     HC_HIP(k1.alloc(n * key_bytes));
-    HC_HIP(v0.alloc(n * val_bytes));
-    HC_HIP(v1.alloc(n * val_bytes));
-    HC_HIP(tmp.alloc(tb));
+    HC_HIP(v0.alloc(or_16(n * val_bytes)));
+    HC_HIP(v1.alloc(or_16(n * val_bytes)));
+    HC_HIP(tmp.alloc(or_16(tb)));
     HC_HIP(hipMemcpy(k0.p, keys, n * key_bytes, hipMemcpyHostToDevice));
     if (val_bytes) HC_HIP(hipMemcpy(v0.p, vals, n * val_bytes, hipMemcpyHostToDevice));
     hipError_t e;
@@ -64,10 +58,10 @@ int hc_dev_exclusive_sum(uint32_t elem_bytes, const void* in, void* out, uint64_
     if (n && (!in || !out)) return fail(HC_ERR_ARG, "hc_dev_exclusive_sum: null buffer");
     if (n == 0) return HC_OK;
     HC_HIP(hipSetDevice(pick_device()));
-    Dev a, tmp;
+    hc_scratch a, tmp;
     const size_t tb = hc::prims::scan_temp_bytes(n, elem_bytes);
     HC_HIP(a.alloc(n * elem_bytes));
-    HC_HIP(tmp.alloc(tb));
+    HC_HIP(tmp.alloc(or_16(tb)));
     HC_HIP(hipMemcpy(a.p, in, n * elem_bytes, hipMemcpyHostToDevice));
     if (elem_bytes == 4) HC_HIP(hc::prims::exclusive_sum(tmp.p, tb, (const uint32_t*)a.p, (uint32_t*)a.p, n, nullptr));  // in place
     else HC_HIP(hc::prims::exclusive_sum(tmp.p, tb, (const uint64_t*)a.p, (uint64_t*)a.p, n, nullptr));
@@ -81,12 +75,12 @@ int hc_dev_select_flagged(const uint8_t* flags, uint64_t n, uint32_t* idx_out, u
     *count = 0;
     if (n == 0) return HC_OK;
     HC_HIP(hipSetDevice(pick_device()));
-    Dev f, idx, cnt, tmp;
+    hc_scratch f, idx, cnt, tmp;
     const size_t tb = hc::prims::select_temp_bytes(n);
     HC_HIP(f.alloc(n));
     HC_HIP(idx.alloc(n * 4));
     HC_HIP(cnt.alloc(8));
-    HC_HIP(tmp.alloc(tb));
+    HC_HIP(tmp.alloc(or_16(tb)));
     HC_HIP(hipMemcpy(f.p, flags, n, hipMemcpyHostToDevice));
     HC_HIP(hc::prims::select_flagged(tmp.p, tb, (const uint8_t*)f.p, n, (uint32_t*)idx.p, (unsigned long long*)cnt.p, nullptr));
     HC_HIP(hipDeviceSynchronize());
@@ -102,12 +96,12 @@ int hc_dev_unique_u64(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* c
     *count = 0;
     if (n == 0) return HC_OK;
     HC_HIP(hipSetDevice(pick_device()));
-    Dev a, b, cnt, tmp;
+    hc_scratch a, b, cnt, tmp;
     const size_t tb = hc::prims::select_temp_bytes(n);
     HC_HIP(a.alloc(n * 8));
     HC_HIP(b.alloc(n * 8));
     HC_HIP(cnt.alloc(8));
-    HC_HIP(tmp.alloc(tb));
+    HC_HIP(tmp.alloc(or_16(tb)));
     HC_HIP(hipMemcpy(a.p, in, n * 8, hipMemcpyHostToDevice));
     HC_HIP(hc::prims::unique(tmp.p, tb, (const uint64_t*)a.p, (uint64_t*)b.p, (unsigned long long*)cnt.p, n, nullptr));
     HC_HIP(hipDeviceSynchronize());

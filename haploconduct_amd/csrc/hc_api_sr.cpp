@@ -420,19 +420,14 @@ int self_merge_ms(hc_ctx* c, SelfWork& W, hc_sr_self_stats* stats) {
     return HC_OK;
 }
 
-// The kept consensus bytes get room for `bytes` and the check kernel's padding behind them, their contents preserved: a new block, a
-// device-to-device copy, a swap.  (hc_scratch::ensure keeps nothing, and its headroom of an eighth is less than the padding for a small block.)
+// The kept consensus bytes get room for `bytes` and the check kernel's padding behind them, their contents preserved.  (The headroom of
+// an eighth, as hc_scratch::ensure's, is less than the padding for a small block.)
 int kept_reserve(hc_ctx* c, uint64_t bytes) {
     hc_ctx::Sr& K = c->sr;
-    for (hc_scratch* b : {&K.seq, &K.qual}) {
-        if (b->p && b->cap >= bytes + hc::kSelfPad) continue;
-        hc_scratch nb;
-        int rc = nb.ensure(bytes + hc::kSelfPad);
-        if (rc) return rc;
-        if (K.kept_bytes && b->p) HC_HIP(hipMemcpyAsync(nb.p, b->p, K.kept_bytes, hipMemcpyDeviceToDevice, c->stream));
-        HC_HIP(hipStreamSynchronize(c->stream));  // (the old block is freed by the swap's temporary)
-        b->swap(nb);
-    }
+    const size_t want = bytes + hc::kSelfPad;
+    for (hc_scratch* b : {&K.seq, &K.qual})
+        if (b->cap < want)
+            if (const int rc = b->grow_keep(want + want / 8, K.kept_bytes, c->stream)) return rc;
     return HC_OK;
 }
 

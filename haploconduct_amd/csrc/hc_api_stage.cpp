@@ -23,13 +23,13 @@ struct hc_block {
     uint64_t cap = 0;  // candidates
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    void* d_in = nullptr;                  // cap hc_cand_rec
-    void* d_out = nullptr;                 // cap hc_result_rec
-    unsigned long long* d_count = nullptr; // rows appended by the kernel
-    hc_gather_row* d_rows = nullptr;       // cap rows: the non-dropped records in sequence order (launch_kept_rows)
-    uint32_t* d_tiles = nullptr;           // its scratch: two arrays of cap / 1024 + 2 counters
-    hc_gather_row* h_rows = nullptr;       // page-locked, mapped: the rows, streamed out by a copy kernel behind it
-    unsigned long long* h_count = nullptr; // page-locked
+    hc_scratch d_in;                             // cap hc_cand_rec
+    hc_scratch d_out;                            // cap hc_result_rec
+    hc_scratch d_count;                          // unsigned long long: rows appended by the kernel
+    hc_scratch d_rows;                           // cap hc_gather_row: the non-dropped records in sequence order (launch_kept_rows)
+    hc_scratch d_tiles;                          // its scratch: two arrays of cap / 1024 + 2 uint32 counters
+    hc_scratch h_rows{hipHostMallocMapped};      // page-locked, mapped: the rows, streamed out by a copy kernel behind it
+    hc_scratch h_count{hipHostMallocDefault};    // page-locked: unsigned long long
     uint64_t n = 0, base_index = 0;
     hc_bucket_ws bucket;                   // scratch of a length-bucketed scoring launch (read sets of mixed sequence length)
     bool in_flight = false;
@@ -45,21 +45,19 @@ int hc_block_create(hc_ctx* c, uint64_t max_candidates, hc_block** out) {
     if (!b) return fail(HC_ERR_NOMEM, "hc_block_create: host allocation failed");
     b->ctx = c;
     b->cap = max_candidates;
-    auto cleanup = [&](hipError_t e, const char* what) {
-        hc_block_destroy(b);
-        return fail(HC_ERR_HIP, std::string("hc_block_create: ") + what + ": " + hipGetErrorString(e));
-    };
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess) return cleanup(e, "stream");
-    if ((e = hipEventCreateWithFlags(&b->done, hipEventDisableTiming)) != hipSuccess) return cleanup(e, "event");
-    if ((e = hipMalloc(&b->d_in, max_candidates * sizeof(hc_cand_rec))) != hipSuccess) return cleanup(e, "candidates");
-    if ((e = hipMalloc(&b->d_out, max_candidates * sizeof(hc_result_rec))) != hipSuccess) return cleanup(e, "results");
-    if ((e = hipMalloc((void**)&b->d_count, sizeof(unsigned long long))) != hipSuccess) return cleanup(e, "count");
-    if ((e = hipMalloc((void**)&b->d_rows, max_candidates * sizeof(hc_gather_row))) != hipSuccess) return cleanup(e, "rows");
-    if ((e = hipMalloc((void**)&b->d_tiles, 2 * (max_candidates / 1024 + 2) * sizeof(uint32_t))) != hipSuccess) return cleanup(e, "tiles");
-    if ((e = hipHostMalloc((void**)&b->h_rows, max_candidates * sizeof(hc_gather_row), hipHostMallocMapped)) != hipSuccess)
-        return cleanup(e, "row buffer");
-    if ((e = hipHostMalloc((void**)&b->h_count, sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess) return cleanup(e, "count buffer");
+    if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&b->done, hipEventDisableTiming)) != hipSuccess ||
+        (e = b->d_in.alloc(max_candidates * sizeof(hc_cand_rec))) != hipSuccess ||
+        (e = b->d_out.alloc(max_candidates * sizeof(hc_result_rec))) != hipSuccess ||
+        (e = b->d_count.alloc(sizeof(unsigned long long))) != hipSuccess ||
+        (e = b->d_rows.alloc(max_candidates * sizeof(hc_gather_row))) != hipSuccess ||
+        (e = b->d_tiles.alloc(2 * (max_candidates / 1024 + 2) * sizeof(uint32_t))) != hipSuccess ||
+        (e = b->h_rows.alloc(max_candidates * sizeof(hc_gather_row))) != hipSuccess ||
+        (e = b->h_count.alloc(sizeof(unsigned long long))) != hipSuccess) {
+        hc_block_destroy(b);
+        return fail(HC_ERR_HIP, std::string("hc_block_create: ") + hipGetErrorString(e));
+    }
     *out = b;
     return HC_OK;
 }
@@ -68,13 +66,6 @@ int hc_block_destroy(hc_block* b) {
     if (!b) return HC_OK;
     (void)hipSetDevice(b->ctx->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->d_in) (void)hipFree(b->d_in);
-    if (b->d_out) (void)hipFree(b->d_out);
-    if (b->d_count) (void)hipFree(b->d_count);
-    if (b->d_rows) (void)hipFree(b->d_rows);
-    if (b->d_tiles) (void)hipFree(b->d_tiles);
-    if (b->h_rows) (void)hipHostFree(b->h_rows);
-    if (b->h_count) (void)hipHostFree(b->h_count);
     if (b->done) (void)hipEventDestroy(b->done);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -91,19 +82,21 @@ int hc_block_submit(hc_block* b, const hc_cand_rec* cands, uint64_t n, uint64_t 
     HC_HIP(hipSetDevice(c->device));
     b->n = n;
     b->base_index = base_index;
-    *b->h_count = 0;
+    *b->h_count.as<unsigned long long>() = 0;
     if (n) {
         void* d_rows = nullptr;
-        HC_HIP(hipHostGetDevicePointer(&d_rows, b->h_rows, 0));
-        HC_HIP(hipMemcpyAsync(b->d_in, cands, n * sizeof(hc_cand_rec), hipMemcpyHostToDevice, b->stream));
+        uint32_t* const d_tiles = b->d_tiles.as<uint32_t>();
+        unsigned long long* const d_count = b->d_count.as<unsigned long long>();
+        HC_HIP(hipHostGetDevicePointer(&d_rows, b->h_rows.p, 0));
+        HC_HIP(hipMemcpyAsync(b->d_in.p, cands, n * sizeof(hc_cand_rec), hipMemcpyHostToDevice, b->stream));
         // as given: the stage's blocks come from files in sfo2overlaps / FNO order; an unordered file still scores
         // correctly, only slower (hc_set_reorder(HC_REORDER_ALWAYS) sorts every block first)
-        int rc = hc_ctx_score(c, HC_REC_COMPACT, b->d_in, n, b->d_out, b->stream, false, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, &b->bucket);
+        int rc = hc_ctx_score(c, HC_REC_COMPACT, b->d_in.p, n, b->d_out.p, b->stream, false, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, &b->bucket);
         if (rc) return rc;
-        HC_HIP(hc::launch_kept_rows((const hc_result_rec*)b->d_out, n, nullptr, base_index, b->d_tiles, b->d_tiles + (b->cap / 1024 + 2), b->d_rows,
-                                    b->cap, b->d_count, nullptr, nullptr, b->stream));
-        HC_HIP(hc::launch_flush_rows(b->d_rows, d_rows, b->d_count, b->cap, sizeof(hc_gather_row), c->n_cu, b->stream));
-        HC_HIP(hipMemcpyAsync(b->h_count, b->d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+        HC_HIP(hc::launch_kept_rows(b->d_out.as<hc_result_rec>(), n, nullptr, base_index, d_tiles, d_tiles + (b->cap / 1024 + 2),
+                                    b->d_rows.as<hc_gather_row>(), b->cap, d_count, nullptr, nullptr, b->stream));
+        HC_HIP(hc::launch_flush_rows(b->d_rows.p, d_rows, d_count, b->cap, sizeof(hc_gather_row), c->n_cu, b->stream));
+        HC_HIP(hipMemcpyAsync(b->h_count.p, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
     }
     HC_HIP(hipEventRecord(b->done, b->stream));
     b->in_flight = true;
@@ -118,9 +111,9 @@ int hc_block_wait(hc_block* b, const hc_gather_row** rows, uint64_t* n_rows) {
     HC_HIP(hipSetDevice(b->ctx->device));
     HC_HIP(hipEventSynchronize(b->done));
     b->in_flight = false;
-    const uint64_t k = *b->h_count;
+    const uint64_t k = *b->h_count.as<unsigned long long>();
     if (k > b->cap) return fail(HC_ERR_STATE, "hc_block_wait: row count beyond the block's capacity");
-    *rows = b->h_rows;  // in sequence order as they are (launch_kept_rows)
+    *rows = b->h_rows.as<hc_gather_row>();  // in sequence order as they are (launch_kept_rows)
     *n_rows = k;
     return HC_OK;
 }
@@ -145,19 +138,7 @@ int hc_graph_append(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n) {
     if (want * sizeof(hc_admit_rec) > g.adm.cap) {  // grow, keeping what is there
         size_t cap = g.adm.cap ? g.adm.cap : ((size_t)1 << 24);
         while (cap < want * sizeof(hc_admit_rec)) cap *= 2;
-        void* bigger = nullptr;
-        HC_HIP(hipStreamSynchronize(c->stream));  // appends in flight land in the old buffer first
-        HC_HIP(hipMalloc(&bigger, cap));
-        if (have) {
-            const hipError_t e = hipMemcpy(bigger, g.adm.p, have * sizeof(hc_admit_rec), hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(bigger);
-                return fail(HC_ERR_HIP, std::string("hc_graph_append: ") + hipGetErrorString(e));
-            }
-        }
-        g.adm.release();
-        g.adm.p = bigger;
-        g.adm.cap = cap;
+        if (const int rc = g.adm.grow_keep(cap, have * sizeof(hc_admit_rec), c->stream)) return rc;  // (appends in flight land in the old buffer first)
     }
     // through a page-locked buffer, asynchronously on the context's stream (the blocks score on their own streams;
     // hc_graph_resolve runs on this one, behind the copies): the caller — the stage's in-order half — does not wait
@@ -166,17 +147,13 @@ int hc_graph_append(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n) {
     const size_t bytes = n * sizeof(hc_admit_rec);
     if (!g.stage_free[t]) HC_HIP(hipEventCreateWithFlags(&g.stage_free[t], hipEventDisableTiming));
     else HC_HIP(hipEventSynchronize(g.stage_free[t]));  // its previous copy (two appends ago) has left the buffer
-    if (g.stage_cap[t] < bytes) {
-        if (g.h_stage[t]) (void)hipHostFree(g.h_stage[t]);
-        g.h_stage[t] = nullptr;
-        g.stage_cap[t] = 0;
+    if (g.h_stage[t].cap < bytes) {
         size_t cap = (size_t)1 << 20;
         while (cap < bytes) cap *= 2;
-        HC_HIP(hipHostMalloc(&g.h_stage[t], cap, hipHostMallocDefault));
-        g.stage_cap[t] = cap;
+        if (const int rc = g.h_stage[t].ensure_exact(cap)) return rc;
     }
-    memcpy(g.h_stage[t], admitted, bytes);
-    HC_HIP(hipMemcpyAsync((char*)g.adm.p + have * sizeof(hc_admit_rec), g.h_stage[t], bytes, hipMemcpyHostToDevice, c->stream));
+    memcpy(g.h_stage[t].p, admitted, bytes);
+    HC_HIP(hipMemcpyAsync((char*)g.adm.p + have * sizeof(hc_admit_rec), g.h_stage[t].p, bytes, hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipEventRecord(g.stage_free[t], c->stream));
     g.n_appended = want;
     return HC_OK;
@@ -227,7 +204,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     ENS(tied_list, ((size_t)V + 1) * 4);
     ENS(temp, hc::graph_temp_bytes(m ? m : 1, V ? V : 1));
     hc::GraphParams gp;
-    gp.reads = c->d_reads;
+    gp.reads = c->d_reads.as<hc::ReadDesc>();
     gp.n_reads = c->view.n_reads;
     gp.vtx = nullptr;
     gp.n_vertices = V;
@@ -322,11 +299,6 @@ int hc_graph_fetch_edges(hc_ctx* c, uint64_t first, uint64_t count, hc_edge_rec*
 
 // ---------------------------------------------------------------------------------------------------------------
 // graph cleaning
-static void swap_scratch(hc_scratch& a, hc_scratch& b) {
-    std::swap(a.p, b.p);
-    std::swap(a.cap, b.cap);
-    std::swap(a.host, b.host);
-}
 
 int hc_graph_size(hc_ctx* c, uint64_t* n_vertices, uint64_t* n_edges) {
     if (!c || !n_vertices || !n_edges) return fail(HC_ERR_ARG, "hc_graph_size: null argument");
@@ -395,11 +367,11 @@ static int clean_prepare(hc_ctx* c, hc::trans::Graph& in, hc::trans::Graph& out)
 }
 
 static void clean_commit(hc_ctx::Graph& g, const hc::trans::Graph& out) {
-    swap_scratch(g.edges_out, g.edges_next);
-    swap_scratch(g.o_out, g.seq_next);
-    swap_scratch(g.out_off, g.out_off_next);
-    swap_scratch(g.in_nodes, g.in_nodes_next);
-    swap_scratch(g.in_off, g.in_off_next);
+    g.edges_out.swap(g.edges_next);
+    g.o_out.swap(g.seq_next);
+    g.out_off.swap(g.out_off_next);
+    g.in_nodes.swap(g.in_nodes_next);
+    g.in_off.swap(g.in_off_next);
     g.n_edges = out.E;
     g.n_tied = 0;  // the lists are in the reference's order now
 }
@@ -487,15 +459,8 @@ int hc_graph_fetch_inclusion_edges(hc_ctx* c, uint32_t* group_vertex, uint64_t* 
 // room for `want` bytes in a grow-only buffer whose first `have` bytes stay
 static int grow_keeping(hc_scratch& b, size_t have, size_t want, hipStream_t s) {
     if (want <= b.cap) return HC_OK;
-    hc_scratch bigger;
-    const int rc = bigger.ensure(std::max(want, 2 * b.cap));
-    if (rc) return rc;
-    if (have) {
-        HC_HIP(hipMemcpyAsync(bigger.p, b.p, have, hipMemcpyDeviceToDevice, s));
-        HC_HIP(hipStreamSynchronize(s));
-    }
-    swap_scratch(b, bigger);
-    return HC_OK;
+    const size_t room = std::max(want, 2 * b.cap);
+    return b.grow_keep(room + room / 8, have, s);  // (an eighth of headroom, as hc_scratch::ensure)
 }
 
 static const char* const kTiedRefusal =

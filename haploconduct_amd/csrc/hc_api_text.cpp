@@ -24,9 +24,9 @@ struct hc_textblock {
     hipEvent_t done = nullptr;
     hipEvent_t lines_known = nullptr;          // chained submits: this block's entry of the line chain is written
     hipEvent_t copied = nullptr;               // the text has arrived (the copies of all blocks share the context's copy stream)
-    char* h_text = nullptr;                    // page-locked, allocated on first use (hc_textblock_buffer): the caller reads the file into it
-    char* d_slab = nullptr;                    // ONE device allocation holding d_text ... d_kept_tiles
-    char *d_rowslab = nullptr, *h_rowslab = nullptr;  // the row buffers (they may grow): d_rows + d_row_lines; h_rows + h_row_lines + h_rejects, page-locked and mapped
+    hc_scratch h_text;                         // page-locked, allocated on first use (hc_textblock_buffer): the caller reads the file into it
+    hc_scratch d_slab;                         // ONE device allocation holding d_text ... d_kept_tiles
+    hc_scratch d_rowslab, h_rowslab{hipHostMallocMapped};  // the row buffers (they may grow): d_rows + d_row_lines; h_rows + h_row_lines + h_rejects, page-locked and mapped
     char* d_text = nullptr;                    // max_bytes + 64
     uint32_t *d_tile_cnt = nullptr, *d_tile_off = nullptr, *d_line_start = nullptr;
     uint32_t* d_tally = nullptr;               // the parse kernel's per-workgroup tallies
@@ -40,8 +40,8 @@ struct hc_textblock {
     hc_gather_row* h_rows = nullptr;           // page-locked, mapped: both streamed out by copy kernels behind the scoring kernel
     hc_line_rec* h_row_lines = nullptr;
     hc_text_reject* h_rejects = nullptr;       // page-locked, mapped: written by the parse kernel
-    unsigned long long* h_counters = nullptr;  // page-locked
-    hc_text_nonplain* h_nonplain = nullptr;    // page-locked, mapped: the parse kernel lists the lines it does not read (hc_textblock_list_nonplain)
+    hc_scratch h_counters{hipHostMallocMapped};  // page-locked, mapped: hc::kTextCounters unsigned long long
+    hc_scratch h_nonplain{hipHostMallocMapped};  // page-locked, mapped: hc_text_nonplain, the parse kernel lists the lines it does not read (hc_textblock_list_nonplain)
     uint32_t nonplain_cap = 0;
     std::vector<hc_text_row> rows;             // what hc_textblock_wait hands out
     hc_bucket_ws bucket;                       // scratch of a length-bucketed scoring launch (read sets of mixed sequence length)
@@ -51,7 +51,7 @@ struct hc_textblock {
     const hc_line_rec* sub_src_lines = nullptr;  // hc_textblock_submit_lines: the block's lines come parsed, from device memory
     uint32_t sub_n_lines = 0;
     uint64_t n_regrown = 0;                    // how often that happened
-    std::vector<void*> old_device, old_host;   // row buffers hc_textblock_reserve_rows replaced: freed with the block (a free waits for the device)
+    std::vector<hc_scratch> old_rowslabs;      // row buffers hc_textblock_reserve_rows replaced: freed with the block (a free waits for the device)
     bool in_flight = false;
 };
 
@@ -143,21 +143,21 @@ int hc_textblock_create(hc_ctx* c, uint64_t max_bytes, hc_textblock** out) {
                      o_tally = place(((size_t)b->max_lines / 256 + 2) * 8 * 4), o_line_start = place((L + 2) * 4),
                      o_cands = place((L + 256) * sizeof(hc_cand_rec)), o_lines = place(L * sizeof(hc_line_rec)), o_out = place(L * sizeof(hc_result_rec)),
                      o_counters = place(hc::kTextCounters * sizeof(unsigned long long)), o_kept = place(2 * (L / 1024 + 2) * sizeof(uint32_t));
-        ok(hipMalloc((void**)&b->d_slab, at));
-        if (b->d_slab) {
-            b->d_text = b->d_slab + o_text;
-            b->d_tile_cnt = (uint32_t*)(b->d_slab + o_tile_cnt);
-            b->d_tile_off = (uint32_t*)(b->d_slab + o_tile_off);
-            b->d_tally = (uint32_t*)(b->d_slab + o_tally);
-            b->d_line_start = (uint32_t*)(b->d_slab + o_line_start);
-            b->d_cands = (hc_cand_rec*)(b->d_slab + o_cands);
-            b->d_lines = (hc_line_rec*)(b->d_slab + o_lines);
-            b->d_out = (hc_result_rec*)(b->d_slab + o_out);
-            b->d_counters = (unsigned long long*)(b->d_slab + o_counters);
-            b->d_kept_tiles = (uint32_t*)(b->d_slab + o_kept);
+        ok(b->d_slab.alloc(at));
+        if (char* const slab = b->d_slab.as<char>()) {
+            b->d_text = slab + o_text;
+            b->d_tile_cnt = (uint32_t*)(slab + o_tile_cnt);
+            b->d_tile_off = (uint32_t*)(slab + o_tile_off);
+            b->d_tally = (uint32_t*)(slab + o_tally);
+            b->d_line_start = (uint32_t*)(slab + o_line_start);
+            b->d_cands = (hc_cand_rec*)(slab + o_cands);
+            b->d_lines = (hc_line_rec*)(slab + o_lines);
+            b->d_out = (hc_result_rec*)(slab + o_out);
+            b->d_counters = (unsigned long long*)(slab + o_counters);
+            b->d_kept_tiles = (uint32_t*)(slab + o_kept);
         }
     }
-    ok(hipHostMalloc((void**)&b->h_counters, hc::kTextCounters * sizeof(unsigned long long), hipHostMallocMapped));  // the last launch of a block writes them
+    ok(b->h_counters.alloc(hc::kTextCounters * sizeof(unsigned long long)));  // the last launch of a block writes them
     if (e != hipSuccess) {
         hc_textblock_destroy(b);
         return fail(HC_ERR_HIP, std::string("hc_textblock_create: ") + hipGetErrorString(e));
@@ -173,21 +173,22 @@ int hc_textblock_create(hc_ctx* c, uint64_t max_bytes, hc_textblock** out) {
 
 char* hc_textblock_buffer(hc_textblock* b) {
     if (!b) return nullptr;
-    if (!b->h_text) {  // only callers that fill the block themselves pay for the page-locked buffer
+    if (!b->h_text.p) {  // only callers that fill the block themselves pay for the page-locked buffer
         (void)hipSetDevice(b->ctx->device);
         // HC_TEXT_BUFFER=wc: write-combined — pread fills it 1.4x as fast, but the CPU must then never read it (the stage
         // with HC_TEXT_SOURCE=pread-chain does not: line numbers come from the device side)
         const char* kind = getenv("HC_TEXT_BUFFER");
         const unsigned flags = (kind && !strcmp(kind, "wc")) ? hipHostMallocWriteCombined : hipHostMallocDefault;
-        if (hipHostMalloc((void**)&b->h_text, b->max_bytes + 64, flags) != hipSuccess) b->h_text = nullptr;
+        b->h_text = hc_scratch(flags);
+        (void)b->h_text.alloc(b->max_bytes + 64);
     }
-    return b->h_text;
+    return b->h_text.as<char>();
 }
 
 // A chain of line counts shared by the blocks of one file, in page-locked memory every device and the host can read:
 // entry k = lines in front of block k.
 struct hc_linechain {
-    unsigned long long* h = nullptr;
+    hc_scratch h{hipHostMallocMapped | hipHostMallocPortable};  // n unsigned long long
     uint64_t n = 0;
 };
 
@@ -197,19 +198,17 @@ int hc_linechain_create(hc_ctx* c, uint64_t n_blocks, hc_linechain** out) {
     hc_linechain* ch = new (std::nothrow) hc_linechain();
     if (!ch) return fail(HC_ERR_NOMEM, "hc_linechain_create: host allocation failed");
     ch->n = n_blocks + 2;
-    hipError_t e = hipHostMalloc((void**)&ch->h, ch->n * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocPortable);
+    hipError_t e = ch->h.alloc(ch->n * sizeof(unsigned long long));
     if (e != hipSuccess) {
         delete ch;
         return fail(HC_ERR_HIP, std::string("hc_linechain_create: ") + hipGetErrorString(e));
     }
-    memset(ch->h, 0, ch->n * sizeof(unsigned long long));
+    memset(ch->h.p, 0, ch->n * sizeof(unsigned long long));
     *out = ch;
     return HC_OK;
 }
 
 int hc_linechain_destroy(hc_linechain* ch) {
-    if (!ch) return HC_OK;
-    if (ch->h) (void)hipHostFree(ch->h);
     delete ch;
     return HC_OK;
 }
@@ -218,12 +217,6 @@ int hc_textblock_destroy(hc_textblock* b) {
     if (!b) return HC_OK;
     (void)hipSetDevice(b->ctx->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (void* p : {(void*)b->d_slab, (void*)b->d_rowslab})  // (d_text ... d_kept_tiles lie in the slab, d_rows / d_row_lines in the row slab)
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->h_text, (void*)b->h_rowslab, (void*)b->h_counters, (void*)b->h_nonplain})
-        if (p) (void)hipHostFree(p);
-    for (void* p : b->old_device) (void)hipFree(p);
-    for (void* p : b->old_host) (void)hipHostFree(p);
     if (b->done) (void)hipEventDestroy(b->done);
     if (b->lines_known) (void)hipEventDestroy(b->lines_known);
     if (b->copied) (void)hipEventDestroy(b->copied);
@@ -247,7 +240,7 @@ static int textblock_device_half(hc_textblock* b) {
     prm.min_overlap_perc = c->settings.min_overlap_perc;
     prm.relax_pe = (c->settings.flags & HC_FLAG_RELAX_PE_EDGES) ? 1u : 0u;
     prm.reject_cap = b->row_cap;
-    prm.nonplain_cap = b->h_nonplain ? b->nonplain_cap : 0u;
+    prm.nonplain_cap = b->h_nonplain.p ? b->nonplain_cap : 0u;
     hc::IdTable ids;
     ids.table = c->id_table.as<uint32_t>();
     ids.keys = c->id_keys.as<uint64_t>();
@@ -259,7 +252,7 @@ static int textblock_device_half(hc_textblock* b) {
     HC_HIP(hipHostGetDevicePointer(&d_rows, b->h_rows, 0));
     HC_HIP(hipHostGetDevicePointer(&d_row_lines, b->h_row_lines, 0));
     void* d_nonplain = nullptr;
-    if (b->h_nonplain) HC_HIP(hipHostGetDevicePointer(&d_nonplain, b->h_nonplain, 0));
+    if (b->h_nonplain.p) HC_HIP(hipHostGetDevicePointer(&d_nonplain, b->h_nonplain.p, 0));
     if (b->sub_src_lines)
         HC_HIP(hc::launch_lines_accept(prm, b->sub_src_lines, b->sub_n_lines, ids, b->d_cands, b->d_lines, (hc_text_reject*)d_rejects, b->d_counters,
                                        b->d_tally, s));
@@ -275,7 +268,7 @@ static int textblock_device_half(hc_textblock* b) {
                                 b->d_row_lines, s, b->d_tally, b->d_counters));
     // both row arrays and the counters -> the block's page-locked words, one launch
     void* d_counters_host = nullptr;
-    HC_HIP(hipHostGetDevicePointer(&d_counters_host, b->h_counters, 0));
+    HC_HIP(hipHostGetDevicePointer(&d_counters_host, b->h_counters.p, 0));
     HC_HIP(hc::launch_flush_text_rows(b->d_rows, d_rows, b->d_row_lines, d_row_lines, b->d_counters + hc::kTextRows, b->row_cap, b->d_counters,
                                       (unsigned long long*)d_counters_host, c->n_cu, s));
     return HC_OK;
@@ -288,15 +281,11 @@ static int textblock_device_half(hc_textblock* b) {
 // the row buffers (device rows, their mapped host twins, the rejects) for `cap` rows; defer_free: the old ones are kept for
 // hc_textblock_destroy instead of being freed now (hipFree / hipHostFree wait for the device: not next to another launch sequence)
 static int textblock_row_buffers(hc_textblock* b, uint64_t cap, bool defer_free) {
-    if (b->d_rowslab) {
-        if (defer_free) b->old_device.push_back(b->d_rowslab);
-        else (void)hipFree(b->d_rowslab);
+    for (hc_scratch* old : {&b->d_rowslab, &b->h_rowslab}) {
+        if (!old->p) continue;
+        if (defer_free) b->old_rowslabs.push_back(std::move(*old));
+        else old->release();
     }
-    if (b->h_rowslab) {
-        if (defer_free) b->old_host.push_back(b->h_rowslab);
-        else (void)hipHostFree(b->h_rowslab);
-    }
-    b->d_rowslab = b->h_rowslab = nullptr;
     b->d_rows = nullptr;
     b->d_row_lines = nullptr;
     b->h_rows = nullptr;
@@ -305,13 +294,14 @@ static int textblock_row_buffers(hc_textblock* b, uint64_t cap, bool defer_free)
     b->row_cap = (uint32_t)cap;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t rows_b = up(cap * sizeof(hc_gather_row)), lines_b = up(cap * sizeof(hc_line_rec)), rej_b = up(cap * sizeof(hc_text_reject));
-    HC_HIP(hipMalloc((void**)&b->d_rowslab, rows_b + lines_b));
-    HC_HIP(hipHostMalloc((void**)&b->h_rowslab, rows_b + lines_b + rej_b, hipHostMallocMapped));
-    b->d_rows = (hc_gather_row*)b->d_rowslab;
-    b->d_row_lines = (hc_line_rec*)(b->d_rowslab + rows_b);
-    b->h_rows = (hc_gather_row*)b->h_rowslab;
-    b->h_row_lines = (hc_line_rec*)(b->h_rowslab + rows_b);
-    b->h_rejects = (hc_text_reject*)(b->h_rowslab + rows_b + lines_b);
+    HC_HIP(b->d_rowslab.alloc(rows_b + lines_b));
+    HC_HIP(b->h_rowslab.alloc(rows_b + lines_b + rej_b));
+    char *const d = b->d_rowslab.as<char>(), *const h = b->h_rowslab.as<char>();
+    b->d_rows = (hc_gather_row*)d;
+    b->d_row_lines = (hc_line_rec*)(d + rows_b);
+    b->h_rows = (hc_gather_row*)h;
+    b->h_row_lines = (hc_line_rec*)(h + rows_b);
+    b->h_rejects = (hc_text_reject*)(h + rows_b + lines_b);
     return HC_OK;
 }
 
@@ -341,8 +331,8 @@ static int textblock_submit(hc_textblock* b, const void* src, uint64_t n_bytes, 
 
 int hc_textblock_submit(hc_textblock* b, uint64_t n_bytes, uint64_t first_line_no, uint64_t base_index) {
     if (!b) return fail(HC_ERR_ARG, "hc_textblock_submit: null block");
-    if (!b->h_text) return fail(HC_ERR_STATE, "hc_textblock_submit: hc_textblock_buffer was never filled");
-    return textblock_submit(b, b->h_text, n_bytes, first_line_no, nullptr, 0, nullptr, base_index);
+    if (!b->h_text.p) return fail(HC_ERR_STATE, "hc_textblock_submit: hc_textblock_buffer was never filled");
+    return textblock_submit(b, b->h_text.p, n_bytes, first_line_no, nullptr, 0, nullptr, base_index);
 }
 
 int hc_textblock_submit_from(hc_textblock* b, const void* text, uint64_t n_bytes, hc_linechain* chain, uint64_t k, hc_textblock* prev,
@@ -361,7 +351,7 @@ static int textblock_submit(hc_textblock* b, const void* src, uint64_t n_bytes, 
     HC_HIP(hipSetDevice(c->device));
     hipStream_t s = b->stream;
     unsigned long long* d_chain = nullptr;
-    if (chain) HC_HIP(hipHostGetDevicePointer((void**)&d_chain, chain->h, 0));
+    if (chain) HC_HIP(hipHostGetDevicePointer((void**)&d_chain, chain->h.p, 0));
     if (n_bytes) {
         // the text as it is (page-locked or pageable: a file mapping goes to the device without a copy by the caller).  The 16-byte
         // pieces of the last tile reach past the text: the kernels that look for newlines ignore what lies there.
@@ -396,7 +386,7 @@ static int textblock_submit(hc_textblock* b, const void* src, uint64_t n_bytes, 
         int rc = textblock_device_half(b);  // (its last launch leaves the counters in h_counters)
         if (rc) return rc;
     } else {
-        HC_HIP(hipMemcpyAsync(b->h_counters, b->d_counters, hc::kTextCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HC_HIP(hipMemcpyAsync(b->h_counters.p, b->d_counters, hc::kTextCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
     HC_HIP(hipEventRecord(b->done, s));
     b->in_flight = true;
@@ -443,17 +433,17 @@ int hc_textblock_wait(hc_textblock* b, hc_text_result* out) {
     HC_HIP(hipSetDevice(b->ctx->device));
     HC_HIP(hipEventSynchronize(b->done));
     b->in_flight = false;
-    const unsigned long long* k = b->h_counters;
+    const unsigned long long* k = b->h_counters.as<unsigned long long>();
     // lines the device did not read send the block to the host unless they are all in the list (hc_textblock_list_nonplain)
     auto nonplain_blocks = [&](const unsigned long long* kk) {
-        return kk[hc::kTextNonPlain] != 0 && !(b->h_nonplain && kk[hc::kTextNonPlain] <= b->nonplain_cap && kk[hc::kTextNonPlainSlots] == kk[hc::kTextNonPlain]);
+        return kk[hc::kTextNonPlain] != 0 && !(b->h_nonplain.p && kk[hc::kTextNonPlain] <= b->nonplain_cap && kk[hc::kTextNonPlainSlots] == kk[hc::kTextNonPlain]);
     };
     if (!(k[hc::kTextOverflow] || nonplain_blocks(k) || k[hc::kTextUnknownId]) &&
         (k[hc::kTextRows] > b->row_cap || k[hc::kTextRejectSlots] > b->row_cap)) {
         const uint64_t need = k[hc::kTextRows] > k[hc::kTextRejectSlots] ? k[hc::kTextRows] : k[hc::kTextRejectSlots];
         int rc = textblock_regrow(b, need);
         if (rc) return rc;
-        k = b->h_counters;
+        k = b->h_counters.as<unsigned long long>();
     }
     out->n_lines = k[hc::kTextLines];
     out->lines_read = k[hc::kTextRead];
@@ -481,8 +471,9 @@ int hc_textblock_wait(hc_textblock* b, hc_text_result* out) {
     out->rejected = b->h_rejects;
     out->n_rejected = n_rej;
     if (k[hc::kTextNonPlain]) {  // (all of them are listed, else needs_host)
-        std::sort(b->h_nonplain, b->h_nonplain + k[hc::kTextNonPlain], [](const hc_text_nonplain& x, const hc_text_nonplain& y) { return x.line_index < y.line_index; });
-        out->nonplain = b->h_nonplain;
+        hc_text_nonplain* const listed = b->h_nonplain.as<hc_text_nonplain>();
+        std::sort(listed, listed + k[hc::kTextNonPlain], [](const hc_text_nonplain& x, const hc_text_nonplain& y) { return x.line_index < y.line_index; });
+        out->nonplain = listed;
         out->n_nonplain_listed = k[hc::kTextNonPlain];
     }
     return HC_OK;
@@ -492,10 +483,9 @@ int hc_textblock_list_nonplain(hc_textblock* b, uint32_t max_lines) {
     if (!b) return fail(HC_ERR_ARG, "hc_textblock_list_nonplain: null block");
     if (b->in_flight) return fail(HC_ERR_STATE, "hc_textblock_list_nonplain: the block is still in flight (hc_textblock_wait first)");
     HC_HIP(hipSetDevice(b->ctx->device));
-    if (max_lines > b->nonplain_cap || (max_lines == 0 && b->h_nonplain)) {
-        if (b->h_nonplain) HC_HIP(hipHostFree(b->h_nonplain));
-        b->h_nonplain = nullptr;
-        if (max_lines) HC_HIP(hipHostMalloc((void**)&b->h_nonplain, (size_t)max_lines * sizeof(hc_text_nonplain), hipHostMallocMapped));
+    if (max_lines > b->nonplain_cap || (max_lines == 0 && b->h_nonplain.p)) {
+        b->h_nonplain.release();
+        if (max_lines) HC_HIP(b->h_nonplain.alloc((size_t)max_lines * sizeof(hc_text_nonplain)));
     }
     b->nonplain_cap = max_lines;
     return HC_OK;

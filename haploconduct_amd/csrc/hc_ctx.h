@@ -12,6 +12,7 @@
 #include "../../include/hcsr.h"
 #include "hc_device.h"
 #include "hc_overlap_finder.h"
+#include "hc_scratch.h"
 
 namespace hc {
 // hc_kernels.hip
@@ -105,7 +106,6 @@ size_t locality_index_temp_bytes(uint32_t n_reads);
 hipError_t launch_locality_index(const uint32_t* order, uint32_t n_reads, const void* in, uint64_t n, const unsigned long long* n_dev, uint32_t* bounds,
                                  uint32_t* start, uint32_t* flag, uint32_t* perm, void* temp, size_t temp_bytes, hipStream_t stream);
 
-int set_last_error(int status, const std::string& what);  // thread-local text behind hc_last_error()
 // hc_api.cpp: the x-space image of a score threshold with a guard band of 2^log2_width relative width (-49: the scoring path's), and the
 // log-probability table of the scoring path in its 16-bit-symbol layout (hc_device.h: two triangles of (K + 2) rows) for the Phred values
 // `phred`; false: the table is not symmetric in the two qualities
@@ -133,54 +133,6 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
 bool build_log_table_u16(const std::vector<int>& phred, double mismatch_setting, std::vector<double>& lut);
 }  // namespace hc
 
-#define HC_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (call);                                                                       \
-        if (e__ != hipSuccess)                                                                         \
-            return hc::set_last_error(HC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-// A grow-only device (or page-locked host) block owned by the context: allocating and freeing per call costs more
-// than most of the kernels here.
-struct hc_scratch {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool host = false;  // hipHostMalloc (mapped) instead of hipMalloc
-    int ensure(size_t bytes) {  // contents are not kept
-        if (bytes <= cap) return HC_OK;
-        release();
-        const size_t want = bytes + bytes / 8;
-        if (host) HC_HIP(hipHostMalloc(&p, want, hipHostMallocMapped));
-        else HC_HIP(hipMalloc(&p, want));
-        cap = want;
-        return HC_OK;
-    }
-    int ensure_exact(size_t bytes) {  // the same without the headroom: a block sized once per read set
-        if (bytes <= cap) return HC_OK;
-        release();
-        if (host) HC_HIP(hipHostMalloc(&p, bytes, hipHostMallocMapped));
-        else HC_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return HC_OK;
-    }
-    void swap(hc_scratch& o) {
-        std::swap(p, o.p);
-        std::swap(cap, o.cap);
-        std::swap(host, o.host);
-    }
-    void release() {
-        if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T* as() const { return (T*)p; }
-    hc_scratch() = default;
-    hc_scratch(const hc_scratch&) = delete;
-    hc_scratch& operator=(const hc_scratch&) = delete;
-    ~hc_scratch() { release(); }
-};
-
 // Scratch of one length-bucketed scoring launch (hc::bucket_perm_kernel): the queue counter, then the permutation.  One per
 // thing that launches on its own stream (the context, every hc_block / hc_textblock); grow-only.
 struct hc_bucket_ws {
@@ -203,10 +155,7 @@ struct hc_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // read store
     bool have_reads = false;
-    void* d_sym = nullptr;
-    hc::ReadDesc* d_reads = nullptr;
-    double* d_lut = nullptr;
-    double* d_inv_n = nullptr;  // StoreView::inv_n
+    hc_scratch d_sym, d_reads, d_lut, d_inv_n;  // symbols, hc::ReadDesc per read, the log-probability table, StoreView::inv_n
     uint32_t len_p5 = 0, len_p95 = 0;  // 5th / 95th percentile of the sequence lengths: what the kernel dispatch calls "mixed"
     uint64_t store_bytes = 0;
     hc::StoreView view{};
@@ -214,34 +163,27 @@ struct hc_ctx {
     // what the overlap finder needs of the sequences (host copies, filled by hc_set_reads)
     std::vector<hc::SeqRef> seq_refs;  // by store sequence index
     bool singles_first = true;
+    // Grow-only device scratch of the finder, one slot per buffer, and of the SFO ingest (hc_found_to_overlaps).  Like d_found and
+    // d_found_lines it outlives the read store (hc_set_reads, hc_reset) and goes with the context: gigabytes at config 3's size, and
+    // giving them back and asking for them again stalled the next stage's first kernels by 0.3 - 0.4 s (profiles/r06_stage_a_from_store.md).
+    hc_scratch finder_scratch[24], ingest_scratch[12];
+    hc_scratch h_ingest[2] = {hc_scratch(hipHostMallocDefault), hc_scratch(hipHostMallocDefault)};  // page-locked ring hc_found_to_overlaps copies the sorted records through
+    hc_scratch h_sfo_text[3] = {hc_scratch(hipHostMallocDefault), hc_scratch(hipHostMallocDefault),
+                                hc_scratch(hipHostMallocDefault)};  // page-locked stations of hc_set_found_from_sfo_text (32 MiB + 64 each), kept
     // result of the last hc_find_overlaps, kept on the device so that the usual "ask for the count, then fetch"
     // pair of calls computes once
-    struct Scratch {  // grow-only device scratch of the finder, one slot per buffer, freed with the store
-        void* p = nullptr;
-        size_t cap = 0;
-    } finder_scratch[24], ingest_scratch[12];  // the second set: hc_found_to_overlaps
-    void* h_ingest[2] = {nullptr, nullptr};  // page-locked ring hc_found_to_overlaps copies the sorted records through
-    size_t h_ingest_cap = 0;                  // bytes of each
-    void* h_sfo_text[3] = {nullptr, nullptr, nullptr};  // page-locked stations of hc_set_found_from_sfo_text (32 MiB + 64 each), kept
-    hc_sfo_rec* d_found = nullptr;  // grow-only (round 6): room for found_cap records, n_found of them valid
-    uint64_t found_cap = 0;
+    hc_scratch d_found;  // hc_sfo_rec, grow-only (round 6): n_found of them valid
     uint64_t n_found = 0;
-    hc_line_rec* d_found_lines = nullptr;  // hc_found_to_lines_device: the overlap lines of the found records, kept until the store is replaced
-    uint64_t found_lines_cap = 0;
+    hc_scratch d_found_lines;  // hc_line_rec, hc_found_to_lines_device: the overlap lines of the found records, kept until the next call
     double found_err = -1;
     uint32_t found_min = 0, found_flags = 0;
     bool found_valid = false;
     // grow-only workspace for the host-buffer entry points
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    uint64_t ws_cap = 0;
-    unsigned long long* d_totals = nullptr;
+    hc_scratch d_in, d_out;  // hc_overlap_rec / hc_result_rec, as many of each
+    hc_scratch d_totals;     // two unsigned long long
     // candidate reorder (HC_REORDER_*): scratch for the (key, index) radix sort, grow-only
     int reorder_mode = HC_REORDER_AUTO;
-    uint32_t* d_sort = nullptr;  // 4 arrays of sort_cap uint32: keys_in, keys_out, idx_in, perm
-    void* d_sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    uint64_t sort_cap = 0;
+    hc_scratch d_sort, d_sort_tmp;  // d_sort: 4 arrays of as many uint32 each (keys_in, keys_out, idx_in, perm)
     hc_bucket_ws bucket;  // length-bucketed launches on the context's own entry points
     // locality order (hc_locality.hip): the reads sorted by the minimiser of mate /1, built by hc_set_reads for a regular store and kept with
     // it; the per-launch scratch (flag, run boundaries and starts, the launch's permutation) is grow-only and shares `scratch_done`
@@ -253,7 +195,7 @@ struct hc_ctx {
     // the multi-GPU step (hc_set_comm_reserve / hc_comm_gate_device): CUs left free for the collective library's kernels, and the
     // count of workgroups that have started, which the gate kernel on the exchange's stream waits for
     uint32_t comm_reserve = 0;
-    unsigned long long* d_started = nullptr;
+    hc_scratch d_started;  // one unsigned long long
     unsigned long long started_target = 0;  // workgroups launched so far with the counter (host side)
 
     // The context's own scratch (reorder workspace, `bucket`, the sink's segments) serves one launch at a time: a launch that uses
@@ -262,11 +204,7 @@ struct hc_ctx {
     hipStream_t scratch_stream = nullptr;
     bool scratch_used = false;
     // compaction scratch, grow-only
-    void* d_compact_tmp = nullptr;
-    size_t compact_tmp_bytes = 0;
-    uint32_t* d_compact_idx = nullptr;
-    hc_result_rec* d_compact_res = nullptr;
-    uint64_t compact_cap = 0;
+    hc_scratch d_compact_tmp, d_compact_idx, d_compact_res;  // idx: uint32, res: hc_result_rec, as many of each
     // hc_text_set_ids (hc_api_text.cpp): FastqStorage::m_ID_to_index on the device
     hc_scratch id_table, id_keys;
     uint64_t id_size = 0;
@@ -289,8 +227,7 @@ struct hc_ctx {
         uint64_t n_appended = 0;  // records hc_graph_append has put into adm
         bool valid = false;
         // hc_graph_append copies through two page-locked buffers on the context's stream and does not wait for the copy
-        void* h_stage[2] = {nullptr, nullptr};
-        size_t stage_cap[2] = {0, 0};
+        hc_scratch h_stage[2] = {hc_scratch(hipHostMallocDefault), hc_scratch(hipHostMallocDefault)};
         hipEvent_t stage_free[2] = {nullptr, nullptr};
         int stage_turn = 0;
     } graph;

@@ -171,6 +171,51 @@ def test_device_resolution_is_the_serial_insert(seed, paired_frac):
             assert np.array_equal(soff, sgot["in_off"]) and np.array_equal(snodes, sgot["in_nodes"].astype(np.uint64))
 
 
+def test_piecewise_appends_that_outgrow_the_buffer_give_the_same_graph():
+    """hc_graph_append growing with records in place: the device buffer of the appended records starts at 2^24 bytes (349 525
+    records of 48 bytes), so of eight pieces of 50 000 the seventh finds 300 000 records there and the buffer must grow around them.
+    Piecewise against whole, each on a fresh context (the test above pins the device against the host mirror at a size that never
+    grows)."""
+    V, m = 300, 400_000
+    reads, adm = _admitted(7, V, m, 0.5)
+    st = hc.Settings(edge_threshold=0.97, flags=FLAG_RESOLVE_ORIENTATIONS | FLAG_IGNORE_INCLUSIONS)
+    got = []
+    for pieces in (8, 0):
+        with hc.EdgeScorer(st) as sc:
+            sc.set_reads(reads)
+            got.append(sc.graph_resolve(adm, V, pieces=pieces))
+    piecewise, whole = got
+    assert whole["counts"]["first_bad"] == -1 and whole["counts"]["n_edges"] > 0
+    assert piecewise["counts"] == whole["counts"]
+    for k in ("edges", "in_nodes", "seq", "inclusions"):
+        assert piecewise[k].tobytes() == whole[k].tobytes(), k
+
+
+def test_workspaces_regrown_and_reused_on_one_context():
+    """The context's grow-only workspaces of the host-buffer entry points (records in, results out, the four arrays of the reorder's
+    sort, the compaction's buffers): a small batch, a larger one that makes every one of them a new block, and the small one again in
+    the larger blocks, all on one context with the reorder forced — each the bytes a fresh context gives for that batch."""
+    reads, cand, st = _workload("pp")
+    always = 1  # HC_REORDER_ALWAYS
+
+    def both(sc, c):
+        idx, res = sc.score_batch_compact(c)
+        return sc.score_batch(c).tobytes(), idx.tobytes(), res.tobytes()
+
+    want = {}
+    for n in (2000, cand.size):
+        with hc.EdgeScorer(st) as sc:
+            sc.set_reads(reads)
+            sc.set_reorder(always)
+            want[n] = both(sc, cand[:n])
+    assert len(want[cand.size][1]) > len(want[2000][1]) > 0  # (some candidates survive, more of the larger batch)
+    with hc.EdgeScorer(st) as sc:
+        sc.set_reads(reads)
+        sc.set_reorder(always)
+        for n in (2000, cand.size, 2000):
+            assert both(sc, cand[:n]) == want[n], n
+
+
 def test_device_resolution_reports_what_the_edge_constructor_rejects():
     reads, adm = _admitted(5, 50, 500)
     adm["len1"][123] = 0  # Edge::set_len asserts len1 > 0 (src/Edge.h:211-218)
