@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/hcedge.h"
+#include "BlockPipeline.h"
 #include "Edge.h"
 #include "FastqStorage.h"
 #include "Overlap.h"
@@ -121,12 +122,35 @@ public:
     } stats;
 
 private:
-    // One device of the stage: a context with its own copy of the read store and the blocks it has in flight.
+    // One device of the stage: a context with its own copy of the read store and the blocks it has in flight.  It owns its handles
+    // (move-only): the blocks go first, then the text blocks, then the context.
     struct Device {
         hc_ctx* ctx = nullptr;
         int device_id = 0;
         hc_block* blk[2] = {nullptr, nullptr};       // blocks of host-parsed records
         std::vector<hc_textblock*> tblk;             // blocks of the file's text (the device parses): m_text_depth per device
+        hc_block* odd_blk = nullptr;                 // the passing odd lines of a text block are scored as one small block (score_odd_lines):
+        size_t odd_blk_cap = 0;                      // made on the first device's context, so only the first device has one
+        Device() = default;
+        Device(Device&& o) noexcept { swap(o); }
+        Device& operator=(Device&& o) noexcept {  // (o leaves with what this one held)
+            swap(o);
+            return *this;
+        }
+        ~Device() {
+            for (hc_block* b : blk) hc_block_destroy(b);
+            hc_block_destroy(odd_blk);
+            for (hc_textblock* b : tblk) hc_textblock_destroy(b);
+            hc_destroy(ctx);
+        }
+        void swap(Device& o) noexcept {
+            std::swap(ctx, o.ctx);
+            std::swap(device_id, o.device_id);
+            std::swap(blk, o.blk);
+            tblk.swap(o.tblk);
+            std::swap(odd_blk, o.odd_blk);
+            std::swap(odd_blk_cap, o.odd_blk_cap);
+        }
     };
     // What the collector makes of one scored block, in sequence order.
     struct BlockOut {
@@ -140,11 +164,10 @@ private:
         bool keep = false;
         std::vector<Device> devices;
         std::vector<int> device_ids;
-        size_t text_block = 0, odd_blk_cap = 0;
+        size_t text_block = 0;
         uint32_t odd_line_cap = 0;
-        hc_block* odd_blk = nullptr;
     };
-    static Park g_park;
+    static Park& g_park;  // (never destroyed: a process that ends with devices parked leaves them to the system, no HIP call at exit)
     static void park_destroy_locked();
     friend void keep_devices_resident(bool on);
     void run_stage(bool then_sort);
@@ -155,7 +178,7 @@ private:
     bool run_stage_from_found(bool then_sort, uint64_t* n_lines);  // the found records of m_ctx -> lines on the device -> run_stage; false: not the device's
     void score_host_parsed(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc);   // the file tokenised on host threads
     void score_device_parsed(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc); // the file's text sent to the device
-    void finalize_text_block(const IdIndex& ids, const hc_text_row* rows, uint64_t n_rows, BlockOut& out, unsigned threads = 0);
+    void make_text_blocks(Device& d, bool in_constructor = false);  // the text blocks (of m_text_block bytes) this device still lacks of m_text_depth
     // per-line fallback (score_device_parsed): what the host makes of the lines of a block the device's parser did not read
     struct OddLines {
         std::vector<hc_text_row> rows;  // the block's rows with the odd lines' rows spliced in (file order)
@@ -164,12 +187,14 @@ private:
         uint64_t scored = 0;
     };
     void score_odd_lines(const OverlapsParser& parser, const char* block_text, const hc_text_result& tr, OddLines& odd);
-    hc_block* m_odd_blk = nullptr;  // the passing odd lines of a block are scored as one small block
-    size_t m_odd_blk_cap = 0;
-    std::mutex m_odd_mu;
+    std::mutex m_odd_mu;            // (m_dev[0].odd_blk serves all collectors)
     uint32_t m_odd_line_cap = 4096;  // entries of a text block's list of such lines (HC_PARSE_FALLBACK=block: 0, the whole block goes to the host)
     void collect_read_info();
-    void finalize_block(const ParsedBatch& batch, const hc_gather_row* rows, uint64_t n_rows, uint64_t base, BlockOut& out);
+    // src/EdgeCalculator.cpp:404-414 for the rows of a block that the device did not drop; Rows says where a row's line, read indices and
+    // perc come from (BatchRows, TextRows in EdgeCalculator.cpp)
+    template <class Rows>
+    void finalize_rows(const Rows& src, uint64_t n_rows, BlockOut& out, unsigned threads = 0);
+    void run_pieces(unsigned T, bool own_threads, const std::function<void(unsigned)>& piece);
     void consume_block(BlockOut& out);  // serial half: insert (or collect) + nonedge_overlaps.txt, :431-555
     void resolve_on_device(bool sorted);
     void resolve_on_host();
@@ -200,8 +225,8 @@ private:
     std::vector<std::vector<hc_admit_rec>> m_admitted;  // admitted candidates of the whole file, block by block, in sequence order
     // The device's copy of a block's admitted records leaves from a thread of its own: the in-order half of the collectors only
     // queues (pointer, count) — the staging copy and the three HIP calls of hc_graph_append took 0.25 ms of every block's turn.
-    struct Appender;
-    std::unique_ptr<Appender> m_appender;
+    // (consume_block asks m_appender->failed(): a failed append stops the stage at the block it is at, not after the whole file)
+    std::unique_ptr<JobThread> m_appender;
     void start_appender();
     void finish_appender(bool rethrow);  // every queued append issued, the thread joined; its first error thrown if asked
 };

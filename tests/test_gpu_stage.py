@@ -572,3 +572,57 @@ def test_blocks_where_most_lines_survive_stay_on_the_device(oracle, tmp_path, mo
     assert (out / "nonedge_overlaps.txt").read_bytes() == (d / "ref_nonedge.txt").read_bytes()
     for k in ("inclusion_count", "dup_count", "edges_added", "nonedges_written", "prefilter_rejected", "lines_read", "scored"):
         assert c[k] == getattr(oc, k), k
+
+
+@pytest.mark.parametrize("env", [{"HC_TEXT_BLOCK": "4096"}, {"HC_TEXT_BLOCK": "4096", "HC_TEXT_DEPTH": "1", "HC_COLLECTORS": "2"},
+                                 {"HC_PARSE": "host", "HC_STAGE_BLOCK": "700"}], ids=["text-blocks", "depth-1-two-collectors", "host-parsed"])
+def test_error_in_a_middle_block_leaves_the_devices_usable(tmp_path, monkeypatch, env):
+    """A line the reference exits on, in the middle of a file of many blocks: the stage raises what a one-block run of the same file raises,
+    and — in a process that keeps its devices — the next stage, on the parked devices and block objects of the failed one, builds the graph,
+    counters and nonedge_overlaps.txt of a stage with devices of its own.  A block object left in flight by the failed stage, or a parked
+    device destroyed by halves, fails the second stage."""
+    reads, meta = synth.make_paired_dataset(400, 1500, flip_frac=0.25, seed=91)
+    cand = synth.paired_candidates(meta, n_candidates=3000, seed=92)
+    lines = synth.records_to_lines(cand, reads)
+    good, bad = str(tmp_path / "overlaps.txt"), str(tmp_path / "bad.txt")
+    open(good, "w").write("\n".join(lines) + "\n")
+    lines[len(lines) // 2] = "0\t1\t0\t-\t-\t*\t+\t100\t-\t10\t-\ts\ts"  # ori '*': the reference exits (test_stage_errors)
+    open(bad, "w").write("\n".join(lines) + "\n")
+    assert os.path.getsize(bad) > 20 * 4096
+    p1, p2 = str(tmp_path / "p1.fastq"), str(tmp_path / "p2.fastq")
+    reads.write_fastq(None, p1, p2)
+    st = hc.Settings(edge_threshold=0.97, min_overlap_len=150, n_threads=4)
+
+    def fails(tag):
+        out = tmp_path / tag
+        out.mkdir()
+        with host.EdgeCalculatorStage(st, paired1=p1, paired2=p2, overlaps=bad, output_dir=str(out) + "/") as ec:
+            with pytest.raises(hc.HcError) as e:
+                ec.construct_edges()
+        return str(e.value)
+
+    def builds(tag):
+        out = tmp_path / tag
+        out.mkdir()
+        with host.EdgeCalculatorStage(st, paired1=p1, paired2=p2, overlaps=good, output_dir=str(out) + "/") as ec:
+            ec.construct_edges()
+            c = ec.counters()
+            # (not the times; and a taken-over text block may arrive with the row buffers it grew before)
+            counters = {k: v for k, v in c.items() if not k.startswith("t_") and k != "regrown_blocks"}
+            return ec.edges().tobytes(), ec.inclusions().tobytes(), counters, (out / "nonedge_overlaps.txt").read_bytes()
+
+    one_block_text = fails("bad_one_block")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    want = builds("own_devices")
+    assert len(want[0]) > 0
+    if "HC_TEXT_BLOCK" in env:
+        assert want[2]["device_blocks"] + want[2]["host_blocks"] >= 20, "the bad line is meant to sit in a middle block"
+    host.keep_devices(True)
+    try:
+        assert fails("bad_many_blocks") == one_block_text
+        got = builds("after_the_error")
+    finally:
+        host.keep_devices(False)
+    assert got[2] == want[2]
+    assert got[0] == want[0] and got[1] == want[1] and got[3] == want[3]
