@@ -188,6 +188,7 @@ _sig = {
     "hc_textblock_list_nonplain": (C.c_int, [_vp, C.c_uint32]),
     "hc_textblock_destroy": (C.c_int, [_vp]),
     "hc_textblock_regrown": (C.c_uint64, [_vp]),
+    "hc_textblock_max_lines": (C.c_uint64, [_vp]),
     "hc_textblock_reserve_rows": (C.c_int, [_vp, C.c_uint64]),
     "hc_graph_begin": (C.c_int, [_vp]),
     "hc_graph_append": (C.c_int, [_vp, _vp, C.c_uint64]),

@@ -14,6 +14,11 @@
 // hc_textblock_list_nonplain) LISTED with its number and span, so that the host takes just that line through its own tokeniser +
 // Overlap constructor, which own every error the reference can raise, and splices the verdict in at its place in file order;
 // without a list (or with more such lines than the list holds) the host takes the whole block.
+// The grammar of a plain line: thirteen fields separated by single tabs, nothing behind the last; ids of 1 - 18 decimal digits without a
+// leading 0 (but "0"); POS / PERC / LEN "-" (read as 0) or 1 - 9 decimal digits; ORD, ORI, TYPE one byte each; POS2 "-" sets PERC2 = LEN2 = 0;
+// ORI + or -, PERC <= 100, TYPE s or p, ORD "-" when a type is s, else 1 or 2.  Overlap::from_plain_line (host/host_model.cpp) is the same
+// rule set on the host.  The reader's per-line pin is tests/test_gpu_text_reader.py: line starts, listed spans and parsed records against the
+// plain restatement tests/_overlap_lines.py, at every piece / tile / scan-round / staging / window edge named above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -33,6 +33,9 @@ TEXT_ROW_DTYPE = np.dtype([("row", ROW_DTYPE), ("line", LINE_DTYPE)], align=Fals
 assert TEXT_ROW_DTYPE.itemsize == 80
 TEXT_REJECT_DTYPE = np.dtype([("line_index", "<u4"), ("pad", "<u4"), ("line", LINE_DTYPE)], align=False)
 assert TEXT_REJECT_DTYPE.itemsize == 56
+# hc_text_nonplain, 16 bytes: a line the device's reader does not read, with its span in the block's text
+TEXT_NONPLAIN_DTYPE = np.dtype([("line_index", "<u4"), ("begin", "<u4"), ("length", "<u4"), ("pad", "<u4")], align=False)
+assert TEXT_NONPLAIN_DTYPE.itemsize == 16
 
 # hc_admit_rec, 48 bytes: an admitted candidate handed to the device's duplicate resolution
 ADMIT_DTYPE = np.dtype([("score", "<f8"), ("read1", "<u4"), ("read2", "<u4"), ("pos1", "<u4"), ("pos2", "<u4"), ("mm", "<u4"), ("n", "<u4"),

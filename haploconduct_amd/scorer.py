@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .records import ADMIT_DTYPE, CAND_DTYPE, OVERLAP_DTYPE, REC_COMPACT, REC_FULL, RESULT_DTYPE, ROW_DTYPE, TEXT_REJECT_DTYPE, TEXT_ROW_DTYPE, Settings
+from .records import ADMIT_DTYPE, CAND_DTYPE, OVERLAP_DTYPE, REC_COMPACT, REC_FULL, RESULT_DTYPE, ROW_DTYPE, TEXT_NONPLAIN_DTYPE, TEXT_REJECT_DTYPE, TEXT_ROW_DTYPE, Settings
 
 
 def _ptr(a):
@@ -218,23 +218,27 @@ class EdgeScorer:
         ids = np.ascontiguousarray(read_ids, dtype=np.uint64)
         N.check(N.lib.hc_text_set_ids(self._ctx, _ptr(ids), ids.shape[0]), "hc_text_set_ids")
 
-    def score_text(self, text, block_bytes=1 << 20, first_line_no=0, chained=False, reserve_rows=0):
-        """The overlaps file's TEXT through hc_textblock_submit / hc_textblock_wait, block by block (cut at line ends).
-        Returns a list with one dict per block: the hc_text_result fields, rows / rejected as numpy copies.
+    def score_text(self, text, block_bytes=1 << 20, first_line_no=0, chained=False, reserve_rows=0, list_nonplain=0, max_bytes=None):
+        """The overlaps file's TEXT through hc_textblock_submit / hc_textblock_wait, block by block (cut at line ends; an empty text is
+        one empty block).  Returns a list with one dict per block: the hc_text_result fields, rows / rejected as numpy copies.
         chained: hc_textblock_submit_from — the text goes to the device straight from `text`, two blocks in flight, line
         numbers through an hc_linechain (first_line_no must be 0).  reserve_rows: hc_textblock_reserve_rows before the first submit;
-        every dict carries "regrown" = hc_textblock_regrown of the block so far."""
+        every dict carries "regrown" = hc_textblock_regrown of the block so far.  list_nonplain: hc_textblock_list_nonplain with that
+        many entries before the first submit (True: hc_textblock_max_lines of them); every dict then carries "nonplain", a copy of the
+        listed lines (TEXT_NONPLAIN_DTYPE), and "max_lines".  max_bytes: the size the blocks are created with (None: block_bytes)."""
         raw = text if isinstance(text, bytes) else text.encode()
+        max_bytes = max(block_bytes if max_bytes is None else max_bytes, 64)
         if chained:
-            return self._score_text_chained(raw, block_bytes)
+            return self._score_text_chained(raw, block_bytes, list_nonplain, max_bytes)
         b = C.c_void_p()
-        N.check(N.lib.hc_textblock_create(self._ctx, max(block_bytes, 64), C.byref(b)), "hc_textblock_create")
+        N.check(N.lib.hc_textblock_create(self._ctx, max_bytes, C.byref(b)), "hc_textblock_create")
         out, at, line_no, base = [], 0, first_line_no, 0
         try:
             if reserve_rows:
                 N.check(N.lib.hc_textblock_reserve_rows(b, reserve_rows), "hc_textblock_reserve_rows")
+            self._list_nonplain(b, list_nonplain)
             buf = N.lib.hc_textblock_buffer(b)
-            while at < len(raw):
+            while at < len(raw) or not out:
                 end = min(len(raw), at + block_bytes)
                 if end < len(raw):
                     nl = raw.rfind(b"\n", at, end)
@@ -245,10 +249,7 @@ class EdgeScorer:
                 N.check(N.lib.hc_textblock_submit(b, end - at, line_no, base), "hc_textblock_submit")
                 r = N.hc_text_result()
                 N.check(N.lib.hc_textblock_wait(b, C.byref(r)), "hc_textblock_wait")
-                d = {k: getattr(r, k) for k, _ in r._fields_ if k not in ("rows", "rejected")}
-                d["rows"] = np.frombuffer((C.c_char * (r.n_rows * 80)).from_address(r.rows), dtype=TEXT_ROW_DTYPE).copy() if r.n_rows else np.zeros(0, TEXT_ROW_DTYPE)
-                d["rejected"] = (np.frombuffer((C.c_char * (r.n_rejected * 56)).from_address(r.rejected), dtype=TEXT_REJECT_DTYPE).copy()
-                                 if r.n_rejected else np.zeros(0, TEXT_REJECT_DTYPE))
+                d = self._text_result(b, r, list_nonplain)
                 d["base"], d["bytes"] = base, (at, end)
                 d["regrown"] = int(N.lib.hc_textblock_regrown(b))
                 out.append(d)
@@ -259,9 +260,27 @@ class EdgeScorer:
             N.lib.hc_textblock_destroy(b)
         return out
 
-    def _score_text_chained(self, raw, block_bytes):
+    @staticmethod
+    def _list_nonplain(b, list_nonplain):
+        if list_nonplain:
+            n = int(N.lib.hc_textblock_max_lines(b)) if list_nonplain is True else int(list_nonplain)
+            N.check(N.lib.hc_textblock_list_nonplain(b, n), "hc_textblock_list_nonplain")
+
+    @staticmethod
+    def _text_result(b, r, list_nonplain):
+        d = {k: getattr(r, k) for k, _ in r._fields_ if k not in ("rows", "rejected", "nonplain")}
+        d["rows"] = np.frombuffer((C.c_char * (r.n_rows * 80)).from_address(r.rows), dtype=TEXT_ROW_DTYPE).copy() if r.n_rows else np.zeros(0, TEXT_ROW_DTYPE)
+        d["rejected"] = (np.frombuffer((C.c_char * (r.n_rejected * 56)).from_address(r.rejected), dtype=TEXT_REJECT_DTYPE).copy()
+                         if r.n_rejected else np.zeros(0, TEXT_REJECT_DTYPE))
+        if list_nonplain:
+            d["nonplain"] = (np.frombuffer((C.c_char * (r.n_nonplain_listed * 16)).from_address(r.nonplain), dtype=TEXT_NONPLAIN_DTYPE).copy()
+                             if r.n_nonplain_listed else np.zeros(0, TEXT_NONPLAIN_DTYPE))
+            d["max_lines"] = int(N.lib.hc_textblock_max_lines(b))
+        return d
+
+    def _score_text_chained(self, raw, block_bytes, list_nonplain, max_bytes):
         cuts, at = [], 0
-        while at < len(raw):
+        while at < len(raw) or not cuts:
             end = min(len(raw), at + block_bytes)
             if end < len(raw):
                 nl = raw.rfind(b"\n", at, end)
@@ -274,7 +293,8 @@ class EdgeScorer:
         blocks = [C.c_void_p(), C.c_void_p()]
         chain = C.c_void_p()
         for b in blocks:
-            N.check(N.lib.hc_textblock_create(self._ctx, max(block_bytes, 64), C.byref(b)), "hc_textblock_create")
+            N.check(N.lib.hc_textblock_create(self._ctx, max_bytes, C.byref(b)), "hc_textblock_create")
+            self._list_nonplain(b, list_nonplain)
         N.check(N.lib.hc_linechain_create(self._ctx, len(cuts), C.byref(chain)), "hc_linechain_create")
         out, base = [], 0
 
@@ -282,10 +302,7 @@ class EdgeScorer:
             nonlocal base
             r = N.hc_text_result()
             N.check(N.lib.hc_textblock_wait(blocks[k % 2], C.byref(r)), "hc_textblock_wait")
-            d = {f: getattr(r, f) for f, _ in r._fields_ if f not in ("rows", "rejected")}
-            d["rows"] = np.frombuffer((C.c_char * (r.n_rows * 80)).from_address(r.rows), dtype=TEXT_ROW_DTYPE).copy() if r.n_rows else np.zeros(0, TEXT_ROW_DTYPE)
-            d["rejected"] = (np.frombuffer((C.c_char * (r.n_rejected * 56)).from_address(r.rejected), dtype=TEXT_REJECT_DTYPE).copy()
-                             if r.n_rejected else np.zeros(0, TEXT_REJECT_DTYPE))
+            d = self._text_result(blocks[k % 2], r, list_nonplain)
             d["base"], d["bytes"] = base, cuts[k]
             base += r.n_lines
             out.append(d)
@@ -294,7 +311,8 @@ class EdgeScorer:
             for k, (a, e) in enumerate(cuts):
                 if k >= 2:
                     collect(k - 2)
-                N.check(N.lib.hc_textblock_submit_from(blocks[k % 2], src.ctypes.data + a, e - a, chain, k, blocks[(k - 1) % 2] if k else None, 0),
+                N.check(N.lib.hc_textblock_submit_from(blocks[k % 2], (src.ctypes.data + a) if e > a else None, e - a, chain, k,
+                                                       blocks[(k - 1) % 2] if k else None, 0),
                         "hc_textblock_submit_from")
             for k in range(max(0, len(cuts) - 2), len(cuts)):
                 collect(k)

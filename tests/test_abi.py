@@ -42,14 +42,14 @@ def test_record_layouts(tmp_path):
     import subprocess
 
     from haploconduct_amd.host import EDGE_DTYPE
-    from haploconduct_amd.records import ADMIT_DTYPE, CAND_DTYPE, LINE_DTYPE, ROW_DTYPE, SFO_DTYPE, TEXT_REJECT_DTYPE, TEXT_ROW_DTYPE
+    from haploconduct_amd.records import ADMIT_DTYPE, CAND_DTYPE, LINE_DTYPE, ROW_DTYPE, SFO_DTYPE, TEXT_NONPLAIN_DTYPE, TEXT_REJECT_DTYPE, TEXT_ROW_DTYPE
 
     assert OVERLAP_DTYPE.itemsize == 32 and RESULT_DTYPE.itemsize == 24
     assert OVERLAP_DTYPE.fields["ord"][1] == 18 and OVERLAP_DTYPE.fields["perc"][1] == 28
     assert RESULT_DTYPE.fields["n_cls"][1] == 20
     views = {"hc_overlap_rec": OVERLAP_DTYPE, "hc_cand_rec": CAND_DTYPE, "hc_result_rec": RESULT_DTYPE, "hc_gather_row": ROW_DTYPE,
              "hc_admit_rec": ADMIT_DTYPE, "hc_edge_rec": EDGE_DTYPE, "hc_sfo_rec": SFO_DTYPE, "hc_line_rec": LINE_DTYPE,
-             "hc_text_row": TEXT_ROW_DTYPE, "hc_text_reject": TEXT_REJECT_DTYPE}
+             "hc_text_row": TEXT_ROW_DTYPE, "hc_text_reject": TEXT_REJECT_DTYPE, "hc_text_nonplain": TEXT_NONPLAIN_DTYPE}
     probes = []
     for name, dt in views.items():
         tag = "struct hc_gather_row" if name == "hc_gather_row" else name

@@ -454,3 +454,32 @@ def test_the_sfo_files_text_read_on_the_device(tmp_path):
         want = sc.found_to_lines(ns, npairs)
         assert sc.set_found_from_sfo_text(big_text) == big.size
         assert sc.found_to_lines(ns, npairs).tobytes() == want.tobytes() and want.size > 100000
+
+
+def test_sfo_text_lengths_mod_16_behind_a_longer_text():
+    """hc_set_found_from_sfo_text splits its text with the overlaps reader's line kernels (text_count / text_scan / text_lines,
+    csrc/hc_text_kernels.hip), whose last 16-byte piece reaches past the text: canonical texts of every length mod 16, with and without the
+    last newline, each after a longer text has gone through the same context — the record count and the overlap lines of the records
+    themselves (hc_set_found_records)."""
+    rng = np.random.default_rng(29)
+    ns, npairs = 40, 60
+    reads = hc.ReadSet.from_lists([(b"ACGT" * 10, b"I" * 40)] * ns, [((b"ACGT" * 10, b"I" * 40), (b"TGCA" * 10, b"I" * 40))] * npairs)
+    recs = _random_sfo(rng, ns + 2 * npairs, 400)
+    longer = _sfo_text(recs)
+    cases = {}  # (length mod 16, last newline) -> number of records, the fewest that give it (from 8 up: more than one 16-byte piece per lane's worth)
+    for k in range(8, 200):
+        t = _sfo_text(recs[:k])
+        cases.setdefault((len(t) % 16, True), k)
+        cases.setdefault(((len(t) - 1) % 16, False), k)
+    assert set(cases) == {(r, nl) for r in range(16) for nl in (True, False)}
+    with hc.EdgeScorer(hc.Settings()) as sc:
+        sc.set_reads(reads)
+        for (r, nl), k in sorted(cases.items()):
+            t = _sfo_text(recs[:k])
+            t = t if nl else t[:-1]
+            assert len(t) % 16 == r and len(t) < len(longer)
+            sc.set_found_records(recs[:k])
+            want = sc.found_to_lines(ns, npairs)
+            assert sc.set_found_from_sfo_text(longer) == recs.size
+            assert sc.set_found_from_sfo_text(t) == k, (r, nl, k)
+            assert sc.found_to_lines(ns, npairs).tobytes() == want.tobytes(), (r, nl, k)

@@ -10,6 +10,7 @@ import pytest
 
 import haploconduct_amd as hc
 from haploconduct_amd import host, synth
+from tests._overlap_lines import mutated
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -245,23 +246,8 @@ def test_one_pass_line_reader_agrees_with_the_general_path(oracle):
     """The stage reads plain lines in one pass (Overlap::from_plain_line) and everything else through the reference's
     tokenise + construct steps; mutate valid lines character by character and require both routes — and the oracle —
     to agree on acceptance and on every field."""
-    rng = random.Random(17)
-
-    def valid():
-        t1, t2 = rng.choice("sp"), rng.choice("sp")
-        ss = t1 == t2 == "s"
-        return "\t".join([str(rng.choice([0, 7, 10, 123456, 99999999, 123456789012345678])), str(rng.randrange(5000)),
-                          str(rng.randrange(300)), "-" if ss else str(rng.randrange(300)), rng.choice("12") if t1 == t2 == "p" else "-",
-                          rng.choice("+-"), rng.choice("+-"), str(rng.randrange(101)), "-" if ss else str(rng.randrange(101)),
-                          str(rng.randrange(1, 999999999)), "-" if ss else str(rng.randrange(500)), t1, t2])
-
-    junk = ["\t", " ", "0", "9", "-", "+", "x", "s", "p", "1", "\r", "00", "1234567890", "0x1f", "101", ""]
     n_plain = n_general = n_bad = 0
-    for it in range(6000):
-        line = valid()
-        for _ in range(rng.choice([0, 0, 1, 1, 2, 4])):
-            k = rng.randrange(len(line) + 1)
-            line = line[:k] + rng.choice(junk) + line[k + rng.choice([0, 1, 1]):]
+    for line in mutated(17, 6000):
         for sp in (False, True):
             rc, o = host.parse_overlap(line, sp)
             rc2, o2 = host.parse_overlap(line, sp, general_only=True)
