@@ -23,6 +23,7 @@
 #include "hc_ctx.h"
 #include "hc_prims.h"
 #include "hc_sr.h"
+#include "hc_sr_merge_next.h"
 #include "hc_sr_next.h"
 #include "hc_sr_self.h"
 #include "host/InBlocks.h"
@@ -533,8 +534,15 @@ extern "C" int hc_sr_merge_self_overlaps_kept(hc_ctx* c, const hc_sr_pair* pairs
     if (!(settings->min_qual == settings->min_qual)) return fail(HC_ERR_ARG, me + "min_qual is NaN");
     if (n_pairs >= (1ull << 32) - 1) return fail(HC_ERR_ARG, me + "more than 2^32 - 2 pairs");
     if (!c->srn.keep) return fail(HC_ERR_STATE, me + "hc_sr_keep_device is off");
+    if (!c->sr.kept_valid) return fail(HC_ERR_STATE, me + "no kept consensus bytes (hc_sr_consensus, hc_sr_edge_merge or hc_sr_kept_load first)");
+    return hc::sr_self_kept_run(c, me.c_str(), pairs, n_pairs, settings, overlap_pos, score, status, out_off, n_out, stats);
+}
+
+// hc_sr_merge_self_overlaps_kept behind its checks: hc_sr_merge_next (hc_api_sr_merge_next.cpp) runs the same on the pairs it builds
+int hc::sr_self_kept_run(hc_ctx* c, const char* me_, const hc_sr_pair* pairs, uint64_t n_pairs, const hc_sr_self_settings* settings,
+                         int32_t* overlap_pos, double* score, uint32_t* status, uint64_t* out_off, uint64_t* n_out, hc_sr_self_stats* stats) {
+    const std::string me = me_;
     hc_ctx::Sr& K = c->sr;
-    if (!K.kept_valid) return fail(HC_ERR_STATE, me + "no kept consensus bytes (hc_sr_consensus, hc_sr_edge_merge or hc_sr_kept_load first)");
     if (stats) memset(stats, 0, sizeof *stats);
     const uint64_t base = K.kept_bytes;
     *n_out = 0;

@@ -12,6 +12,7 @@
 #include "../../include/hcsr.h"
 #include "hc_ctx.h"
 #include "hc_prims.h"
+#include "hc_sr_merge_next.h"
 #include "hc_sr_next.h"
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
@@ -36,72 +37,18 @@ extern "C" int hc_sr_keep_device(hc_ctx* c, int on) {
     return HC_OK;
 }
 
-extern "C" int hc_sr_set_next_reads(hc_ctx* c, const hc_sr_next_entry* entries, uint64_t n, const uint8_t* extra_seq, const uint8_t* extra_qual,
-                                    uint64_t n_extra, const hc_sr_next_settings* settings, int32_t* new_id, uint32_t* status,
-                                    hc_sr_next_counts* counts) {
-    const char* me = "hc_sr_set_next_reads: ";
-    if (!c || !settings || (n && (!entries || !new_id || !status)) || (n_extra && (!extra_seq || !extra_qual)))
-        return fail(HC_ERR_ARG, std::string(me) + "null argument");
-    if (n >= (1ull << 31)) return fail(HC_ERR_ARG, std::string(me) + "2^31 entries or more");
+// From "the entries, their statuses and the two sums are on the device" on: the survivors' bytes are gathered, the host plans as
+// hc_set_reads does and the encoder runs on the new raw arrays.  hc_sr_set_next_reads and hc_sr_merge_next both end here.
+int hc::sr_next_store(hc_ctx* c, uint64_t n, uint64_t n_extra, uint32_t n_kept, uint32_t n_seq, uint64_t total, hc_sr_next_counts& cn) {
     hc_ctx::SrNext& N = c->srn;
-    if (!N.keep) return fail(HC_ERR_STATE, std::string(me) + "hc_sr_keep_device is off");
-    if (!c->have_reads || !N.raw_valid) return fail(HC_ERR_STATE, std::string(me) + "no store whose raw arrays were kept (hc_sr_keep_device, then hc_set_reads)");
-    hc_sr_next_counts cn;
-    memset(&cn, 0, sizeof cn);
-    if (counts) *counts = cn;
-    if (n == 0) return HC_SR_NEXT_EMPTY;
-    HC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const uint32_t n_reads_old = (uint32_t)(N.h_first.size() - 1);
     const hc::SrNextSources S{c->sr.kept_valid ? c->sr.kept_bytes : 0, n_extra, N.off.as<uint64_t>(), N.first.as<uint32_t>(), n_reads_old};
-    const size_t scan_bytes = hc::prims::scan_temp_bytes(n + 1, sizeof(uint64_t));
-    int rc;
-    if ((rc = N.entries.ensure(n * sizeof(hc_sr_next_entry))) || (rc = N.status.ensure(n * sizeof(uint32_t))) ||
-        (rc = N.cnt.ensure((n + 1) * sizeof(uint64_t))) || (rc = N.bytes.ensure((n + 1) * sizeof(uint64_t))) ||
-        (rc = N.cnt_off.ensure((n + 1) * sizeof(uint64_t))) || (rc = N.byte_off.ensure((n + 1) * sizeof(uint64_t))) ||
-        (rc = N.temp.ensure(scan_bytes ? scan_bytes : 16)) || (rc = N.hist.ensure(512 * sizeof(unsigned long long))) ||
-        (rc = N.extra_seq.ensure(n_extra ? n_extra : 1)) || (rc = N.extra_qual.ensure(n_extra ? n_extra : 1)))
-        return rc;
     const hc::SrNextBytes B{{c->sr.seq.as<uint8_t>(), N.extra_seq.as<uint8_t>(), N.bases.as<uint8_t>()},
                             {c->sr.qual.as<uint8_t>(), N.extra_qual.as<uint8_t>(), N.quals.as<uint8_t>()}};
-    HC_HIP(hipMemcpyAsync(N.entries.p, entries, n * sizeof(hc_sr_next_entry), hipMemcpyHostToDevice, s));
-    if (n_extra) {
-        HC_HIP(hipMemcpyAsync(N.extra_seq.p, extra_seq, n_extra, hipMemcpyHostToDevice, s));
-        HC_HIP(hipMemcpyAsync(N.extra_qual.p, extra_qual, n_extra, hipMemcpyHostToDevice, s));
-    }
-    float ms_a = 0, ms_b = 0;
-    HC_HIP(hipEventRecord(c->ev0, s));
-    HC_HIP(hc::sr_next_launch_check(N.entries.as<hc_sr_next_entry>(), n, S, B, settings->keep_singletons, N.status.as<uint32_t>(), N.cnt.as<uint64_t>(),
-                                    N.bytes.as<uint64_t>(), s));
-    HC_HIP(hc::prims::exclusive_sum(N.temp.p, N.temp.cap, N.cnt.as<uint64_t>(), N.cnt_off.as<uint64_t>(), n + 1, s));
-    HC_HIP(hc::prims::exclusive_sum(N.temp.p, N.temp.cap, N.bytes.as<uint64_t>(), N.byte_off.as<uint64_t>(), n + 1, s));
-    HC_HIP(hipEventRecord(c->ev1, s));
-    uint64_t tot[2] = {0, 0};  // kept | sequences << 32, bytes
-    HC_HIP(hipMemcpyAsync(&tot[0], N.cnt_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HC_HIP(hipMemcpyAsync(&tot[1], N.byte_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HC_HIP(hipMemcpyAsync(status, N.status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HC_HIP(hipStreamSynchronize(s));
-    HC_HIP(hipEventElapsedTime(&ms_a, c->ev0, c->ev1));
-    const uint32_t n_kept = (uint32_t)tot[0], n_seq = (uint32_t)(tot[0] >> 32);
-    const uint64_t total = tot[1];
-    {
-        int32_t rank = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint32_t st = status[i];
-            new_id[i] = st == HC_SR_NEXT_KEPT ? rank++ : -1;
-            cn.n_kept += st == HC_SR_NEXT_KEPT;
-            cn.n_dropped_empty += st == HC_SR_NEXT_DROPPED_EMPTY;
-            cn.n_dropped_n_rate += st == HC_SR_NEXT_DROPPED_N_RATE;
-            cn.n_dropped_short += st == HC_SR_NEXT_DROPPED_SHORT;
-            cn.n_bad += st == HC_SR_NEXT_BAD_ENTRY;
-        }
-    }
-    cn.n_seq = n_seq;
-    cn.n_bytes = total;
-    cn.ms_device = ms_a;
-    if (counts) *counts = cn;
-    if (cn.n_kept != n_kept) return fail(HC_ERR_STATE, std::string(me) + "the statuses and the device's count of survivors disagree");
-    if (n_kept == 0) return HC_SR_NEXT_EMPTY;  // the old store stays
+    int rc;
+    float ms_b = 0;
+    if ((rc = N.hist.ensure(512 * sizeof(unsigned long long)))) return rc;
     // the survivors' bytes, the new offsets and the byte histograms
     if ((rc = N.next_bases.ensure_exact(total)) || (rc = N.next_quals.ensure_exact(total)) ||
         (rc = N.next_off.ensure_exact(sizeof(uint64_t) * ((size_t)n_seq + 1))) || (rc = N.next_first.ensure_exact(sizeof(uint32_t) * ((size_t)n_kept + 1))))
@@ -147,7 +94,77 @@ extern "C" int hc_sr_set_next_reads(hc_ctx* c, const hc_sr_next_entry* entries, 
     N.h_first.swap(h_first);
     N.total = total;
     N.raw_valid = true;
-    cn.ms_device = (double)ms_a + ms_b;
+    cn.ms_device += ms_b;
+    return HC_OK;
+}
+
+extern "C" int hc_sr_set_next_reads(hc_ctx* c, const hc_sr_next_entry* entries, uint64_t n, const uint8_t* extra_seq, const uint8_t* extra_qual,
+                                    uint64_t n_extra, const hc_sr_next_settings* settings, int32_t* new_id, uint32_t* status,
+                                    hc_sr_next_counts* counts) {
+    const char* me = "hc_sr_set_next_reads: ";
+    if (!c || !settings || (n && (!entries || !new_id || !status)) || (n_extra && (!extra_seq || !extra_qual)))
+        return fail(HC_ERR_ARG, std::string(me) + "null argument");
+    if (n >= (1ull << 31)) return fail(HC_ERR_ARG, std::string(me) + "2^31 entries or more");
+    hc_ctx::SrNext& N = c->srn;
+    if (!N.keep) return fail(HC_ERR_STATE, std::string(me) + "hc_sr_keep_device is off");
+    if (!c->have_reads || !N.raw_valid) return fail(HC_ERR_STATE, std::string(me) + "no store whose raw arrays were kept (hc_sr_keep_device, then hc_set_reads)");
+    hc_sr_next_counts cn;
+    memset(&cn, 0, sizeof cn);
+    if (counts) *counts = cn;
+    if (n == 0) return HC_SR_NEXT_EMPTY;
+    HC_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const uint32_t n_reads_old = (uint32_t)(N.h_first.size() - 1);
+    const hc::SrNextSources S{c->sr.kept_valid ? c->sr.kept_bytes : 0, n_extra, N.off.as<uint64_t>(), N.first.as<uint32_t>(), n_reads_old};
+    const size_t scan_bytes = hc::prims::scan_temp_bytes(n + 1, sizeof(uint64_t));
+    int rc;
+    if ((rc = N.entries.ensure(n * sizeof(hc_sr_next_entry))) || (rc = N.status.ensure(n * sizeof(uint32_t))) ||
+        (rc = N.cnt.ensure((n + 1) * sizeof(uint64_t))) || (rc = N.bytes.ensure((n + 1) * sizeof(uint64_t))) ||
+        (rc = N.cnt_off.ensure((n + 1) * sizeof(uint64_t))) || (rc = N.byte_off.ensure((n + 1) * sizeof(uint64_t))) ||
+        (rc = N.temp.ensure(scan_bytes ? scan_bytes : 16)) || (rc = N.hist.ensure(512 * sizeof(unsigned long long))) ||
+        (rc = N.extra_seq.ensure(n_extra ? n_extra : 1)) || (rc = N.extra_qual.ensure(n_extra ? n_extra : 1)))
+        return rc;
+    const hc::SrNextBytes B{{c->sr.seq.as<uint8_t>(), N.extra_seq.as<uint8_t>(), N.bases.as<uint8_t>()},
+                            {c->sr.qual.as<uint8_t>(), N.extra_qual.as<uint8_t>(), N.quals.as<uint8_t>()}};
+    HC_HIP(hipMemcpyAsync(N.entries.p, entries, n * sizeof(hc_sr_next_entry), hipMemcpyHostToDevice, s));
+    if (n_extra) {
+        HC_HIP(hipMemcpyAsync(N.extra_seq.p, extra_seq, n_extra, hipMemcpyHostToDevice, s));
+        HC_HIP(hipMemcpyAsync(N.extra_qual.p, extra_qual, n_extra, hipMemcpyHostToDevice, s));
+    }
+    float ms_a = 0;
+    HC_HIP(hipEventRecord(c->ev0, s));
+    HC_HIP(hc::sr_next_launch_check(N.entries.as<hc_sr_next_entry>(), n, S, B, settings->keep_singletons, N.status.as<uint32_t>(), N.cnt.as<uint64_t>(),
+                                    N.bytes.as<uint64_t>(), s));
+    HC_HIP(hc::prims::exclusive_sum(N.temp.p, N.temp.cap, N.cnt.as<uint64_t>(), N.cnt_off.as<uint64_t>(), n + 1, s));
+    HC_HIP(hc::prims::exclusive_sum(N.temp.p, N.temp.cap, N.bytes.as<uint64_t>(), N.byte_off.as<uint64_t>(), n + 1, s));
+    HC_HIP(hipEventRecord(c->ev1, s));
+    uint64_t tot[2] = {0, 0};  // kept | sequences << 32, bytes
+    HC_HIP(hipMemcpyAsync(&tot[0], N.cnt_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipMemcpyAsync(&tot[1], N.byte_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipMemcpyAsync(status, N.status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HC_HIP(hipStreamSynchronize(s));
+    HC_HIP(hipEventElapsedTime(&ms_a, c->ev0, c->ev1));
+    const uint32_t n_kept = (uint32_t)tot[0], n_seq = (uint32_t)(tot[0] >> 32);
+    const uint64_t total = tot[1];
+    {
+        int32_t rank = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint32_t st = status[i];
+            new_id[i] = st == HC_SR_NEXT_KEPT ? rank++ : -1;
+            cn.n_kept += st == HC_SR_NEXT_KEPT;
+            cn.n_dropped_empty += st == HC_SR_NEXT_DROPPED_EMPTY;
+            cn.n_dropped_n_rate += st == HC_SR_NEXT_DROPPED_N_RATE;
+            cn.n_dropped_short += st == HC_SR_NEXT_DROPPED_SHORT;
+            cn.n_bad += st == HC_SR_NEXT_BAD_ENTRY;
+        }
+    }
+    cn.n_seq = n_seq;
+    cn.n_bytes = total;
+    cn.ms_device = ms_a;
+    if (counts) *counts = cn;
+    if (cn.n_kept != n_kept) return fail(HC_ERR_STATE, std::string(me) + "the statuses and the device's count of survivors disagree");
+    if (n_kept == 0) return HC_SR_NEXT_EMPTY;  // the old store stays
+    if ((rc = hc::sr_next_store(c, n, n_extra, n_kept, n_seq, total, cn))) return rc;
     if (counts) *counts = cn;
     return HC_OK;
 }

@@ -276,6 +276,13 @@ struct hc_ctx {
     struct SrEdge {
         hc_scratch targets, pairs, vread, vfwd, status, lay_cnt, mem_cnt, first, mem_off, layouts, members, who, sub, temp;
     } sr_edge;
+    // hc_sr_merge_next (hc_api_sr_merge_next.cpp): grow-only scratch — the call's inputs; its slots (hc_sr_merge_next.h: Slots) and the merged
+    // pairs' rewrites; the tables before they are copied out (t_*); the scans' workspace
+    struct SrMergeNext {
+        hc_scratch pairs, pair_status, first_layout, layouts, members, lay_status, out_off, sub, v_read, v_fwd, incl, tip_reads;
+        hc_scratch entries, status, cnt, bytes, key, rank, overlap_pos, n_clique, visited, rewrite;
+        hc_scratch t_kind, t_id, t_v_state, t_nodes, t_srs, t_sr_pair, t_clique_cnt, t_clique_off, t_clique_nodes, t_sub_off, t_sub, t_tips, temp;
+    } sr_mn;
 };
 
 namespace hc {

@@ -115,6 +115,18 @@ class Fno1Input:
         self.n_inclusion_groups = len(inclusion_groups)
         self.new_read_count, self.edge_threshold, self.flags, self.n_threads = new_read_count, edge_threshold, flags, n_threads
 
+    @classmethod
+    def from_tables(cls, nodes, srs, clique_off, clique_nodes, subread_off, subreads, graph_edges, **kw):
+        """The same from super-read tables that are in CSR form already (clique_off / subread_off: n_srs + 1 offsets): what
+        hc_sr_merge_next returns (merge_next.MergeNext).  kw: the further arguments of the constructor."""
+        inp = cls(nodes, srs, [], [], graph_edges, **kw)
+        inp.clique_off, inp.clique_nodes = _arr(clique_off, np.uint64), _arr(clique_nodes, np.uint64)
+        inp.subread_off, inp.subreads = _arr(subread_off, np.uint64), _arr(subreads, FNO_SUBREAD_DTYPE)
+        if inp.clique_off.size != len(inp.srs) + 1 or inp.subread_off.size != len(inp.srs) + 1 or int(inp.clique_off[-1]) != inp.clique_nodes.size or \
+                int(inp.subread_off[-1]) != inp.subreads.size:
+            raise ValueError("the offsets do not describe the tables")
+        return inp
+
     def struct(self):
         s = hc_fno1_input()
         s.nodes, s.n_nodes = _ptr(self.nodes), len(self.nodes)
@@ -171,6 +183,13 @@ def _collect(h, out_path):
         return data, c.as_dict()
     finally:
         N.lib.hc_fno_output_free(h)
+
+
+def input_from_merge_next(res, graph_edges, **kw):
+    """The first block of an hc_fno1_input — nodes, srs, the cliques, the subread maps and new_read_count — from what EdgeScorer.sr_merge_next
+    or host.sr_merge_next returned (a merge_next.MergeNext), as it is; the edge sources and settings as Fno1Input takes them."""
+    return Fno1Input.from_tables(res.nodes, res.srs, res.clique_off, res.clique_nodes, res.subread_off, res.subreads, graph_edges,
+                                 new_read_count=res.new_read_count, **kw)
 
 
 def find_next_overlaps(inp, out_path=None):

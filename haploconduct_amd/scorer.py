@@ -128,6 +128,21 @@ class EdgeScorer:
 
         return NR.fetch(self._ctx)
 
+    def sr_merge_next(self, pairs, edge, vertex_read, vertex_fwd, inclusions=None, tip_reads=None, keep_singletons=0, ignore_inclusions=False,
+                      store_tips_separately=False, self_overlap=True, min_score=0.99, min_qual=0.99, min_overlap=15, n_threads=16):
+        """hc_sr_merge_next: the rest of SRBuilder::mergeAlongEdges (src/SRBuilder.cpp:981-1001, 1260-1380) from what sr_edge_merge returned
+        (edge: its consensus.SrEdgeLayouts) — the self-overlap test, the `visited` marks, the trivial super-reads, the tips list, the
+        numbering, the next store and the vertex / super-read tables of find-next-overlaps.  Returns a merge_next.MergeNext (empty = True:
+        nothing survived, the old store is in place)."""
+        from . import merge_next as MN
+
+        res = MN.merge_next(self._ctx, pairs, edge, vertex_read, vertex_fwd, inclusions, tip_reads, keep_singletons, ignore_inclusions,
+                            store_tips_separately, self_overlap, min_score, min_qual, min_overlap, n_threads,
+                            n_reads=self._reads.n_reads if self._reads is not None else None)
+        if not res.empty:
+            self._reads = None  # (the new reads live on the device: sr_next_reads_fetch)
+        return res
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

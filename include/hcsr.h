@@ -12,6 +12,7 @@
 #define HCSR_H_
 
 #include "hcedge.h"
+#include "hcfno.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -116,7 +117,7 @@ int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const ui
  * do that on the graph the context holds (hc_graph_resolve / hc_graph_load and the cleaning calls), for every combination of
  * single-end and paired reads.
  * Left to the caller: cliques of more than two vertices and filter_subreads (:597-651), clique enumeration, the
- * original-index maps (:750-843) and subreads.txt, the `visited` marks and the trivial-entry list of :1260-1373. */
+ * original-index maps (:750-843) and subreads.txt.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next.) */
 
 typedef struct hc_merge_pairs_stats {
     double ms_kernel; /* device call only: the target-column kernel, by events on the context's stream */
@@ -324,10 +325,11 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
  * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
  * context's read store by the result.
- * Left to the caller: the original-index maps and subreads.txt (the subread infos of an edge merge: hc_sr_edge_merge);
- * ignore_inclusions and the tip handling of mergeAlongEdges (:1298-1311: the caller omits those vertices); the FASTQ text
- * itself; the index shifts and the re-sort of a clique that merge_self_overlap merged (:911-949).  (The self-overlap test
- * between the consensus call and this one runs on the kept bytes: hc_sr_merge_self_overlaps_kept.) */
+ * Left to the caller: the original-index maps and subreads.txt (the subread infos of an edge merge: hc_sr_edge_merge); the FASTQ
+ * text itself.  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
+ * clique that merge_self_overlap merged (:911-949) itself; hc_sr_merge_next below builds the list, the marks, the tips and the
+ * shifted cliques from an edge merge's outputs.  (The self-overlap test between the consensus call and this one runs on the kept
+ * bytes: hc_sr_merge_self_overlaps_kept.) */
 
 /* Off by default: every other call then behaves and allocates as it does without this section.  While it is on, hc_set_reads
  * keeps its device copies of the raw base, quality and offset arrays (trivial super-reads are copied from them: the encoded
@@ -424,6 +426,134 @@ int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint
                           uint64_t n_extra, const hc_sr_next_settings* settings, int32_t* new_id, uint32_t* status,
                           hc_sr_next_counts* counts, uint8_t* out_bases, uint8_t* out_quals, uint64_t cap, uint64_t* n_bytes,
                           uint64_t* out_seq_off, uint32_t* out_read_first_seq);
+
+/* ---- the rest of mergeAlongEdges in one call: marks, trivials, the next store and the FNO tables --------------------------
+ *
+ * Between hc_sr_edge_merge and find-next-overlaps SRBuilder::mergeAlongEdges (src/SRBuilder.cpp:1238-1384) judges the super-reads
+ * (process_cliques, :981-1001, with merge_self_overlap, :872-955), marks the vertices of the survivors (:1260-1277), walks the
+ * unvisited vertices for the trivial super-reads (:1282-1373) and numbers the three groups (:1279-1280, :1370-1371, :1378).
+ * hc_sr_merge_next does that on the device from what hc_sr_edge_merge returned: it leaves the next store in the context, as
+ * hc_sr_set_next_reads would for the same entries in the same order, and returns the vertex and super-read tables of an
+ * hc_fno1_input (hcfno.h) ready to use.
+ * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in
+ * arrival order (:1004-1011), which is not deterministic; one thread gives pair order.
+ * Left to the caller: the original-index maps (:750-843, :1312-1369) and subreads.txt; the FASTQ text, including
+ * removed_tip_sequences.fastq (the tips list names the vertices); cliques of more than two vertices. */
+
+typedef struct hc_sr_merge_next_input {
+    /* what hc_sr_edge_merge returned, unchanged: host arrays */
+    const uint32_t* pairs;              /* (v, w) of pair i = pairs[2 i], pairs[2 i + 1]: process_cliques' clique_vec, :980              */
+    uint64_t n_pairs;
+    const uint32_t* pair_status;        /* HC_SR_EDGE_*: anything but OK owns no super-read (constructSuperread asserted or exited, :981) */
+    const uint64_t* first_layout;       /* n_pairs + 1: one layout = single-end, two = paired (:850-869)                                 */
+    const hc_sr_layout* layouts;        /* first_layout[n_pairs] of them: the first one's members give get_sorted_clique (:853, :864)     */
+    const hc_sr_member* members;
+    uint64_t n_members;                 /* entries of members: at most 6 n_pairs, what hc_sr_edge_merge has room for (HC_ERR_ARG beyond)  */
+    const uint32_t* status;             /* HC_SR_* per layout: a layout that is not HC_SR_OK is an empty mate (:983, :999)               */
+    const uint64_t* out_off;            /* n_layouts + 1: cons_seq1 / cons_seq2 (:852, :863) among the KEPT consensus bytes              */
+    const hc_sr_subread_info* subreads; /* 2 n_pairs: calcSubreadInfo's entries of the smaller and the larger vertex (:536-595)          */
+    /* the graph's vertices */
+    const uint32_t* vertex_read;        /* OverlapGraph::vertex_to_read as store indices, :1284                                          */
+    const uint8_t* vertex_fwd;          /* OverlapGraph::getOrientation, :1331                                                           */
+    uint64_t n_vertices;                /* OverlapGraph::getVertexCount, :1261, :1282                                                    */
+    const uint8_t* inclusions;          /* OverlapGraph::inclusions, one byte per vertex (hc_graph_fetch), :1298; NULL: none             */
+    const uint8_t* tip_reads;           /* Read::is_tip(), :1305: one byte for EVERY read of the current store (hc_graph_fetch_tip_reads
+                                           with n_reads = the store's reads); the call reads that many and cannot check it; NULL: none  */
+} hc_sr_merge_next_input;
+
+typedef struct hc_sr_merge_next_settings {
+    uint32_t keep_singletons;       /* program_settings.keep_singletons, :1286                                              */
+    uint32_t ignore_inclusions;     /* program_settings.ignore_inclusions, :1298                                            */
+    uint32_t store_tips_separately; /* program_settings.store_tips_separately, :1305                                        */
+    uint32_t no_self_overlap;       /* 1: merge_self_overlap (:985) is left out, every paired super-read stays paired       */
+    hc_sr_self_settings self;       /* merge_self_overlap's constants (:873-874: min_score 0.99, min_overlap 15) and minQual */
+} hc_sr_merge_next_settings; /* 40 bytes */
+
+/* What became of pair i. */
+enum {
+    HC_SR_MN_NONE = 0,            /* no super-read: pair_status is not HC_SR_EDGE_OK, or the pair's layouts / vertices are refused     */
+    HC_SR_MN_DROPPED_EMPTY = 1,   /* an empty mate, :983, :999                                                                         */
+    HC_SR_MN_DROPPED_N_RATE = 2,  /* test_N_rate false, :986, :999 (of the merged read for a pair that self-merged)                    */
+    HC_SR_MN_SINGLE = 3,          /* singles_this_thread, :1000                                                                        */
+    HC_SR_MN_SINGLE_SELF = 4,     /* a paired super-read merge_self_overlap merged, :993-995                                           */
+    HC_SR_MN_PAIRED = 5           /* pairs_this_thread, :990-992                                                                       */
+};
+/* What became of vertex v; the tests of an unvisited vertex run in this order (:1286-1311). */
+enum {
+    HC_SR_MN_V_MERGED = 0,    /* visited by a surviving super-read, :1264-1275                                                         */
+    HC_SR_MN_V_TRIVIAL = 1,   /* a trivial super-read, :1312-1371                                                                      */
+    HC_SR_MN_V_SHORT = 2,     /* get_len() < keep_singletons, :1286                                                                    */
+    HC_SR_MN_V_N_RATE = 3,    /* test_N_rate false, :1292                                                                              */
+    HC_SR_MN_V_INCLUSION = 4, /* ignore_inclusions && inclusions[v], :1298: on the tips list                                           */
+    HC_SR_MN_V_TIP = 5,       /* is_tip() && store_tips_separately, :1305: on the tips list                                            */
+    HC_SR_MN_V_BAD = 6        /* refused: vertex_read[v] is no read of the store.  Marked visited, no id.                              */
+};
+
+typedef struct hc_sr_merge_next_output {
+    /* per pair (n_pairs entries each) */
+    uint32_t* pair_kind;   /* HC_SR_MN_*                                                                                               */
+    int32_t* pair_new_id;  /* Read id of the pair's super-read in the next store (:1280, :1378) or -1                                  */
+    int32_t* overlap_pos;  /* merge_self_overlap's overlap_pos (:882) of a pair it merged, else -1                                     */
+    double* self_score;    /* overlap_score's value there (:886), else 0                                                               */
+    /* per vertex (n_vertices entries each) */
+    uint32_t* vertex_state; /* HC_SR_MN_V_*                                                                                            */
+    hc_fno_read* nodes;     /* id = nodes_to_new_IDs (:1370) of a trivial, else 0; len1 / len2 / paired of vertex_read[v] in the store
+                               the call found; visited = SRBuilder::visited after :1373; orientation = vertex_fwd[v]                   */
+    /* per surviving super-read, single_SR_vec then paired_SR_vec (:1023-1024); room for n_pairs (+ 1 for the offsets) */
+    hc_fno_read* srs;           /* id = the new id, len1 / len2 = the mates' lengths, paired                                            */
+    uint32_t* sr_pair;          /* the pair it came from                                                                                */
+    uint64_t* clique_off;       /* n_srs + 1 offsets into clique_nodes                                                                  */
+    uint64_t* clique_nodes;     /* room for 4 n_pairs: get_sorted_clique(0) of a single (:864), get_sorted_clique(1) of a paired
+                                   super-read (:853) — the vertex of every member of the pair's FIRST layout in member order (a paired
+                                   read in an 's' layout appears twice) —, new_sorted_clique of a self-merged one (:913-935)            */
+    uint64_t* subread_off;      /* n_srs + 1: 2 k                                                                                       */
+    hc_fno_subread* subreads;   /* room for 2 n_pairs: the subreadMap (:857, :866), smaller vertex first; after a self-merge index2 +=
+                                   overlap_pos where index2 >= 0 (:918-922)                                                            */
+    uint32_t* tips;             /* room for n_vertices: the vertices of tips_vec in its order (:1302, :1309)                            */
+    /* filled by the call */
+    uint64_t n_srs, n_singles, n_trivials, n_paired, n_tips, n_self_merged;
+    uint64_t new_read_count;    /* SRBuilder::new_read_count, :1380                                                                     */
+    hc_sr_next_counts counts;   /* of the store: n_kept = new_read_count; the dropped counts over pairs and vertices together          */
+    hc_sr_self_stats self_stats;
+    double ms_device;           /* device call only: this section's own kernels, by events on the context's stream                     */
+    double ms_copy;             /* device call only: waiting for the copies of the inputs and of the tables                             */
+} hc_sr_merge_next_output;
+
+/* Needs hc_sr_keep_device on, a store whose raw arrays were kept and kept consensus bytes (HC_ERR_STATE otherwise);
+ * n_pairs + n_vertices >= 2^31, first_layout[n_pairs] > 2 n_pairs or n_members > 6 n_pairs: HC_ERR_ARG.  Any error leaves the old store usable.
+ * 1. The super-read of pair i (:981-1001).  pair_status != HC_SR_EDGE_OK: none.  One layout: single-end, its bytes at out_off of that
+ *    layout; two: paired.  An empty mate drops it.  A paired super-read with two non-empty mates goes through merge_self_overlap —
+ *    hc_sr_merge_self_overlaps_kept's own run on an hc_sr_pair list built from out_off — and a merged pair becomes a single-end
+ *    super-read at the offset the kept form appended it (the kept bytes grow as there).  Then test_N_rate.
+ *    Refused as HC_SR_MN_NONE, nothing read: a vertex >= n_vertices, v == w, another number of layouts than 1 or 2, a layout or a
+ *    member range outside the arrays, a first layout with no member or more than 4, descending out_off.
+ * 2. visited[x] = 1 for both vertices of every super-read that survived 1, and only those (:1261-1277).  Two pairs naming one vertex
+ *    both mark it.
+ * 3. Every unvisited vertex in vertex order (:1282-1373), tested in the order of HC_SR_MN_V_*; a trivial has rev = !vertex_fwd[v]
+ *    (:1331-1368).
+ * 4. Ids: the single-end super-reads in pair order from 0 (a self-merged pair at its pair's place), then the trivials in vertex
+ *    order, then the paired super-reads in pair order: hc_sr_set_next_reads' own numbering for that entry list.
+ * 5. The store is replaced exactly as hc_sr_set_next_reads replaces it for that entry list (the same code from the gather on).  When
+ *    nothing survives: HC_SR_NEXT_EMPTY, the outputs filled, the old store kept.
+ * 6. After a self-merge (:911-935) the merged read's sorted clique lists, for each of the pair's two vertices, (vertex, index1) and,
+ *    where index2 >= 0, (vertex, index2 + overlap_pos), ordered by index; among equal indexes the vertex of the first layout's SECOND
+ *    member comes first, and a vertex's index1 entry before its index2 entry (the unordered_map's iteration order — the reverse of the
+ *    insertion order of :571 for two keys — kept by the insertion sort std::sort is on four elements).
+ * The member-to-vertex choice: a member is the smaller vertex's when its read is vertex_read of the smaller vertex, else the larger's.
+ * The tables can be handed to hc_fno1_input as they are.  No base or quality byte crosses the link apart from the mates of the pairs the
+ * host decides in the self-overlap scan. */
+int hc_sr_merge_next(hc_ctx* ctx, const hc_sr_merge_next_input* in, const hc_sr_merge_next_settings* st, hc_sr_merge_next_output* out);
+
+/* The same contract on the host (no device, no context): the current store as hc_set_reads takes it, the kept consensus bytes (n_cons
+ * each), in, st, out — and the four arrays of the next store as hc_host_sr_next_reads returns them (out_seq_off: room for
+ * 2 (n_pairs + n_vertices) + 1, out_read_first_seq: n_pairs + n_vertices + 1; cap / *n_bytes: count, then fetch).  It walks the
+ * reference's loops as written, over hc_host_sr_merge_self_overlaps and hc_host_sr_next_reads.  ec_settings: --mismatch and
+ * --min_read_len for the self-overlap test, as hc_host_sr_merge_self_overlaps takes them. */
+int hc_host_sr_merge_next(const hc_settings* ec_settings, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,
+                          const uint32_t* read_first_seq, uint32_t n_reads, const uint8_t* cons_seq, const uint8_t* cons_qual, uint64_t n_cons,
+                          const hc_sr_merge_next_input* in, const hc_sr_merge_next_settings* st, hc_sr_merge_next_output* out,
+                          uint8_t* out_bases, uint8_t* out_quals, uint64_t cap, uint64_t* n_bytes, uint64_t* out_seq_off,
+                          uint32_t* out_read_first_seq);
 
 #ifdef __cplusplus
 }
