@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../host/EdgeCalculator.h"
+#include "../host/EnvKnobs.h"
 
 using namespace hc;
 
@@ -404,7 +405,7 @@ extern "C" int hc_cli_main(int argc, char** argv, void (*on_done)(int code, void
         // defer_cleanup) only gives memory back — nothing that writes may ever be handed to it.
         if (on_done) {
             done(0);  // the client leaves now; what is left of the stage goes behind its back (its devices stay: keep_devices_resident)
-        } else if (!getenv("HC_CLI_TEARDOWN")) {
+        } else if (!env::given(env::Knob::CLI_TEARDOWN)) {
             fflush(stdout);
             fflush(stderr);
             _exit(0);

@@ -29,6 +29,8 @@
 #include <string>
 #include <vector>
 
+#include "../host/EnvKnobs.h"
+
 extern char** environ;
 static const uint32_t kResidentMagic = 0x48435235u;
 
@@ -60,7 +62,7 @@ static uint64_t library_stamp() {
 }
 
 static std::string socket_dir() {
-    if (const char* d = getenv("HC_RESIDENT_DIR")) return d;
+    if (const char* d = hc::env::raw(hc::env::Knob::RESIDENT_DIR)) return d;
     if (const char* d = getenv("XDG_RUNTIME_DIR")) return std::string(d) + "/hc-edgecalc";
     return "/tmp/hc-edgecalc-" + std::to_string((unsigned)getuid());
 }
@@ -257,8 +259,7 @@ int main(int argc, char** argv) {
         typedef int (*daemon_fn)(const char*, int, unsigned long long);
         daemon_fn fn = (daemon_fn)dlsym(lib, "hc_cli_daemon");
         if (!fn) return 1;
-        const char* idle = getenv("HC_RESIDENT_IDLE_S");
-        return fn(argv[2], idle ? atoi(idle) : 600, (unsigned long long)library_stamp());
+        return fn(argv[2], hc::env::i(hc::env::Knob::RESIDENT_IDLE_S, 600), (unsigned long long)library_stamp());
     }
     typedef int (*main_fn)(int, char**, void (*)(int, void*), void*);
     main_fn fn = (main_fn)dlsym(lib, "hc_cli_main");

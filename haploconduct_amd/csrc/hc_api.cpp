@@ -18,7 +18,11 @@
 
 #include "../../include/hcedge.h"
 #include "hc_ctx.h"
+#include "host/EnvKnobs.h"
 #include "host/LogP.h"
+
+namespace env = hc::env;
+using env::Knob;
 
 static thread_local std::string g_last_error;
 
@@ -256,8 +260,8 @@ int plan_store(hc_ctx* c, const uint64_t* hist, const uint64_t* base_hist, const
         // therefore dealt by FREQUENCY (round 5): the most frequent quality values take the indices whose partner i ^ 4 is the N index, the
         // invalid index or no index at all (entries that are next to never read), the others are paired hottest with coldest.  Any
         // assignment gives the same results (table and symbols are built from the same map); HC_QIDX_ORDER=value keeps byte order (A/B knob).
-        const char* qo = getenv("HC_QIDX_ORDER");
-        if (Kq >= 5 && Kq <= 6 && !(qo && strcmp(qo, "value") == 0)) {
+        const bool by_value = env::is(Knob::QIDX_ORDER, "value");
+        if (Kq >= 5 && Kq <= 6 && !by_value) {
             std::vector<uint32_t> by_freq(Kq);
             for (uint32_t k = 0; k < Kq; k++) by_freq[k] = k;
             std::stable_sort(by_freq.begin(), by_freq.end(), [&](uint32_t a, uint32_t b) { return hist[present[a]] > hist[present[b]]; });
@@ -281,12 +285,12 @@ int plan_store(hc_ctx* c, const uint64_t* hist, const uint64_t* base_hist, const
             const bool seven = hc::lut_lg(Kq) == 7;
             std::vector<uint32_t> by_freq(Kq);
             for (uint32_t k = 0; k < Kq; k++) by_freq[k] = k;
-            if (!(qo && strcmp(qo, "value") == 0))
+            if (!by_value)
                 std::stable_sort(by_freq.begin(), by_freq.end(), [&](uint32_t a, uint32_t b) { return hist[present[a]] > hist[present[b]]; });
             wide_rows.assign(64, -2);
             wide_rows[hc::kWideN] = -1;
             for (uint32_t r = 0; r < Kq; r++) {
-                const uint32_t label = (qo && strcmp(qo, "value") == 0) ? hc::wide_first(seven ? 7u : 6u) + r
+                const uint32_t label = by_value ? hc::wide_first(seven ? 7u : 6u) + r
                                                                         : (seven ? hc::kWide7RankLabel[r] : hc::kWideRankLabel[r]);
                 qmap[present[by_freq[r]]] = (uint8_t)label;
                 wide_rows[label] = present[by_freq[r]] - 33;
@@ -317,8 +321,8 @@ int plan_store(hc_ctx* c, const uint64_t* hist, const uint64_t* base_hist, const
         uint64_t aligned_bytes = 0;
         for (uint32_t q = 0; q < n_seq; q++) aligned_bytes += 2 * hc::slot_stride(seq_len[q], symbytes, 128) * symbytes;
         if (aligned_bytes > (256ull << 20)) slot_align = 16;
-        if (const char* v = getenv("HC_SLOT_ALIGN")) {  // tuning knob: 16, 32, 64, 128, 256
-            const int a = atoi(v);
+        if (env::given(Knob::SLOT_ALIGN)) {  // tuning knob: 16, 32, 64, 128, 256
+            const int a = env::i(Knob::SLOT_ALIGN, 0);
             if (a >= 16 && a <= 4096 && (a & (a - 1)) == 0) slot_align = (uint32_t)a;
         }
     }
@@ -436,7 +440,7 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
         uint32_t n_single = 0;
         for (uint32_t r = 0; r < n_reads; r++) n_single += read_first_seq[r + 1] - read_first_seq[r] == 1;
         c->view.regular = (same_len && c->singles_first && !any_bad_base) ? 1u : 0u;
-        if (const char* v = getenv("HC_REGULAR_STORE")) c->view.regular = c->view.regular && atoi(v) != 0;  // test / tuning knob: 0 forces look-ups
+        c->view.regular = c->view.regular && env::i(Knob::REGULAR_STORE, 1) != 0;  // test / tuning knob: 0 forces look-ups
         c->view.ulen = same_len ? seq_len[0] : 0u;
         c->view.n_single = n_single;
         c->view.seq_syms = same_len ? (uint32_t)(2 * hc::slot_stride(seq_len[0], symbytes, slot_align)) : 0u;
@@ -476,12 +480,12 @@ int finish_store(hc_ctx* c, const StorePlan& P, const uint8_t* d_bases, const ui
         // reads of 100..400 bp (mean 216) 0.196 / 0.234 ms, 120..900 bp (mean 387) 0.307 / 0.289, 150..1 500 bp (mean 586)
         // 0.441 / 0.348, 150..6 000 bp (mean 1 586) 1.35 / 0.63 (profiles/r03_bucket_dispatch.txt)
         c->view.balance = (n_seq && lmax > 2u * lmin && total / n_seq > 350) ? 1u : 0u;
-        if (const char* b = getenv("HC_BALANCE")) c->view.balance = atoi(b) != 0;
+        if (env::given(Knob::BALANCE)) c->view.balance = env::i(Knob::BALANCE, 0) != 0;
     }
     c->coop_fetch = true;
-    if (const char* v = getenv("HC_FETCH_GROUP")) {
-        c->coop_fetch = !strcmp(v, "coop");
-        c->fetch_group = atoi(v) == 2 ? 2 : 4;
+    if (env::given(Knob::FETCH_GROUP)) {
+        c->coop_fetch = env::is(Knob::FETCH_GROUP, "coop");
+        c->fetch_group = env::i(Knob::FETCH_GROUP, 0) == 2 ? 2 : 4;
     } else {
         // Which kernel a read set takes, by its shape (2 * 10^6 candidates each, kernel ms; profiles/r04_dispatch.txt, r04_dispatch_pairs.txt):
         //   pairs 2 x 150 (C2)                        cooperative 0.186        per lane 0.25            -> cooperative (LDS-DMA rows)
@@ -623,10 +627,8 @@ static int ensure_sort_workspace(hc_ctx* c, uint64_t n) {
 // moves the threshold (A/B and test knobs, read at every launch).
 static constexpr uint64_t kLocalityMinCandidates = 8000000;
 static bool locality_wanted(uint64_t n) {
-    const char* e = getenv("HC_LOCALITY");
-    if (e && atoi(e) == 0) return false;
-    const char* m = getenv("HC_LOCALITY_MIN");
-    return n >= (m ? strtoull(m, nullptr, 10) : kLocalityMinCandidates);
+    if (env::i(Knob::LOCALITY, 1) == 0) return false;
+    return n >= env::u64(Knob::LOCALITY_MIN, kLocalityMinCandidates);
 }
 
 int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_out, hipStream_t s, bool reorder,

@@ -20,6 +20,7 @@
 #include "hc_prims.h"
 #include "hc_sfo_device.h"
 #include "hc_text.h"
+#include "host/EnvKnobs.h"
 #include "host/NumaBind.h"
 #include "host/Types.h"
 
@@ -29,6 +30,9 @@ std::string sfo_sorted_to_overlaps(const SfoFlipped* recs, uint64_t n, long ns, 
 }  // namespace hc
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
+
+namespace env = hc::env;
+using env::Knob;
 
 namespace {
 // A view of one of the context's grow-only scratch slots (hc_ctx::finder_scratch).  The overlap finder needs
@@ -56,12 +60,6 @@ struct IngestScratch {
             if (sl.p) idle.push_back(&sl);
     }
     hipError_t operator()(size_t bytes, void** p) {
-        const hipError_t e = take(bytes, p);
-        if (getenv("HC_SCRATCH_TRACE")) fprintf(stderr, "[hc scratch] %zu bytes: %s\n", bytes, how);
-        return e;
-    }
-    const char* how = "";
-    hipError_t take(size_t bytes, void** p) {
         const size_t need = bytes ? bytes : 16;
         int best = -1;
         for (size_t i = 0; i < idle.size(); i++)
@@ -69,12 +67,10 @@ struct IngestScratch {
         if (best >= 0) {
             *p = idle[(size_t)best]->p;
             idle[(size_t)best] = nullptr;
-            how = "an idle block";
             return hipSuccess;
         }
         while (n_own < 12 && c->ingest_scratch[n_own].p) n_own++;  // an empty slot of the second set
         hc_scratch* sl = nullptr;
-        how = "a new block of the second set";
         if (n_own < 12) {
             sl = &c->ingest_scratch[n_own];
         } else {  // every slot holds a block that is too small: the smallest idle one OF THE SECOND SET grows (a finder slot given another
@@ -90,12 +86,10 @@ struct IngestScratch {
                 if (e != hipSuccess) return e;
                 *p = q.p;
                 mine.push_back(std::move(q));
-                how = "a block of this call's own (hipMalloc + hipFree)";
                 return hipSuccess;
             }
             sl = idle[(size_t)small];
             idle[(size_t)small] = nullptr;
-            how = "the smallest idle block of the second set regrown (hipFree + hipMalloc)";
         }
         const hipError_t e = sl->alloc(need);
         *p = sl->p;
@@ -131,7 +125,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
         return HC_OK;
     }
     HC_HIP(hipSetDevice(c->device));
-    const bool timing = getenv("HC_FIND_TIMING") != nullptr;
+    const bool timing = env::given(Knob::FIND_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tmark = now();
     auto lap = [&](const char* what) {
@@ -273,8 +267,7 @@ int hc_find_overlaps(hc_ctx* c, double err_rate, uint32_t min_overlap, uint32_t 
     }
     // 2^27 seed hits in flight (28 bytes of scratch each): with 2^29 the first call of a context allocated 15 GB for the batches alone,
     // which costs 0.2 - 0.9 s on some hosts (the call itself takes 0.12 s); four batches instead of one cost 6 % once the scratch exists
-    uint64_t batch_hits = 1ull << 27;
-    if (const char* e = getenv("HC_FIND_BATCH_HITS")) batch_hits = strtoull(e, nullptr, 10);
+    uint64_t batch_hits = env::u64(Knob::FIND_BATCH_HITS, 1ull << 27);
     if (batch_hits < 1024) batch_hits = 1024;
     if (batch_hits > (1ull << 31)) batch_hits = 1ull << 31;  // the sorts (hc_prims.hip) index with 32 bits
     struct Batch {
@@ -410,7 +403,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
     if (!c) return fail(HC_ERR_ARG, "hc_found_to_overlaps: null argument");
     if (!c->found_valid) return fail(HC_ERR_STATE, "hc_found_to_overlaps: hc_find_overlaps has not been called on this read set");
     const uint64_t n = c->n_found;
-    const bool timing = getenv("HC_SFO_TIMING") != nullptr;
+    const bool timing = env::given(Knob::SFO_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     struct Freed {
         void* host = nullptr;
@@ -463,7 +456,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
             // and the places.  HC_SFO_FILTER=0: all of them, as before.
             uint64_t n_out = n;
             const hc::SfoFlipped* d_send = d_sorted;
-            const bool filter = !(getenv("HC_SFO_FILTER") && atoi(getenv("HC_SFO_FILTER")) == 0);
+            const bool filter = env::i(Knob::SFO_FILTER, 1) != 0;
             if (filter) {
                 uint8_t *d_grouped = (uint8_t*)d_k[0], *d_keep = (uint8_t*)d_k[1];
                 uint32_t* d_idx = (uint32_t*)d_k[2];
@@ -489,7 +482,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
             // the page-locked ring the sorted records come back through (kept with the context)
             const uint64_t ring = 2u << 20;  // records per buffer of the ring: 64 MiB
             uint64_t chunk = ring;            // records per copy (HC_SFO_CHUNK: test knob, small chunks on small inputs)
-            if (const char* e = getenv("HC_SFO_CHUNK")) chunk = std::min<uint64_t>(ring, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+            if (env::given(Knob::SFO_CHUNK)) chunk = std::min<uint64_t>(ring, std::max<uint64_t>(1, env::u64(Knob::SFO_CHUNK, 0)));
             for (hc_scratch& h : c->h_ingest)
                 if (const int rc = h.ensure_exact(ring * sizeof(hc::SfoFlipped))) return rc;
             HC_HIP(hipStreamSynchronize(st));
@@ -545,7 +538,7 @@ int hc_found_to_lines_device(hc_ctx* c, uint64_t num_singles, uint64_t num_pairs
     const uint64_t n = c->n_found;
     if (n == 0) return HC_OK;
     if (n >= 0x7FFFFFF0ull) return fail(HC_ERR_NOT_ON_DEVICE, "hc_found_to_lines_device: not on the device (2^31 records and more)");
-    const bool timing = getenv("HC_SFO_TIMING") != nullptr;
+    const bool timing = env::given(Knob::SFO_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     IngestScratch dmalloc(c);
     HC_HIP(hipSetDevice(c->device));
@@ -799,7 +792,7 @@ int hc_set_found_from_sfo_text(hc_ctx* c, const char* text, uint64_t n_bytes, ui
     {
         unsigned T = std::thread::hardware_concurrency();
         T = T == 0 ? 1 : (T > 16 ? 16 : T);
-        if (const char* e = getenv("HC_SFO_COPY_THREADS")) T = (unsigned)std::max(1, std::min(64, atoi(e)));
+        if (env::given(Knob::SFO_COPY_THREADS)) T = (unsigned)std::max(1, std::min(64, env::i(Knob::SFO_COPY_THREADS, 0)));
         if (n_bytes < (8u << 20)) T = 1;
         copiers.start(T);
     }

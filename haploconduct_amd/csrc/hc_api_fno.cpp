@@ -18,6 +18,7 @@
 #include "hc_overlap_finder.h"
 #include "hc_prims.h"
 #include "hc_scratch.h"
+#include "host/EnvKnobs.h"
 #include "host/Types.h"
 
 namespace hc {
@@ -50,9 +51,8 @@ void hip_check(hipError_t e, const char* what) {
 }  // namespace
 
 bool fno_device_wanted(uint64_t n_items) {
-    const char* e = getenv("HC_FNO");
-    if (e && strcmp(e, "host") == 0) return false;
-    const bool forced = e && strcmp(e, "device") == 0;
+    if (env::is(env::Knob::FNO, "host")) return false;
+    const bool forced = env::is(env::Knob::FNO, "device");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
         (void)hipGetLastError();
@@ -138,7 +138,7 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
     auto now = [] { return std::chrono::steady_clock::now(); };
     const auto t0 = now();
     hipStream_t st = nullptr;
-    const bool debug = getenv("HC_FNO_DEBUG") != nullptr;
+    const bool debug = env::given(env::Knob::FNO_DEBUG);
     auto left = [&](const char* where, unsigned long long status) {  // why the host form takes over (HC_FNO_DEBUG)
         if (debug) fprintf(stderr, "[hc fno] the device route ends at %s, status %llu\n", where, status);
         return false;

@@ -8,15 +8,13 @@
 #include "../../include/hcedge.h"
 #include "hc_scratch.h"
 #include "hc_prims.h"
+#include "host/EnvKnobs.h"
 
 static int fail(int status, const std::string& what) { return hc::set_last_error(status, what); }
 
 namespace {
 size_t or_16(size_t bytes) { return bytes ? bytes : 16; }  // (no bytes: a block all the same)
-int pick_device() {
-    const char* e = getenv("HC_DEVICE");
-    return e ? atoi(e) : 0;
-}
+int pick_device() { return hc::env::i(hc::env::Knob::DEVICE, 0); }
 }  // namespace
 
 extern "C" {

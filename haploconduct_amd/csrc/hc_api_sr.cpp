@@ -26,6 +26,7 @@
 #include "hc_sr_merge_next.h"
 #include "hc_sr_next.h"
 #include "hc_sr_self.h"
+#include "host/EnvKnobs.h"
 #include "host/InBlocks.h"
 #include "host/SrConsensus.h"
 #include "host/SrSelfOverlap.h"
@@ -312,8 +313,8 @@ int self_scan(hc_ctx* c, const std::string& me, const SelfBatch& B, const uint8_
     if ((rc = sr_tables(c, S.tables, q_of, settings->min_qual))) return rc;
     hc::SrSelfParams prm;
     int log2_width = -49;
-    if (const char* e = getenv("HC_SR_SELF_BAND_LOG2")) {  // test knob: a wider guard band, so that the host-decided path runs
-        const int v = atoi(e);
+    {  // test knob: a wider guard band, so that the host-decided path runs
+        const int v = hc::env::i(hc::env::Knob::SR_SELF_BAND_LOG2, log2_width);
         if (v >= -60 && v <= -2) log2_width = v;
     }
     prm.band = hc::threshold_band(settings->min_score, log2_width);

@@ -24,7 +24,7 @@ struct hc_textblock {
     hipEvent_t done = nullptr;
     hipEvent_t lines_known = nullptr;          // chained submits: this block's entry of the line chain is written
     hipEvent_t copied = nullptr;               // the text has arrived (the copies of all blocks share the context's copy stream)
-    hc_scratch h_text;                         // page-locked, allocated on first use (hc_textblock_buffer): the caller reads the file into it
+    hc_scratch h_text{hipHostMallocDefault};   // page-locked, allocated on first use (hc_textblock_buffer): the caller reads the file into it
     hc_scratch d_slab;                         // ONE device allocation holding d_text ... d_kept_tiles
     hc_scratch d_rowslab, h_rowslab{hipHostMallocMapped};  // the row buffers (they may grow): d_rows + d_row_lines; h_rows + h_row_lines + h_rejects, page-locked and mapped
     char* d_text = nullptr;                    // max_bytes + 64
@@ -175,11 +175,6 @@ char* hc_textblock_buffer(hc_textblock* b) {
     if (!b) return nullptr;
     if (!b->h_text.p) {  // only callers that fill the block themselves pay for the page-locked buffer
         (void)hipSetDevice(b->ctx->device);
-        // HC_TEXT_BUFFER=wc: write-combined — pread fills it 1.4x as fast, but the CPU must then never read it (the stage
-        // with HC_TEXT_SOURCE=pread-chain does not: line numbers come from the device side)
-        const char* kind = getenv("HC_TEXT_BUFFER");
-        const unsigned flags = (kind && !strcmp(kind, "wc")) ? hipHostMallocWriteCombined : hipHostMallocDefault;
-        b->h_text = hc_scratch(flags);
         (void)b->h_text.alloc(b->max_bytes + 64);
     }
     return b->h_text.as<char>();

@@ -4,6 +4,7 @@
 // resolution of all admitted candidates at once (hc_graph_resolve).  nonedge_overlaps.txt bookkeeping and the per-edge
 // insert into a graph that already holds edges stay on the host.
 #include "EdgeCalculator.h"
+#include "EnvKnobs.h"
 #include "NumaBind.h"
 
 #include <sched.h>
@@ -33,6 +34,8 @@ std::string sfo_to_overlaps(const char* sfo_text, size_t sfo_bytes, long ns, lon
 
 namespace hc {
 
+using env::Knob;
+
 static double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -58,7 +61,7 @@ static ParsedBatch::RecStorage pinned_recs(hc_ctx* ctx) {
 // one device), else the bits of --device_mask, else --device alone.
 static std::vector<int> device_list(const ProgramSettings& ps) {
     std::vector<int> d;
-    if (const char* e = getenv("HC_DEVICE_LIST")) {
+    if (const char* e = env::raw(Knob::DEVICE_LIST)) {
         for (const char* p = e; *p;) {
             char* end = nullptr;
             const long v = strtol(p, &end, 10);
@@ -79,24 +82,23 @@ void EdgeCalculator::bind_here() const { bind_thread_to(m_node_cpus); }
 EdgeCalculator::EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_ptr<OverlapGraph> graph,
                                const ProgramSettings& ps)
     : program_settings(ps), fastq_storage(std::move(fastq)), overlap_graph(std::move(graph)) {
-    if (const char* m = getenv("HC_INSERT_MODE")) m_serial_insert = std::string(m) == "serial";
-    if (const char* m = getenv("HC_RESOLVE")) m_host_resolve = std::string(m) == "host";
-    if (const char* m = getenv("HC_PARSE")) m_host_parse = std::string(m) == "host";
-    if (const char* m = getenv("HC_PARSE_FALLBACK")) {  // "block": a line the device does not read sends its whole block to the host (round 4's route)
-        if (std::string(m) == "block") m_odd_line_cap = 0;
-        else if (atoi(m) > 0) m_odd_line_cap = (uint32_t)atoi(m);  // test knob: entries of a block's list
-    }
-    if (const char* m = getenv("HC_TEXT_BLOCK")) m_text_block = std::max<size_t>(4096, (size_t)strtoull(m, nullptr, 10));
+    m_serial_insert = env::is(Knob::INSERT_MODE, "serial");
+    m_host_resolve = env::is(Knob::RESOLVE, "host");
+    m_host_parse = env::is(Knob::PARSE, "host");
+    // "block": a line the device does not read sends its whole block to the host (round 4's route)
+    if (env::is(Knob::PARSE_FALLBACK, "block")) m_odd_line_cap = 0;
+    else if (env::i(Knob::PARSE_FALLBACK, 0) > 0) m_odd_line_cap = (uint32_t)env::i(Knob::PARSE_FALLBACK, 0);  // test knob: entries of a block's list
+    if (env::given(Knob::TEXT_BLOCK)) m_text_block = std::max<size_t>(4096, (size_t)env::u64(Knob::TEXT_BLOCK, 0));
     m_cs = to_hc_settings(ps);
-    if (const char* m = getenv("HC_TEXT_DEPTH")) {
-        m_text_depth = std::max<size_t>(1, (size_t)atoi(m));
+    if (env::given(Knob::TEXT_DEPTH)) {
+        m_text_depth = std::max<size_t>(1, (size_t)env::i(Knob::TEXT_DEPTH, 0));
     } else {  // as deep as the overlaps file has blocks for one device, between 2 and 10: a small file does not pay for buffers it never fills
         struct stat sb;
         const size_t n_dev = std::max<size_t>(1, device_list(ps).size());
         if (stat(ps.overlaps_file.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) {
             // a file shorter than one block: the blocks are made for ITS size (page-locking and device buffers for 16 MiB took 38 ms of
             // the SAVAGE example's process, whose file has 3 MB); a longer text on a later call is cut into more blocks of this size
-            if (!getenv("HC_TEXT_BLOCK") && (size_t)sb.st_size < m_text_block)
+            if (!env::given(Knob::TEXT_BLOCK) && (size_t)sb.st_size < m_text_block)
                 m_text_block = std::max<size_t>((size_t)64 << 10, (((size_t)sb.st_size + 4096) + 65535) & ~(size_t)65535);
             const size_t blocks = ((size_t)sb.st_size + m_text_block - 1) / m_text_block;
             m_text_depth = std::min<size_t>(m_text_depth, std::max<size_t>(2, (blocks + n_dev - 1) / n_dev));
@@ -172,7 +174,7 @@ EdgeCalculator::EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_
             tc3 = now_s();
             blocks.join();
             if (blocks_error.status) throw blocks_error;
-            if (getenv("HC_STAGE_TIMING"))
+            if (env::given(Knob::STAGE_TIMING))
                 fprintf(stderr, "[hc stage] device %d: context %.3f s, read store %.3f s, id table %.3f s, %zu text blocks %.3f s beside them (+ %.3f s)\n", d, tc1 - tc0,
                         tc2 - tc1, tc3 - tc2, dv.tblk.size(), blocks_s, now_s() - tc3);
         }
@@ -556,7 +558,7 @@ void EdgeCalculator::finish_appender(bool rethrow) {
 // The serial half for the whole file on the device: hc_graph_resolve + hc_graph_fetch, then the
 // lists of the graph simply point into the arrays that came back.
 void EdgeCalculator::resolve_on_device(bool sorted) {
-    const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
+    const bool timing = env::given(Knob::STAGE_TIMING);
     double tp = now_s();
     auto lap = [&](const char* what) {
         if (timing) {
@@ -650,7 +652,7 @@ void EdgeCalculator::resolve_on_device(bool sorted) {
     std::vector<Read*>& reads = fastq_storage->m_read_vec;
     // HC_FETCH_PIECE_BYTES: bytes of edges per piece (default 32 MiB; 0: the whole graph in one fetch, then adopt — round 3's order; tests
     // set a few KiB to run small graphs through the pieces)
-    const size_t piece_bytes = getenv("HC_FETCH_PIECE_BYTES") ? (size_t)strtoull(getenv("HC_FETCH_PIECE_BYTES"), nullptr, 10) : ((size_t)32 << 20);
+    const size_t piece_bytes = (size_t)env::u64(Knob::FETCH_PIECE_BYTES, (uint64_t)32 << 20);
     if (piece_bytes == 0 || E * sizeof(hc_edge_rec) <= piece_bytes) {
         check(hc_graph_fetch(m_ctx, edges, out_off.data(), in_nodes, in_off.data(), seq, incl.data(), tied.empty() ? nullptr : tied.data()),
               "hc_graph_fetch");
@@ -864,7 +866,7 @@ void EdgeCalculator::score_device_parsed(OverlapsParser& parser, std::vector<Ove
     // the calling thread copies text too: next to the device for the length of the call, then back where it was allowed before
     BoundForNow bound(m_node_cpus);
     for (Device& d : m_dev) make_text_blocks(d);
-    if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] text blocks ready after %.3f s\n", now_s() - t_setup0);
+    if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] text blocks ready after %.3f s\n", now_s() - t_setup0);
     struct Slot {
         hc_textblock* tb = nullptr;  // nullptr: the host's block (nothing was submitted)
         size_t begin = 0, end = 0;
@@ -885,11 +887,8 @@ void EdgeCalculator::score_device_parsed(OverlapsParser& parser, std::vector<Ove
     //   map: no copy at all — the runtime moves the pageable mapping (hc_textblock_submit_from on the mapping): 0.25 s,
     //       the runtime's pageable copy reaches 25 GB/s beside the collectors' HIP calls (40-50 alone:
     //       tools/experiments/register_cost.cpp).
-    // HC_TEXT_BUFFER=wc makes the blocks' buffers write-combined (pread fills those 1.4x as fast in isolation,
-    // tools/experiments/pread_targets.cpp; no gain in the stage, where the producer then waits for the device).
-    const char* text_source = getenv("HC_TEXT_SOURCE");
-    const bool from_map = text_source && !strcmp(text_source, "map");
-    const bool pread_chain = !text_source || !strcmp(text_source, "pread-chain");
+    const bool from_map = env::is(Knob::TEXT_SOURCE, "map");
+    const bool pread_chain = !env::given(Knob::TEXT_SOURCE) || env::is(Knob::TEXT_SOURCE, "pread-chain");
     const bool chained = from_map || pread_chain;
     struct ChainGuard {
         hc_linechain* p = nullptr;
@@ -901,7 +900,7 @@ void EdgeCalculator::score_device_parsed(OverlapsParser& parser, std::vector<Ove
     // order and finalising them (exp() of the admitted ones, the lines of the non-edges) happens side by side for
     // different blocks, the serial half (and everything that touches shared state) strictly in block order.
     unsigned C = std::max(1u, std::min<unsigned>(4u, program_settings.n_threads));
-    if (const char* e = getenv("HC_COLLECTORS")) C = std::max(1, atoi(e));
+    if (env::given(Knob::COLLECTORS)) C = std::max(1, env::i(Knob::COLLECTORS, 0));
     C = (unsigned)std::min<size_t>(C, D * N);  // at most D * N blocks are in flight
     auto collect = [&](unsigned c) {
         ParsedBatch host_batch(pinned_recs(m_ctx));
@@ -1093,7 +1092,7 @@ void EdgeCalculator::score_device_parsed(OverlapsParser& parser, std::vector<Ove
     stats.t_score = t_collect;
     for (Device& dev : m_dev)
         for (hc_textblock* tb : dev.tblk) stats.regrown_blocks += hc_textblock_regrown(tb);
-    if (getenv("HC_STAGE_TIMING"))
+    if (env::given(Knob::STAGE_TIMING))
         fprintf(stderr, "[hc stage] device-parsed pipeline: %lu block(s) went to the host parser; producer: waiting for a block object %.3f s, "
                         "copy %.3f s, submit %.3f s; %u collector(s), summed: waiting for the device + ordering rows %.3f s, finalise %.3f s, "
                         "waiting for their turn %.3f s, serial half %.3f s\n",
@@ -1176,7 +1175,7 @@ void EdgeCalculator::score_device_lines(OverlapsParser& parser, std::vector<Over
     gate.rethrow();
     stats.t_score = now_s() - t0;
     for (hc_textblock* tb : dev.tblk) stats.regrown_blocks += hc_textblock_regrown(tb);
-    if (getenv("HC_STAGE_TIMING"))
+    if (env::given(Knob::STAGE_TIMING))
         fprintf(stderr, "[hc stage] device-lines pipeline: %lu piece(s) of up to %lu lines; helper: waiting for the device %.3f s, finalise %.3f s; serial half %.3f s; "
                         "all %.3f s\n", (unsigned long)K, (unsigned long)L, tm_wait, tm_final, tm_consume, now_s() - t0);
 }
@@ -1185,7 +1184,7 @@ void EdgeCalculator::score_device_lines(OverlapsParser& parser, std::vector<Over
 // through).
 void EdgeCalculator::score_host_parsed(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc) {
     size_t overlaps_per_vec = 250000;  // the reference batches 1,000,000 (:571); batch boundaries do not influence the result
-    if (const char* e = getenv("HC_STAGE_BLOCK")) overlaps_per_vec = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));  // experiment knob
+    if (env::given(Knob::STAGE_BLOCK)) overlaps_per_vec = std::max<size_t>(1, (size_t)env::u64(Knob::STAGE_BLOCK, 0));  // test knob
     // The pipeline.  The caller's thread tokenises block k (on the parser's worker threads) and submits it to device
     // k mod N; the collector thread waits for the blocks in file order, finalises what the device kept of them and
     // runs the serial half.  Every stage consumes the blocks strictly in file order, so the graph, the counters and
@@ -1262,7 +1261,7 @@ void EdgeCalculator::score_host_parsed(OverlapsParser& parser, std::vector<Overl
 void EdgeCalculator::run_stage(bool then_sort) {
     const double t_stage0 = now_s();
     auto stage_lap = [&](const char* what) {
-        if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] %s at %.3f s\n", what, now_s() - t_stage0);
+        if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] %s at %.3f s\n", what, now_s() - t_stage0);
     };
     collect_read_info();  // vertex ids may have been assigned since the last call
     stage_lap("read info collected");
@@ -1318,7 +1317,7 @@ void EdgeCalculator::run_stage(bool then_sort) {
             m_admitted.clear();
             defer_cleanup([old] { delete old; });
         }
-        if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] resolve total %.3f s\n", now_s() - tr);
+        if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] resolve total %.3f s\n", now_s() - tr);
         stage_lap("graph resolved");
         m_collect = false;
         stats.t_insert += now_s() - tr;
@@ -1394,7 +1393,7 @@ void EdgeCalculator::construct_edges_from_reads(double err_rate, uint32_t min_ov
     } reset{m_text_override};
     m_text_override = text;
     run_stage(then_sort);
-    if (getenv("HC_STAGE_TIMING"))
+    if (env::given(Knob::STAGE_TIMING))
         fprintf(stderr, "[hc stage] reads -> graph: find %.3f s (%lu SFO records), ingest %.3f s (%lu lines, %zu bytes of text in memory), construct %.3f s\n",
                 t1 - t0, (unsigned long)found, t2 - t1, (unsigned long)lines, text->size(), now_s() - t2);
 }
@@ -1428,7 +1427,7 @@ void EdgeCalculator::construct_edges_from_store(double err_rate, uint32_t min_ov
     if (device_route) *device_route = 1;
     if (n_found) *n_found = found;
     if (n_lines) *n_lines = lines;
-    if (getenv("HC_STAGE_TIMING"))
+    if (env::given(Knob::STAGE_TIMING))
         fprintf(stderr, "[hc stage] reads -> graph on the device: find %.3f s (%lu SFO records), ingest + construct %.3f s (%lu lines, none of them text)\n",
                 t1 - t0, (unsigned long)found, now_s() - t1, (unsigned long)lines);
 }
@@ -1440,7 +1439,7 @@ bool EdgeCalculator::run_stage_from_found(bool then_sort, uint64_t* n_lines) {
     const int rc = hc_found_to_lines_device(m_ctx, fastq_storage->m_readcount_single, fastq_storage->m_readcount_paired, &d_lines, &lines);
     if (rc == HC_ERR_NOT_ON_DEVICE) return false;
     check(rc, "hc_found_to_lines_device");
-    if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] SFO ingest on the device: %.3f s (%lu lines)\n", now_s() - t0, (unsigned long)lines);
+    if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] SFO ingest on the device: %.3f s (%lu lines)\n", now_s() - t0, (unsigned long)lines);
     if (n_lines) *n_lines = lines;
     struct Reset {
         EdgeCalculator* self;
@@ -1497,8 +1496,7 @@ void EdgeCalculator::construct_edges_from_sfo(const std::string& sfo_path, bool 
         const double tp0 = now_s();
         uint64_t n_rec = 0;
         int rc = HC_ERR_NOT_ON_DEVICE;
-        const char* route = getenv("HC_SFO_PARSE");
-        if (route && !strcmp(route, "host")) {
+        if (env::is(Knob::SFO_PARSE, "host")) {
             std::vector<hc_sfo_rec, DefaultInitAllocator<hc_sfo_rec>> recs;
             if (sfo_text_to_records(text, bytes, recs)) {
                 n_rec = recs.size();
@@ -1506,13 +1504,13 @@ void EdgeCalculator::construct_edges_from_sfo(const std::string& sfo_path, bool 
                 auto spent = std::make_shared<std::vector<hc_sfo_rec, DefaultInitAllocator<hc_sfo_rec>>>(std::move(recs));  // 2 GB at config 3's size:
                 defer_cleanup([spent]() mutable { spent.reset(); });                                                     // given back behind the caller's back
             }
-        } else if (!getenv("HC_SFO_TEXT_GENERAL")) {
+        } else if (!env::given(Knob::SFO_TEXT_GENERAL)) {
             rc = hc_set_found_from_sfo_text(m_ctx, text, bytes, &n_rec);
         }
         if (rc != HC_ERR_NOT_ON_DEVICE) {
             check(rc, "hc_set_found_from_sfo_text");
             if (n_records) *n_records = n_rec;
-            if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] SFO file: %zu bytes -> %lu records on the device in %.3f s\n", bytes, (unsigned long)n_rec, now_s() - tp0);
+            if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] SFO file: %zu bytes -> %lu records on the device in %.3f s\n", bytes, (unsigned long)n_rec, now_s() - tp0);
             if (run_stage_from_found(then_sort, &lines)) {
                 if (device_route) *device_route = 1;
                 if (n_lines) *n_lines = lines;

@@ -30,6 +30,7 @@
 #include "../../../include/hcfno.h"
 #include "../hc_fno_items.h"
 #include "DefaultInit.h"
+#include "EnvKnobs.h"
 #include "Types.h"
 
 namespace hc {
@@ -45,6 +46,7 @@ struct hc_fno_output {
 
 namespace {
 using hc::FatalError;
+namespace env = hc::env;
 
 [[noreturn]] void ref_abort(const char* what) { throw FatalError{HC_ERR_FORMAT, std::string("the reference stops here: ") + what}; }
 #define FNO_REQUIRE(c) \
@@ -251,7 +253,7 @@ public:
 
     void run(hc_fno_output& out) {
         threads_ = thread_count(in_.n_threads);
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::FNO_TIMING);
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto t0 = now();
         check_input();
@@ -490,14 +492,7 @@ private:
     // inclusion-induced edges (:612-630, :635-813, :816-887)
     void collect_work() {
         if (in_.n_graph_edges + in_.n_branching_edges + in_.n_nonedges >= 0xFFFFFFF0ull) throw FatalError{HC_ERR_ARG, "too many edges"};
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
-        auto tl = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!timing) return;
-            const auto t = std::chrono::steady_clock::now();
-            fprintf(stderr, "hc_fno1_run: edges in walk order: %s %.3f s\n", what, std::chrono::duration<double>(t - tl).count());
-            tl = t;
-        };
+        env::Lap lap(env::Knob::FNO_TIMING, "hc_fno1_run: edges in walk order: ");
         work_[0] = {in_.graph_edges, in_.n_graph_edges};
         work_[1] = {in_.branching_edges, in_.n_branching_edges};
         const bool use_nonedges = !(in_.flags & HC_FNO_OPTIMIZE) && in_.n_nonedges;  // :914
@@ -562,7 +557,7 @@ private:
     // pair of new ids, the first combination it meets (overlaps_found); here every combination is stamped with its
     // place in that order and each hash partition keeps the earliest one per pair.
     void walk() {
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::FNO_TIMING);
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto lap = [&](const char* what, std::chrono::steady_clock::time_point& since) {
             if (!timing) return;
@@ -800,7 +795,7 @@ private:
     bool deduce_on_device(hc_fno_output& out) {
         const uint64_t n = items_.size();
         if (n == 0 || n >= 0x7FFFFFF0ull) return false;
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::FNO_TIMING);
         auto now = [] { return std::chrono::steady_clock::now(); };
         const auto t0 = now();
         // 64 bytes per combination, written once by the threads below: 2 MiB pages where the system grants them (the
@@ -843,13 +838,12 @@ private:
     // FNO=1 whole on the device (hc_fno_items.h: fno1_walk_on_device): the edges in walk order go over as they lie in the caller's
     // arrays (the kept non-edges gathered first), with nodes_to_SR and the sorted subread maps; false = the host form runs.
     bool walk_on_device(hc_fno_output& out) {
-        if (const char* e = getenv("HC_FNO_WALK"))
-            if (strcmp(e, "host") == 0) return false;
+        if (env::is(env::Knob::FNO_WALK, "host")) return false;
         const bool use_nonedges = !(in_.flags & HC_FNO_OPTIMIZE) && in_.n_nonedges;  // :914
         const uint64_t E = in_.n_graph_edges + in_.n_branching_edges + (use_nonedges ? in_.n_nonedges : 0);
         if (!hc::fno_device_wanted(E)) return false;
         if (use_nonedges && !in_.nonedges) throw FatalError{HC_ERR_ARG, "null array"};
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::FNO_TIMING);
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t i = 0; i < in_.n_srs; ++i) FNO_REQUIRE(in_.clique_off[i + 1] > in_.clique_off[i]);  // get_sorted_clique asserts size() > 0
         if (in_.n_inclusion_groups) {  // few edges, on the host: they need checkEdge, i.e. adj_out here as well
@@ -1049,14 +1043,7 @@ private:
     void walk() {
         // :26-76.  The walk order of :100 is the iteration order of this very container type in the reference;
         // it is kept as is so that the order (a property of the host's libstdc++) is the reference's.
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
-        auto tl = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!timing) return;
-            const auto t = std::chrono::steady_clock::now();
-            fprintf(stderr, "hc_fno3_run: walk: %s %.3f s\n", what, std::chrono::duration<double>(t - tl).count());
-            tl = t;
-        };
+        env::Lap lap(env::Knob::FNO_TIMING, "hc_fno3_run: walk: ");
         std::unordered_map<unsigned long, unsigned long> original_to_index;
         std::vector<uint64_t> count;  // super-reads per original, by index
         std::vector<uint64_t> slot_of(n_ ? in_.orig_off[n_] : 0);
@@ -1175,7 +1162,7 @@ private:
     bool emit_on_device(hc_fno_output& out) {
         const uint64_t n = cands_.size();
         if (n == 0 || n >= 0x7FFFFFF0ull) return false;
-        const bool timing = getenv("HC_FNO_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::FNO_TIMING);
         auto now = [] { return std::chrono::steady_clock::now(); };
         const auto t0 = now();
         std::unique_ptr<hc::FnoItem[]> items(new hc::FnoItem[n]);

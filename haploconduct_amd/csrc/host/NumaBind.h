@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../../include/hcedge.h"
+#include "EnvKnobs.h"
 
 namespace hc {
 
@@ -18,8 +19,7 @@ namespace hc {
 // Empty when the machine has one node, the node is unknown, or HC_NUMA=0.
 inline std::vector<int> cpus_near_device(int device) {
     std::vector<int> cpus;
-    if (const char* e = getenv("HC_NUMA"))
-        if (atoi(e) == 0) return cpus;
+    if (env::i(env::Knob::NUMA, 1) == 0) return cpus;
     char bus[64] = {0};
     if (hc_device_bus_id(device, bus, (uint32_t)sizeof bus) != HC_OK) return cpus;
     for (char* c = bus; *c; c++) *c = (char)tolower((unsigned char)*c);

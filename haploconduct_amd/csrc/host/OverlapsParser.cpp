@@ -1,6 +1,7 @@
 // OverlapsParser.cpp — tokenizer / validator / prefilter of construct_edges over an mmap'ed
 // overlaps file (reference src/EdgeCalculator.cpp:569-635).
 #include "OverlapsParser.h"
+#include "EnvKnobs.h"
 
 #include "WorkerPool.h"
 
@@ -221,7 +222,7 @@ OverlapsParser::OverlapsParser(std::shared_ptr<const std::string> text, const Pr
 }
 
 OverlapsParser::~OverlapsParser() {
-    const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
+    const bool timing = env::given(env::Knob::STAGE_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     m_pool = nullptr;

@@ -25,6 +25,7 @@
 #include "../../../include/hcedge_host.h"
 #include "../hc_sfo_items.h"
 #include "DefaultInit.h"
+#include "EnvKnobs.h"
 #include "Types.h"
 
 namespace hc {
@@ -423,13 +424,13 @@ bool parse_canonical_sfo(const char* text, size_t N, RecVec& recs) {
 // The records of a CANONICAL SFO text (what rust-overlaps / hc_host_write_sfo write), or false: the general path owns such a file.
 // (the records are written in full by the parsing threads: not zero-filled first — 2 GB at config 3's size, a third of a second on one thread)
 bool sfo_text_to_records(const char* sfo_text, size_t sfo_bytes, std::vector<hc_sfo_rec, DefaultInitAllocator<hc_sfo_rec>>& recs) {
-    if (getenv("HC_SFO_TEXT_GENERAL")) return false;  // (test knob: always the general path)
+    if (env::given(env::Knob::SFO_TEXT_GENERAL)) return false;  // (test knob: always the general path)
     return parse_canonical_sfo(sfo_text, sfo_bytes, recs);
 }
 
 // Returns the output text; n_lines receives the number of lines.
 std::string sfo_to_overlaps(const char* sfo_text, size_t sfo_bytes, long ns, long np, uint64_t& n_lines) {
-    if (!getenv("HC_SFO_TEXT_GENERAL")) {  // (test knob: always take the general path)
+    if (!env::given(env::Knob::SFO_TEXT_GENERAL)) {  // (test knob: always take the general path)
         std::vector<hc_sfo_rec> recs;
         if (parse_canonical_sfo(sfo_text, sfo_bytes, recs)) return sfo_records_to_overlaps(recs.data(), recs.size(), ns, np, n_lines);
     }
@@ -684,7 +685,7 @@ std::string sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, long ns,
     if (T > 64) T = 64;
     // buckets: several per thread (short sorts that stay in the caches, an even finish), none below 20 000 records
     uint64_t NB = std::min<uint64_t>((uint64_t)T * 8, n / 20000 + 1);
-    if (const char* e = getenv("HC_SFO_BUCKETS")) NB = (uint64_t)std::max(1, atoi(e));  // test knob: many buckets on small inputs
+    if (env::given(env::Knob::SFO_BUCKETS)) NB = (uint64_t)std::max(1, env::i(env::Knob::SFO_BUCKETS, 0));  // test knob: many buckets on small inputs
     if (NB > 4096) NB = 4096;
     if (NB < T) T = (unsigned)NB;
     auto workers = [&](unsigned count, const std::function<void(unsigned)>& body) {
@@ -768,8 +769,7 @@ std::string sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, long ns,
     // 3. sort and match every bucket on its own
     // (HC_SFO_VIA_MATCHER=<records per chunk>, test knob: only sort here, then hand the sorted run to the chunk-fed matcher
     // of hc_found_to_overlaps, which otherwise needs a device to be reached)
-    const char* via_env = getenv("HC_SFO_VIA_MATCHER");
-    const bool via_matcher = via_env != nullptr;
+    const bool via_matcher = env::given(env::Knob::SFO_VIA_MATCHER);
     std::vector<BucketResult> res(B);
     std::atomic<uint64_t> sort_ns{0}, match_ns{0};  // summed over the threads (HC_SFO_TIMING)
     {
@@ -802,7 +802,7 @@ std::string sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, long ns,
     if (via_matcher) {
         for (const BucketResult& r : res)
             if (r.error.status) throw r.error;
-        const uint64_t chunk = std::max<uint64_t>(1, strtoull(via_env, nullptr, 10));
+        const uint64_t chunk = std::max<uint64_t>(1, env::u64(env::Knob::SFO_VIA_MATCHER, 0));
         SfoSortedMatcher m(ns, np);
         std::vector<SfoFlipped> buf;
         for (uint64_t at = 0; at < n; at += chunk) {
@@ -819,7 +819,7 @@ std::string sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, long ns,
     // 4. stitch: the open group travels to the next bucket that holds a non-single record and is matched there
     const auto t2 = std::chrono::steady_clock::now();
     std::string out = stitch(res, n_lines);
-    if (getenv("HC_SFO_TIMING"))
+    if (env::given(env::Knob::SFO_TIMING))
         fprintf(stderr, "sfo_records_to_overlaps: flip + partition %.3f s, sort + match %.3f s (thread-seconds: sort %.3f, match %.3f), stitch %.3f s (%u buckets, %u threads)\n",
                 std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t2 - t1).count(), sort_ns.load() * 1e-9, match_ns.load() * 1e-9,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count(), B, T);
@@ -858,7 +858,7 @@ struct SfoSortedMatcher::Impl {
         const uint64_t nc = carry.size();
         auto at = [&](uint64_t i) -> const SfoFlipped& { return i < nc ? carry[i] : recs[i - nc]; };
         uint64_t P = std::min<uint64_t>((uint64_t)threads * 4, total / 20000 + 1);
-        if (const char* e = getenv("HC_SFO_BUCKETS")) P = (uint64_t)std::max(1, atoi(e));
+        if (env::given(env::Knob::SFO_BUCKETS)) P = (uint64_t)std::max(1, env::i(env::Knob::SFO_BUCKETS, 0));
         if (P > 4096) P = 4096;
         std::vector<uint64_t> start(P + 1, total);
         start[0] = 0;
@@ -919,7 +919,7 @@ std::string SfoSortedMatcher::finish(uint64_t& n_lines) {
     m.carry.clear();
     const auto t0 = std::chrono::steady_clock::now();
     std::string out = stitch(m.res, n_lines);
-    if (getenv("HC_SFO_TIMING"))
+    if (env::given(env::Knob::SFO_TIMING))
         fprintf(stderr, "sorted SFO records: matching %.3f s (%zu pieces, %u threads), stitch %.3f s\n", m.match_s, m.res.size(), m.threads,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return out;

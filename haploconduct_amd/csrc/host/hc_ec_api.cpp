@@ -8,6 +8,7 @@
 
 #include "../../../include/hcedge_host.h"
 #include "EdgeCalculator.h"
+#include "EnvKnobs.h"
 
 #include <sys/stat.h>
 #include "NumaBind.h"
@@ -33,7 +34,7 @@ struct hc_ec {
 // Worth it when the FASTQ parsing beside it lasts longer than the extra work costs: on the SAVAGE example (2 ms of parsing) a process
 // with the warm-up took 0.178 s, without 0.163; with 0.3 GB of FASTQ it saves 0.05 s.
 bool hc::warm_up_pays(const ProgramSettings& ps) {
-    if (const char* w = getenv("HC_WARM")) return atoi(w) != 0;
+    if (env::given(env::Knob::WARM)) return env::i(env::Knob::WARM, 0) != 0;
     uint64_t bytes = 0;
     for (const std::string* f : {&ps.singles_file, &ps.paired1_file, &ps.paired2_file}) {
         struct stat sb;
@@ -94,7 +95,7 @@ int hc_ec_open(hc_ec** out, const hc_settings* settings, const hc_ec_paths* path
     *out = nullptr;
     std::unique_ptr<hc_ec> ec(new hc_ec());
     int rc = guarded("hc_ec_open", [&] {
-        const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
+        const bool timing = env::given(env::Knob::STAGE_TIMING);
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t0 = now();
         std::thread warm;  // once per process and device
@@ -138,7 +139,7 @@ int hc_ec_construct_edges_sorted(hc_ec* ec) {
     if (!ec) return set_last_error(HC_ERR_ARG, "hc_ec_construct_edges_sorted: null");
     const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     const int rc = guarded("construct_edges", [&] { ec->calc->construct_edges_sorted(); });
-    if (getenv("HC_STAGE_TIMING"))
+    if (env::given(env::Knob::STAGE_TIMING))
         fprintf(stderr, "[hc stage] hc_ec_construct_edges_sorted took %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0);
     return rc;
 }

@@ -23,12 +23,15 @@
 #include "Edge.h"
 #include "ExtLen.h"
 #include "EdgeCalculator.h"
+#include "EnvKnobs.h"
 #include "FastqStorage.h"
 #include "Overlap.h"
 #include "OverlapGraph.h"
 #include "TargetOrder.h"
 
 namespace hc {
+
+using env::Knob;
 
 // ------------------------------------------------------------------ Read
 node_id_t Read::get_vertex_id(bool normal) const {  // src/Read.h:111-120
@@ -255,7 +258,7 @@ struct MappedFastq {
         void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
         if (m == MAP_FAILED) return false;
         p = (const char*)m;
-        T = std::max(1u, std::min<unsigned>(T, (unsigned)(size >> (getenv("HC_FASTQ_GRAIN") ? 4 : 20)) + 1));
+        T = std::max(1u, std::min<unsigned>(T, (unsigned)(size >> (env::given(Knob::FASTQ_GRAIN) ? 4 : 20)) + 1));
         std::vector<uint64_t> nl(T + 1, 0);
         auto chunk = [&](unsigned t, size_t& a, size_t& b) {
             a = size * t / T;
@@ -321,14 +324,13 @@ bool FastqStorage::read_mapped(const std::string& path1, const std::string* path
     }
     const double tm0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     auto tlap = [&](const char* what) {
-        if (getenv("HC_STAGE_TIMING")) fprintf(stderr, "[hc stage] fastq %s at %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tm0);
+        if (env::given(Knob::STAGE_TIMING)) fprintf(stderr, "[hc stage] fastq %s at %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tm0);
     };
     const size_t n = paired ? std::min(f1.n, f2.n) : f1.n;  // records up to the shorter file, :170
     // small input: the sequential reader is as fast (HC_FASTQ_PARALLEL_MIN / HC_FASTQ_GRAIN: test knobs — bytes from which
     // this path is taken, records per thread at least)
-    size_t min_bytes = (size_t)4 << 20, grain = 4096;
-    if (const char* e = getenv("HC_FASTQ_PARALLEL_MIN")) min_bytes = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("HC_FASTQ_GRAIN")) grain = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));
+    const size_t min_bytes = (size_t)env::u64(Knob::FASTQ_PARALLEL_MIN, (uint64_t)4 << 20);
+    const size_t grain = std::max<size_t>(1, (size_t)env::u64(Knob::FASTQ_GRAIN, 4096));
     if (f1.size + f2.size < min_bytes) return false;
     const unsigned T = (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n / grain + 1));
     const size_t per = paired ? 2 : 1;
@@ -482,11 +484,11 @@ void FastqStorage::read_pairs(const std::string& p1, const std::string& p2, unsi
 }
 
 FastqStorage::FastqStorage(const ProgramSettings& ps) {  // src/FastqStorage.h:58-98
-    const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
+    const bool timing = env::given(Knob::STAGE_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     m_threads = std::max(1u, std::min(16u, (unsigned)ps.n_threads));
-    if (const char* e = getenv("HC_FASTQ_THREADS")) m_threads = (unsigned)std::max(1, atoi(e));
+    if (env::given(Knob::FASTQ_THREADS)) m_threads = (unsigned)std::max(1, env::i(Knob::FASTQ_THREADS, 0));
     if (!ps.id_correspondence.empty()) read_new_ids(ps.id_correspondence);
     if (!ps.singles_file.empty() && ps.singles_file != "None") read_singles(ps.singles_file, ps.max_reads);
     m_readcount_single = (unsigned int)m_singles_vec.size();
@@ -1002,16 +1004,7 @@ void OverlapGraph::bulk_add_edges(const Edge* pool, const std::vector<uint32_t>&
         for (uint32_t k : order) addEdge(pool[k]);
         return;
     }
-    static const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tp = now();
-    auto lap = [&](const char* what) {
-        if (timing) {
-            const double t = now();
-            fprintf(stderr, "[hc stage] bulk fill: %s %.3f s\n", what, t - tp);
-            tp = t;
-        }
-    };
+    env::Lap lap(Knob::STAGE_TIMING, "[hc stage] bulk fill: ");
     std::thread indexer([&] { slots.bulk_add(keys.data(), m, std::max(1u, T / 4)); });  // independent of the lists
     std::vector<uint32_t> out_deg(V, 0), in_deg(V, 0);
     run_workers(T, [&](unsigned t) {
@@ -1224,16 +1217,7 @@ void resolve_admitted_edges(OverlapGraph& g, const ProgramSettings& ps, Edge* ad
     if (n == 0) return;
     if (n > 0xFFFFFFFFull) throw FatalError{HC_ERR_STATE, "resolve_admitted_edges: more than 2^32 admitted edges"};
     const unsigned T = n < (1u << 14) ? 1u : std::max(1u, std::min<unsigned>((unsigned)ps.n_threads, 32u));
-    static const bool timing = getenv("HC_STAGE_TIMING") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tp = now();
-    auto lap = [&](const char* what) {
-        if (timing) {
-            const double t = now();
-            fprintf(stderr, "[hc stage] resolve: %s %.3f s\n", what, t - tp);
-            tp = t;
-        }
-    };
+    env::Lap lap(Knob::STAGE_TIMING, "[hc stage] resolve: ");
     struct Item {
         uint64_t key;  // smaller vertex << 33 | larger vertex << 1 | (ori1 == ori2)
         uint32_t seq;

@@ -88,6 +88,41 @@ def test_a_pipeline_of_changing_stages_through_one_resident_process(tmp_path):
         shutil.rmtree(sock_base, ignore_errors=True)
 
 
+def test_the_host_resolution_reads_its_timing_knob_job_by_job(tmp_path):
+    """HC_RESOLVE=host reaches resolve_admitted_edges (and, from a size on, OverlapGraph::bulk_add_edges), whose laps must follow the
+    CLIENT's HC_STAGE_TIMING job by job like every other print of the stage: set, unset, set through one resident process.  (A value
+    read once per process gave [True, True, True].)"""
+    from haploconduct_amd import synth
+
+    d = str(tmp_path) + "/"
+    sock_base = tempfile.mkdtemp(prefix="hcres-", dir="/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None)  # (sun_path: see above)
+    env = {k: v for k, v in os.environ.items() if k != "HC_STAGE_TIMING"}
+    env.update(HC_RESIDENT_DIR=os.path.join(sock_base, "res"), HC_RESIDENT_IDLE_S="60", HC_RESOLVE="host")
+    r1, m1 = synth.make_paired_dataset(4000, 6000, flip_frac=0.25, seed=21)
+    args = _case(d, "a", r1, synth.paired_candidates(m1, n_candidates=25000, seed=22), ["--edge_threshold", "0.97", "--min_overlap_len", "150"])
+    os.makedirs(d + "own")
+    own = subprocess.run([EXE] + args + ["--output", d + "own/"], env=env, capture_output=True, text=True, timeout=120)
+    assert own.returncode == 0, own.stderr[-1500:]
+    expected = open(d + "own/edges_sorted.tsv", "rb").read()
+    assert len(expected) > 1000
+    resolve, bulk = [], []
+    try:
+        for k, e in enumerate((dict(env, HC_STAGE_TIMING="1"), env, dict(env, HC_STAGE_TIMING="1"))):  # the first call starts the process
+            o = f"{d}res_{k}/"
+            os.makedirs(o)
+            r = subprocess.run([EXE, "--resident"] + args + ["--output", o], env=e, capture_output=True, text=True, timeout=120)
+            assert r.returncode == 0, (k, r.stderr[-1500:])
+            assert open(o + "edges_sorted.tsv", "rb").read() == expected, f"call {k}: the resident process wrote another graph"
+            resolve.append("[hc stage] resolve:" in r.stderr)
+            bulk.append("[hc stage] bulk fill:" in r.stderr)
+    finally:
+        subprocess.run([EXE, "--resident_stop"], env=env, timeout=60)
+        shutil.rmtree(sock_base, ignore_errors=True)
+    assert resolve == [True, False, True], resolve
+    if bulk[0]:
+        assert bulk == [True, False, True], bulk
+
+
 def test_stages_of_one_process_take_over_each_others_devices(tmp_path):
     """hc_ec_keep_devices (what the resident process does, for a caller that opens stage after stage itself): with it on, a closed stage's
     contexts and text blocks serve the next one — other reads, other settings, another kernel — and every graph equals the one a stage with
