@@ -90,6 +90,22 @@ class hc_branch_counts(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class hc_graph_text_settings(C.Structure):
+    _fields_ = [("edge_threshold", C.c_double), ("merge_contigs", C.c_double), ("n_singles", C.c_uint64)]
+
+
+class hc_graph_text_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_bytes", "n_lines", "n_pairs", "n_segments", "l_count", "c_count")] + \
+               [("status", C.c_uint32), ("pad", C.c_uint32), ("bad_v", C.c_uint64), ("bad_pos", C.c_uint64), ("ms_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+GRAPH_TEXT_KINDS = {"cliques": 0, "digraph": 1, "gfa": 2}  # HC_GRAPH_TEXT_*
+GRAPH_TEXT_STATUS = ("OK", "SELF_LOOP", "INCLUSION_HAS_EDGES", "WEAK_EDGE", "PAIRED_IN_SINGLES", "EMPTY_SEQ", "BAD_BASE")
+
+
 class hc_sr_settings(C.Structure):  # include/hcsr.h
     _fields_ = [("min_qual", C.c_double), ("min_clique_size", C.c_uint32), ("error_correction", C.c_uint32), ("subreads_needed", C.c_uint32),
                 ("n_threads", C.c_uint32)]
@@ -203,6 +219,8 @@ _sig = {
     "hc_graph_remove_branches": (C.c_int, [_vp, C.POINTER(hc_branch_counts)]),
     "hc_graph_fetch_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_graph_fetch_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "hc_graph_write_text": (C.c_int, [_vp, C.c_uint32, C.POINTER(hc_graph_text_settings), C.POINTER(hc_graph_text_counts)]),
+    "hc_graph_text_fetch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "hc_reset": (C.c_int, [_vp, _vp]),
     "hc_set_comm_reserve": (C.c_int, [_vp, C.c_uint32]),
     "hc_comm_gate_device": (C.c_int, [_vp, _vp, C.c_uint32]),

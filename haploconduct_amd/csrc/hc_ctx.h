@@ -231,6 +231,15 @@ struct hc_ctx {
         hipEvent_t stage_free[2] = {nullptr, nullptr};
         int stage_turn = 0;
     } graph;
+    // hc_graph_write_text / hc_graph_text_fetch (hc_api_graph_text.cpp): grow-only scratch — the items' byte counts (their exclusive sum
+    // after the scan), the records' keep bytes, the counters, the scan's workspace — and the text itself, n_bytes of it, kept until
+    // the next hc_graph_write_text or the next call that replaces or cleans the graph (drop())
+    struct GraphText {
+        hc_scratch sizes, keep, counters, temp, text;
+        uint64_t n_bytes = 0;
+        bool valid = false;
+        void drop() { valid = false, n_bytes = 0; }
+    } graph_text;
     // The consensus tables of one call path on the device (hc_api_sr.cpp: sr_tables): the log10 terms by term index, q_of itself, the
     // table of one- and two-member columns — and what they were built for.
     struct SrTables {

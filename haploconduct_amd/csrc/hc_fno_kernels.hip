@@ -3,6 +3,7 @@
 // radix sorts (least significant 64 bits first) one lane per sorted place drops repeated lines and measures the text;
 // after a scan one lane per line writes it.  Integer work, one float division per percentage (correctly rounded on
 // both sides, -ffp-contract=off).
+#include "hc_decimal.h"
 #include "hc_fno_device.h"
 
 namespace hc {
@@ -110,32 +111,7 @@ __device__ __forceinline__ uint64_t dec_key_signed(int32_t x) {
     for (int i = 0; i < 11; i++) key = key * 12 + (i < n ? ch[i] : 0);
     return key;
 }
-__device__ __forceinline__ uint32_t digits_u64(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
-__device__ __forceinline__ uint32_t chars_i32(int32_t x) {
-    const uint32_t v = x < 0 ? 0u - (uint32_t)x : (uint32_t)x;
-    return digits_u64(v) + (x < 0 ? 1u : 0u);
-}
-__device__ __forceinline__ char* put_u64(char* p, uint64_t v) {
-    char tmp[20];
-    int n = 0;
-    do {
-        tmp[n++] = (char)('0' + v % 10);
-        v /= 10;
-    } while (v);
-    while (n) *p++ = tmp[--n];
-    return p;
-}
-__device__ __forceinline__ char* put_i32(char* p, int32_t x) {  // std::to_string(int)
-    if (x < 0) *p++ = '-';
-    return put_u64(p, x < 0 ? 0u - (uint32_t)x : (uint32_t)x);
-}
+// (digits_u64 / chars_i32 / put_u64 / put_i32: hc_decimal.h)
 
 __global__ __launch_bounds__(kBlock) void fno_deduce_kernel(const FnoItem* __restrict__ items, uint64_t n, uint32_t no_inclusions,
                                                             FnoRec* __restrict__ rec, uint64_t* __restrict__ k0, uint64_t* __restrict__ k1,

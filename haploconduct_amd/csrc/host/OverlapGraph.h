@@ -134,6 +134,11 @@ public:
     void removeTips(unsigned int max_tip_len, const hc_read_geom* reads, size_t n_reads, hc_tip_counts* counts = nullptr);
     // src/GraphAlgos.cpp:835-936 (with :714-743, :746-833); adj_out is left in target order, as sortAdjOut leaves it
     void removeBranches(hc_branch_counts* counts = nullptr);
+    // writeGraphToFile (:322-385), writeDiGraphToFile (:388-409) and write2GFA (:468-543) into a string, with the contract of
+    // hc_graph_write_text (include/hcedge.h): a failed assert stops at its place and sets counts->status / bad_v / bad_pos.  The reads
+    // (GFA only): bases, seq_off (n_seq + 1), read_first_seq (n_reads + 1)
+    void writeText(uint32_t kind, const hc_graph_text_settings& st, const uint8_t* bases, const uint64_t* seq_off, const uint32_t* read_first_seq,
+                   uint64_t n_reads, std::string& out, hc_graph_text_counts& counts) const;
     double checkEdge(node_id_t v, node_id_t w, bool reverse_allowed) const;                   // :233-259
     // :608-719 (--add_duplicates; called at the end of construct_edges, EdgeCalculator.cpp:650-652): every edge once more
     // between the vertices of the reverse-complemented reads.  The mirrored edges carry no reverse offsets and no

@@ -490,6 +490,24 @@ int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_re
     return HC_OK;
 }
 
+int hc_host_graph_write_text(hc_host_graph* g, uint32_t kind, const hc_graph_text_settings* st, const uint8_t* bases, const uint64_t* seq_off,
+                             const uint32_t* read_first_seq, uint64_t n_reads, char* dst, uint64_t cap, hc_graph_text_counts* counts) {
+    if (!g || !st || !counts) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: null");
+    memset(counts, 0, sizeof *counts);
+    if (kind > HC_GRAPH_TEXT_GFA) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: unknown kind");
+    if (kind == HC_GRAPH_TEXT_GFA) {
+        if (!seq_off || !read_first_seq || (!bases && n_reads)) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: GFA needs the reads");
+        if (st->n_singles > n_reads) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: n_singles exceeds the reads");
+    }
+    std::string out;
+    const int rc = guarded("writeText", [&] { g->graph->writeText(kind, *st, bases, seq_off, read_first_seq, n_reads, out, *counts); });
+    if (rc != HC_OK) return rc;
+    if (out.size() > cap) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: the text is longer than the room given (counts->n_bytes)");
+    if (!out.empty() && !dst) return set_last_error(HC_ERR_ARG, "hc_host_graph_write_text: null destination");
+    if (!out.empty()) memcpy(dst, out.data(), out.size());
+    return HC_OK;
+}
+
 int hc_host_graph_free(hc_host_graph* g) {
     delete g;
     return HC_OK;

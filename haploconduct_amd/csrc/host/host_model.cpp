@@ -1644,4 +1644,102 @@ void OverlapGraph::removeBranches(hc_branch_counts* counts) {
     }
 }
 
+// ---- writeGraphToFile (:322-385), writeDiGraphToFile (:388-409), write2GFA (:468-543) -------------------------------
+
+void OverlapGraph::writeText(uint32_t kind, const hc_graph_text_settings& st, const uint8_t* bases, const uint64_t* seq_off,
+                             const uint32_t* read_first_seq, uint64_t n_reads, std::string& out, hc_graph_text_counts& counts) const {
+    memset(&counts, 0, sizeof counts);
+    out.clear();
+    const size_t V = adj_out.size();
+    auto stop = [&](uint32_t status, uint64_t v, uint64_t pos) {
+        out.clear();
+        memset(&counts, 0, sizeof counts);
+        counts.status = status;
+        counts.bad_v = v;
+        counts.bad_pos = pos;
+    };
+    if (kind == HC_GRAPH_TEXT_CLIQUES) {
+        std::string body;
+        uint64_t count = 0;
+        for (node_id_t i = 0; i < V; i++) {
+            if (inclusions[i] == 1) {
+                if (!adj_out[i].empty()) return stop(HC_GRAPH_TEXT_INCLUSION_HAS_EDGES, i, 0);  // :346
+                continue;
+            }
+            uint64_t pos = 0;
+            for (const Edge& e : adj_out[i]) {
+                const uint64_t at = pos++;
+                const node_id_t j = e.get_vertex(2);
+                if (inclusions[j] == 1) continue;                           // :352
+                if (j == i) return stop(HC_GRAPH_TEXT_SELF_LOOP, i, at);    // :355
+                if (j < i) {                                                 // :357, checkEdge(j, i, false): the first j -> i record
+                    double found = -1;
+                    for (const Edge& r : adj_out[j])
+                        if (r.get_vertex(2) == i) {
+                            if (!(r.get_score() >= st.edge_threshold || r.get_mismatch_rate() <= st.merge_contigs))
+                                return stop(HC_GRAPH_TEXT_WEAK_EDGE, i, at);  // :242
+                            found = r.get_score();
+                            break;
+                        }
+                    if (found > 0) continue;
+                }
+                body += std::to_string(i) + "," + std::to_string(j) + "\n";  // :362-365
+                body += std::to_string(j) + "," + std::to_string(i) + "\n";
+                count++;
+            }
+        }
+        out = std::to_string(V) + "\n" + std::to_string(2 * count) + "\n" + body;  // :373-376
+        counts.n_pairs = count;
+        counts.n_lines = 2 + 2 * count;
+    } else if (kind == HC_GRAPH_TEXT_DIGRAPH) {
+        for (node_id_t i = 0; i < V; i++) {
+            uint64_t pos = 0;
+            for (const Edge& e : adj_out[i]) {
+                const uint64_t at = pos++;
+                const node_id_t j = e.get_vertex(2);
+                if (j == i) return stop(HC_GRAPH_TEXT_SELF_LOOP, i, at);  // :402
+                out += std::to_string(i) + "\t" + std::to_string(j) + "\n";
+                counts.n_lines++;
+            }
+        }
+    } else {
+        const uint64_t readcount = n_reads, singlecount = st.n_singles;
+        auto is_segment = [&](uint64_t v) { return v < singlecount || (v >= readcount && v < readcount + singlecount); };
+        out = "H\tVN:Z:1.0\n";  // :478
+        for (node_id_t i = 0; i < V; i++) {
+            if (!is_segment(i)) continue;  // :503-506
+            const bool rev = i >= readcount;
+            const uint64_t rd = rev ? i - readcount : i;
+            const uint32_t q = read_first_seq[rd];
+            if (read_first_seq[rd + 1] - q != 1) return stop(HC_GRAPH_TEXT_PAIRED_IN_SINGLES, i, 0);  // :494, :500
+            std::string seq((const char*)bases + seq_off[q], (size_t)(seq_off[q + 1] - seq_off[q]));
+            if (rev) {  // build_rev_comp, src/Types.h:109-129
+                std::reverse(seq.begin(), seq.end());
+                for (char& c : seq) {
+                    if (c == 'A') c = 'T';
+                    else if (c == 'T') c = 'A';
+                    else if (c == 'C') c = 'G';
+                    else if (c == 'G') c = 'C';
+                    else if (c != 'N') return stop(HC_GRAPH_TEXT_BAD_BASE, i, 0);
+                }
+            }
+            if (seq.empty()) return stop(HC_GRAPH_TEXT_EMPTY_SEQ, i, 0);  // :508
+            out += "S\t" + std::to_string(i) + "\t" + seq + "\n";
+            counts.n_segments++;
+            uint64_t pos = 0;
+            for (const Edge& e : adj_out[i]) {
+                const uint64_t at = pos++;
+                const node_id_t j = e.get_vertex(2);
+                if (j == i) return stop(HC_GRAPH_TEXT_SELF_LOOP, i, at);  // :513
+                if (!is_segment(j)) continue;
+                out += "L\t" + std::to_string(i) + "\t+\t" + std::to_string(j) + "\t+\t" + std::to_string(e.get_len(0)) + "M\n";
+                if (e.get_perc() < 100) counts.l_count++;  // :519-531
+                else counts.c_count++;
+            }
+        }
+        counts.n_lines = 1 + counts.n_segments + counts.l_count + counts.c_count;
+    }
+    counts.n_bytes = out.size();
+}
+
 }  // namespace hc

@@ -97,6 +97,8 @@ _sig = {
     "hc_host_graph_remove_branches": (C.c_int, [_vp, C.POINTER(N.hc_branch_counts)]),
     "hc_host_graph_get_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_host_graph_get_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "hc_host_graph_write_text": (C.c_int, [_vp, C.c_uint32, C.POINTER(N.hc_graph_text_settings), _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64,
+                                           C.POINTER(N.hc_graph_text_counts)]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(N.lib, _name)
@@ -315,6 +317,25 @@ class HostGraph:
         N.check(N.lib.hc_host_graph_get_tip_reads(self._h, out.ctypes.data if n_reads else None, n_reads), "hc_host_graph_get_tip_reads")
         return out
 
+    def write_text(self, kind, edge_threshold=0.0, merge_contigs=0.0, n_singles=0, bases=None, seq_off=None, read_first_seq=None):
+        """hc_host_graph_write_text: graph.txt ("cliques"), digraph.txt ("digraph") or a GFA file ("gfa") of this graph as (bytes, counts);
+        the reads (GFA only): bases, seq_off (n_seq + 1), read_first_seq (n_reads + 1).  Counts first, then the text."""
+        st = N.hc_graph_text_settings(edge_threshold, merge_contigs, n_singles)
+        c = N.hc_graph_text_counts()
+        k = N.GRAPH_TEXT_KINDS.get(kind, kind)
+        b = None if bases is None else np.ascontiguousarray(bases, np.uint8)
+        so = None if seq_off is None else np.ascontiguousarray(seq_off, np.uint64)
+        fs = None if read_first_seq is None else np.ascontiguousarray(read_first_seq, np.uint32)
+        args = (None if b is None or not b.size else b.ctypes.data, None if so is None else so.ctypes.data, None if fs is None else fs.ctypes.data,
+                0 if fs is None else fs.size - 1)
+        rc = N.lib.hc_host_graph_write_text(self._h, k, C.byref(st), *args, None, 0, C.byref(c))
+        if rc == 0 or c.n_bytes == 0:  # an empty text, a failed assert, or a refusal
+            N.check(rc, "hc_host_graph_write_text")
+            return b"", c.as_dict()
+        out = np.empty(int(c.n_bytes), np.uint8)
+        N.check(N.lib.hc_host_graph_write_text(self._h, k, C.byref(st), *args, out.ctypes.data, out.size, C.byref(c)), "hc_host_graph_write_text")
+        return out.tobytes(), c.as_dict()
+
     def get(self):
         n = C.c_uint64()
         c = hc_ec_counters()
@@ -500,3 +521,8 @@ def sr_merge_next(reads, cons_seq, cons_qual, pairs, edge, vertex_read, vertex_f
     from . import merge_next as MN
 
     return MN.host_merge_next(reads, cons_seq, cons_qual, pairs, edge, vertex_read, vertex_fwd, **kw)
+
+
+def graph_write_text(graph: HostGraph, kind, **kw):
+    """hc_host_graph_write_text on a HostGraph: the mirror of Scorer.graph_write_text; (bytes, counts)."""
+    return graph.write_text(kind, **kw)

@@ -438,6 +438,22 @@ class EdgeScorer:
         N.check(N.lib.hc_graph_fetch_tip_reads(self._ctx, _ptr(out) if n_reads else None, n_reads), "hc_graph_fetch_tip_reads")
         return out
 
+    def graph_write_text(self, kind, edge_threshold=0.0, merge_contigs=0.0, n_singles=0, piece_bytes=None):
+        """hc_graph_write_text + hc_graph_text_fetch: graph.txt ("cliques"), digraph.txt ("digraph") or a GFA file ("gfa") of the device
+        graph as (bytes, counts).  piece_bytes: fetch the text in pieces of that many bytes.  A failed reference assert: empty bytes and
+        counts["status"] != 0 (N.GRAPH_TEXT_STATUS)."""
+        st = N.hc_graph_text_settings(edge_threshold, merge_contigs, n_singles)
+        c = N.hc_graph_text_counts()
+        N.check(N.lib.hc_graph_write_text(self._ctx, N.GRAPH_TEXT_KINDS.get(kind, kind), C.byref(st), C.byref(c)), "hc_graph_write_text")
+        if c.status != 0:
+            return b"", c.as_dict()
+        out = np.empty(int(c.n_bytes), np.uint8)
+        step = int(piece_bytes) if piece_bytes else max(out.size, 1)
+        for first in range(0, out.size, step):
+            n = min(step, out.size - first)
+            N.check(N.lib.hc_graph_text_fetch(self._ctx, first, n, _ptr(out[first:first + n])), "hc_graph_text_fetch")
+        return out.tobytes(), c.as_dict()
+
     def graph_fetch(self):
         """hc_graph_fetch of the graph the device holds: edges, out_off, in_nodes, in_off, seq, inclusions."""
         from .host import EDGE_DTYPE

@@ -619,6 +619,54 @@ int hc_graph_fetch_branching_edges(hc_ctx* ctx, hc_edge_rec* edges, uint64_t cap
 /* Read::is_tip() of reads [0, n_reads): one byte each (reads no hc_graph_remove_tips call has seen: 0). */
 int hc_graph_fetch_tip_reads(hc_ctx* ctx, uint8_t* is_tip, uint64_t n_reads);
 
+/* ---- graph.txt, digraph.txt and the GFA files from the device graph -----------------------------------------------------
+ * OverlapGraph::writeGraphToFile (src/OverlapGraph.cpp:322-385, the input of quick-cliques), writeDiGraphToFile (:388-409) and
+ * write2GFA (:468-543), which the reference calls in every iteration (src/ViralQuasispecies.cpp:312, 388-392): the bytes of the
+ * file, built on the device from the adjacency lists in list order (and, for GFA, from the raw reads hc_sr_keep_device keeps),
+ * the reference's statements evaluated in its order.  hc_graph_write_text leaves the graph as it found it and keeps the text on
+ * the device until the next hc_graph_write_text, hc_graph_load, hc_graph_resolve or hc_graph_remove_*; hc_graph_text_fetch copies
+ * a range of it out.  A graph hc_graph_resolve left with tied lists is refused as the cleaning calls refuse it (the file order is
+ * the list order).  The items of one text (records, plus vertices for GFA) are placed by one prefix sum over V + E < 2^32 of
+ * them, which hc_graph_load's limits (V, E < 2^31) always satisfy.
+ * A reference assert that would fail is no error of the call: HC_OK, counts->status != 0, n_bytes = 0, no text kept, and
+ * (bad_v, bad_pos) = the first such place in file order — the vertex, and the record's position in its list (0 for a status
+ * of the vertex itself: INCLUSION_HAS_EDGES, PAIRED_IN_SINGLES, EMPTY_SEQ, BAD_BASE). */
+#define HC_GRAPH_TEXT_CLIQUES 0u /* graph.txt      OverlapGraph.cpp:322-385 */
+#define HC_GRAPH_TEXT_DIGRAPH 1u /* digraph.txt    :388-409                 */
+#define HC_GRAPH_TEXT_GFA     2u /* graph*.gfa     :468-543                 */
+
+#define HC_GRAPH_TEXT_OK 0u
+#define HC_GRAPH_TEXT_SELF_LOOP 1u           /* assert (j != i), :355, :402, :513                                   */
+#define HC_GRAPH_TEXT_INCLUSION_HAS_EDGES 2u /* assert (it2->empty()), :346                                         */
+#define HC_GRAPH_TEXT_WEAK_EDGE 3u           /* checkEdge's assert on the first j -> i record, :242                 */
+#define HC_GRAPH_TEXT_PAIRED_IN_SINGLES 4u   /* assert (read->is_paired() == false), :494, :500                     */
+#define HC_GRAPH_TEXT_EMPTY_SEQ 5u           /* assert (seq.size() > 0), :508                                       */
+#define HC_GRAPH_TEXT_BAD_BASE 6u            /* build_rev_comp exits on the byte (src/Types.h:123-126)              */
+
+typedef struct hc_graph_text_settings {
+    double edge_threshold, merge_contigs; /* checkEdge's assert, :242 (CLIQUES only) */
+    uint64_t n_singles;                   /* FastqStorage::m_readcount_single (GFA only) */
+} hc_graph_text_settings;
+
+typedef struct hc_graph_text_counts {
+    uint64_t n_bytes, n_lines;
+    uint64_t n_pairs;            /* CLIQUES: `count` (:366); the header says 2 * count   */
+    uint64_t n_segments;         /* GFA: S lines                                          */
+    uint64_t l_count, c_count;   /* GFA: :522, :530                                       */
+    uint32_t status;             /* HC_GRAPH_TEXT_OK or the first failed assert, above    */
+    uint32_t pad;
+    uint64_t bad_v, bad_pos;     /* vertex and list position of that record / vertex      */
+    double ms_device;            /* this call's kernels and scans, by events              */
+} hc_graph_text_counts;
+
+/* GFA: vertex i is a segment iff i < n_singles (read i as stored) or n_reads <= i < n_reads + n_singles (read i - n_reads, reverse
+ * complement), n_reads = the reads of the store whose raw arrays are kept; every other vertex is skipped with its edges.  GFA
+ * without kept raw arrays: HC_ERR_STATE; n_singles > n_reads: HC_ERR_ARG. */
+int hc_graph_write_text(hc_ctx* ctx, uint32_t kind, const hc_graph_text_settings* st, hc_graph_text_counts* counts);
+/* Bytes [first, first + count) of the kept text into dst.  Synchronous.  A range outside the text: HC_ERR_ARG, nothing copied;
+ * no text kept: HC_ERR_STATE. */
+int hc_graph_text_fetch(hc_ctx* ctx, uint64_t first, uint64_t count, char* dst);
+
 /* PCI bus id of a device ("0000:c1:00.0"), for callers that place the host threads feeding it on its NUMA node
  * (/sys/bus/pci/devices/<id>/numa_node); the stage does (HC_NUMA=0 turns that off). */
 int hc_device_bus_id(int32_t device, char* bus_id, uint32_t cap);

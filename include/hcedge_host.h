@@ -214,6 +214,12 @@ int hc_host_graph_remove_branches(hc_host_graph* g, hc_branch_counts* counts);
 /* OverlapGraph::branching_edges so far (room for cap records; *n_out is always set) and Read::is_tip() of reads [0, n_reads). */
 int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint64_t cap, uint64_t* n_out);
 int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads);
+/* OverlapGraph::writeGraphToFile (src/OverlapGraph.cpp:322-385), writeDiGraphToFile (:388-409) and write2GFA (:468-543) on the bare
+ * graph, with the contract of hc_graph_write_text (include/hcedge.h): the reference's loops over the lists, string appends, the same
+ * statuses.  The reads (GFA only; NULL otherwise): bases, seq_off (n_seq + 1 offsets into them), read_first_seq (n_reads + 1).  The
+ * text goes to dst (room for cap bytes); a text longer than cap: HC_ERR_ARG with counts filled, so a caller can count, then fetch. */
+int hc_host_graph_write_text(hc_host_graph* g, uint32_t kind, const hc_graph_text_settings* st, const uint8_t* bases, const uint64_t* seq_off,
+                             const uint32_t* read_first_seq, uint64_t n_reads, char* dst, uint64_t cap, hc_graph_text_counts* counts);
 int hc_host_graph_free(hc_host_graph* g);
 
 /* Super-read consensus and edge merges on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts,
