@@ -115,6 +115,11 @@ class hc_sr_stats(C.Structure):
     _fields_ = [("n_columns", C.c_uint64), ("n_host_columns", C.c_uint64), ("ms_device", C.c_double), ("ms_host_finish", C.c_double)]
 
 
+class hc_sr_clique_stats(C.Structure):
+    _fields_ = [("sr", hc_sr_stats), ("n_filtered_layouts", C.c_uint64), ("n_host_filters", C.c_uint64), ("ms_layout", C.c_double),
+                ("ms_host_filter", C.c_double)]
+
+
 class hc_merge_pairs_stats(C.Structure):
     _fields_ = [("ms_kernel", C.c_double), ("ms_copy", C.c_double), ("ms_walk", C.c_double)]
 
@@ -167,6 +172,12 @@ _sig = {
                                    _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]),
     "hc_host_sr_edge_merge_layouts": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.POINTER(hc_sr_settings), _vp,
                                                 _vp, _vp, _vp, _vp, _vp]),
+    "hc_sr_clique_merge": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_clique_stats)]),
+    "hc_sr_clique_filter_on_host": (C.c_int, [_vp, C.c_int]),
+    "hc_host_sr_clique_merge_layouts": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(hc_sr_settings),
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(hc_sr_clique_stats)]),
+    "hc_host_sr_clique_filter": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(C.c_uint32)]),
     "hc_version": (C.c_char_p, []),
     "hc_strerror": (C.c_char_p, [C.c_int]),
     "hc_last_error": (C.c_char_p, []),

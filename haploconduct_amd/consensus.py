@@ -177,6 +177,133 @@ def host_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fw
     return _trim(status, first, layouts, members, sub)
 
 
+# ---- cliques of any size (hc_sr_clique_merge) ------------------------------------------------------------------------------
+SR_CLIQUE_TOO_SMALL, SR_CLIQUE_REPEATED_VERTEX = 6, 7
+SR_FILTER_NONE, SR_FILTER_GROUPS, SR_FILTER_STABLE, SR_FILTER_HOST = range(4)
+
+
+@dataclass
+class SrCliqueLayouts:
+    clique_status: np.ndarray  # uint32 per clique: SR_EDGE_* / SR_CLIQUE_*
+    first_layout: np.ndarray   # uint64, n_cliques + 1
+    layouts: np.ndarray        # SR_LAYOUT_DTYPE: the FULL lists, packed in clique order ('l' before 'r')
+    members: np.ndarray        # SR_MEMBER_DTYPE, packed
+    member_vertex: np.ndarray  # uint32 per member: sorted_vertices1 / sorted_vertices2
+    member_used: np.ndarray    # uint8 per member: handed to consensus
+    layout_filter: np.ndarray  # uint8 per layout: SR_FILTER_*
+    subreads: np.ndarray       # SR_SUBREAD_DTYPE per clique vertex, ascending vertex, at clique_off (None: the mirror without ret)
+    n_filtered_layouts: int = 0
+    n_host_filters: int = 0
+    ms_layout: float = 0.0
+    ms_host_filter: float = 0.0
+    result: SrResult = None    # the device call: hc_sr_consensus' outputs for the USED members
+
+    def used_layouts(self):
+        """(layouts, members) of the USED members, as hc_sr_consensus takes them."""
+        used = self.member_used.astype(bool)
+        before = np.concatenate([[0], np.cumsum(used)]).astype(np.uint64)
+        lay = self.layouts.copy()
+        fm = self.layouts["first_member"].astype(np.int64)
+        lay["first_member"] = before[fm]
+        lay["n_members"] = before[fm + self.layouts["n_members"].astype(np.int64)] - before[fm]
+        return lay, self.members[used]
+
+
+def clique_csr(cliques):
+    """[[vertex, ...], ...] -> (clique_off uint64, clique_nodes uint32)."""
+    off = np.zeros(len(cliques) + 1, np.uint64)
+    off[1:] = np.cumsum([len(q) for q in cliques])
+    nodes = np.asarray([v for q in cliques for v in q], np.uint32)
+    return off, nodes
+
+
+def _clique_buffers(clique_off, clique_nodes):
+    off = np.ascontiguousarray(clique_off, dtype=np.uint64)
+    nodes = np.ascontiguousarray(clique_nodes, dtype=np.uint32)
+    n, total = off.size - 1, int(off[-1])
+    if nodes.size != total:
+        raise ValueError("clique_nodes does not hold clique_off[-1] entries")
+    return (off, nodes, n, total, np.zeros(n, np.uint32), np.zeros(n + 1, np.uint64), np.zeros(2 * n, SR_LAYOUT_DTYPE),
+            np.zeros(2 * total, SR_MEMBER_DTYPE), np.zeros(2 * total, np.uint32), np.zeros(2 * total, np.uint8), np.zeros(2 * n, np.uint8))
+
+
+def _trim_clique(status, first, layouts, members, vertex, used, filt, subreads, stats, result=None):
+    nl = int(first[-1])
+    nm = int(layouts["n_members"][:nl].astype(np.int64).sum())
+    return SrCliqueLayouts(status, first, layouts[:nl], members[:nm], vertex[:nm], used[:nm], filt[:nl], subreads, int(stats.n_filtered_layouts),
+                           int(stats.n_host_filters), float(stats.ms_layout), float(stats.ms_host_filter), result)
+
+
+def clique_merge(ctx, clique_off, clique_nodes, vertex_read, vertex_fwd, settings, cap=None):
+    """hc_sr_clique_merge on the context's graph and store: constructSuperread (src/SRBuilder.cpp:654-748) for cliques of any size given as
+    a CSR of vertex ids.  Returns an SrCliqueLayouts with .result set.  cap: as edge_merge's."""
+    off, nodes, n, total, status, first, layouts, members, vertex, used, filt = _clique_buffers(clique_off, clique_nodes)
+    vr = np.ascontiguousarray(vertex_read, dtype=np.uint32)
+    vf = np.ascontiguousarray(vertex_fwd, dtype=np.uint8)
+    if vr.size != vf.size:
+        raise ValueError("vertex_read and vertex_fwd differ in length")
+    sub = np.zeros(total, SR_SUBREAD_DTYPE)
+    ret, lstat, out_off = np.zeros(2 * n, np.int32), np.zeros(2 * n, np.uint32), np.zeros(2 * n + 1, np.uint64)
+    n_bytes = C.c_uint64(0)
+    stats = N.hc_sr_clique_stats()
+
+    def once(seq, qual, room):
+        return N.lib.hc_sr_clique_merge(ctx, off.ctypes.data, _ptr(nodes), n, _ptr(vr), _ptr(vf), vr.size, C.byref(settings), _ptr(status),
+                                        first.ctypes.data, _ptr(layouts), _ptr(members), _ptr(vertex), _ptr(used), _ptr(filt), _ptr(sub), _ptr(ret),
+                                        _ptr(lstat), out_off.ctypes.data, _ptr(seq), _ptr(qual), room, C.byref(n_bytes), C.byref(stats))
+
+    if cap is None:
+        empty = np.zeros(0, np.uint8)
+        rc = once(empty, empty, 0)
+        if rc != 0 and n_bytes.value == 0:
+            N.check(rc, "sr_clique_merge")
+        cap = int(n_bytes.value)
+        seq, qual = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        if cap:
+            N.check(once(seq, qual, cap), "sr_clique_merge")
+    else:
+        seq, qual = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+        N.check(once(seq, qual, cap), "sr_clique_merge")
+    nl, nb = int(first[-1]), int(n_bytes.value)
+    res = SrResult(ret[:nl], lstat[:nl], out_off[:nl + 1], seq[:nb], qual[:nb], int(stats.sr.n_columns), int(stats.sr.n_host_columns),
+                   float(stats.sr.ms_device), float(stats.sr.ms_host_finish))
+    return _trim_clique(status, first, layouts, members, vertex, used, filt, sub, stats, res)
+
+
+def host_clique_merge_layouts(edges, out_off, reads, clique_off, clique_nodes, vertex_read, vertex_fwd, settings, ret=None):
+    """hc_host_sr_clique_merge_layouts: the layouts, filter_subreads' choice and (given the layouts' ret) the subread infos of clique_merge on a
+    host graph (hc_graph_fetch's edges / out_off) and a ReadSet."""
+    from .host import EDGE_DTYPE
+
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    oo = np.ascontiguousarray(out_off, dtype=np.uint64)
+    off, nodes, n, total, status, first, layouts, members, vertex, used, filt = _clique_buffers(clique_off, clique_nodes)
+    vr = np.ascontiguousarray(vertex_read, dtype=np.uint32)
+    vf = np.ascontiguousarray(vertex_fwd, dtype=np.uint8)
+    sub = None
+    if ret is not None:
+        ret = np.ascontiguousarray(ret, dtype=np.int32)
+        sub = np.zeros(total, SR_SUBREAD_DTYPE)
+    stats = N.hc_sr_clique_stats()
+    N.check(N.lib.hc_host_sr_clique_merge_layouts(_ptr(edges), oo.ctypes.data, oo.size - 1, reads.seq_off.ctypes.data, reads.read_first_seq.ctypes.data,
+                                                  reads.n_reads, off.ctypes.data, _ptr(nodes), n, _ptr(vr), _ptr(vf), C.byref(settings), _ptr(status),
+                                                  first.ctypes.data, _ptr(layouts), _ptr(members), _ptr(vertex), _ptr(used), _ptr(filt),
+                                                  None if ret is None else ret.ctypes.data, None if sub is None else _ptr(sub), C.byref(stats)),
+            "sr_clique_merge_layouts")
+    return _trim_clique(status, first, layouts, members, vertex, used, filt, sub, stats)
+
+
+def host_clique_filter(vertex, endpos, num, base_vertex, tie_order=0):
+    """hc_host_sr_clique_filter: filter_subreads' selection (src/SRBuilder.cpp:597-622) for one layout -> (used uint8 per entry, SR_FILTER_*)."""
+    vertex = np.ascontiguousarray(vertex, dtype=np.uint32)
+    endpos = np.ascontiguousarray(endpos, dtype=np.int32)
+    used = np.zeros(vertex.size, np.uint8)
+    cls = C.c_uint32(0)
+    N.check(N.lib.hc_host_sr_clique_filter(_ptr(vertex), _ptr(endpos), vertex.size, int(num), int(base_vertex), int(tie_order), _ptr(used),
+                                           C.byref(cls)), "sr_clique_filter")
+    return used, int(cls.value)
+
+
 def column(nucleotides, qualities, min_qual=0.99):
     """consensus_pos for one column given as byte strings: (nucleotide, quality byte), or None where it returns 0."""
     out = (C.c_uint8 * 2)()

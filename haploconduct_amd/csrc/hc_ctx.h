@@ -285,6 +285,14 @@ struct hc_ctx {
     struct SrEdge {
         hc_scratch targets, pairs, vread, vfwd, status, lay_cnt, mem_cnt, first, mem_off, layouts, members, who, sub, temp;
     } sr_edge;
+    // clique merge (hc_api_sr_clique.cpp: hc_sr_clique_merge): grow-only scratch, the blocks of hc_sr.h: SrCliqueView by name, the call's
+    // inputs and the scans' and sorts' workspace; filter_on_host: hc_sr_clique_filter_on_host
+    struct SrClique {
+        hc_scratch off, nodes, vread, vfwd, key_in, key, hit, slot, ecnt, eoff, sel, sub, failkey, base_rank, type, geom, ext, deg, rec_off, lay0,
+            pl_first, status, lay_cnt, first, mem_cnt, mem_off, pl, pl_total, pl_filter, ekey_in, ekey, eval_in, eval, ekey2, eval2, slotpos, fmem, fvert, fend,
+            fused, out_layouts, out_members, out_vertex, out_used, out_filter, uflag, uoff, temp;
+        bool filter_on_host = false;
+    } sr_clique;
     // hc_sr_merge_next (hc_api_sr_merge_next.cpp): grow-only scratch — the call's inputs; its slots (hc_sr_merge_next.h: Slots) and the merged
     // pairs' rewrites; the tables before they are copied out (t_*); the scans' workspace
     struct SrMergeNext {

@@ -6,7 +6,7 @@
 // sr_edge_layout_kernel (one lane per pair) does constructSuperread's ordering, type and base choice (src/SRBuilder.cpp:658-698) and
 // sort_vertices (:33-285) for a clique of two.  getEdgeInfo (src/OverlapGraph.cpp:263-282) is a scan in list order: a lane walks a list
 // of fewer than 64 records, the wave walks a longer one 64 records at a time and stops at the first chunk with a hit (the split of
-// hc_trans_kernels.hip: k_list_sum).  The list the reference builds by insertion (:198-222) has at most three entries; its order is
+// hc_trans_kernels.hip: k_list_sum; hc_sr_lay.h: find_first, shared with the clique kernels as is the per-node part of the loop).  The list the reference builds by insertion (:198-222) has at most three entries; its order is
 // (position ascending, insertion number descending), which three comparisons give.  Pairedness and lengths come from the store's read
 // descriptors; no symbol is read.  A pair writes into slots of its own; sr_edge_compact_kernel packs layouts and members behind two
 // exclusive sums.  sr_edge_subread_kernel is calcSubreadInfo (:536-595), one lane per pair, behind the consensus.
@@ -14,44 +14,16 @@
 #include <stdint.h>
 
 #include "hc_sr.h"
+#include "hc_sr_lay.h"
 
 namespace hc {
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
+using namespace srlay;  // find_first, FoundEdge, base_member, lay_node, sub_place
 
 __global__ __launch_bounds__(256) void sr_edge_target_kernel(const hc_edge_rec* __restrict__ E, uint64_t n, uint32_t* __restrict__ tgt) {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) tgt[k] = (uint32_t)E[k].v2;
-}
-
-// The first k in [a, b) with E[k].v2 == target, or kNone; every lane of the wave calls it (a == b: nothing to find).
-__device__ uint32_t find_first(const hc_edge_rec* __restrict__ E, uint32_t a, uint32_t b, uint32_t target, uint32_t lane) {
-    uint32_t hit = kNone;
-    const bool is_long = b - a >= 64;
-    if (!is_long)
-        for (uint32_t k = a; k < b; k++)
-            if (E[k].v2 == target) {
-                hit = k;
-                break;
-            }
-    unsigned long long longs = __ballot(is_long);
-    while (longs) {
-        const int j = __ffsll((long long)longs) - 1;
-        longs &= longs - 1;
-        const uint32_t aj = __shfl(a, j), bj = __shfl(b, j), tj = __shfl(target, j);
-        uint32_t found = kNone;
-        for (uint32_t base = aj; base < bj; base += 64) {  // (wave-uniform: aj, bj and the ballot are)
-            const uint32_t k = base + lane;
-            const unsigned long long m = __ballot(k < bj && E[k].v2 == tj);
-            if (m) {
-                found = base + (uint32_t)(__ffsll((long long)m) - 1);
-                break;
-            }
-        }
-        if ((int)lane == j) hit = found;
-    }
-    return hit;
 }
 
 struct Entry {
@@ -64,12 +36,6 @@ struct Entry {
 // an entry inserted later goes in front of the first whose position is not smaller (:198-222)
 __device__ inline bool before(const Entry& x, const Entry& y) { return x.pos < y.pos || (x.pos == y.pos && x.ins > y.ins); }
 
-struct FoundEdge {
-    uint32_t read1, read2;
-    int32_t pos1, pos2;
-    uint8_t ord;
-};
-
 // sort_vertices for {base, node} with the record found: HC_SR_EDGE_*; on OK the members (positions shifted), who and total_len
 __device__ uint32_t lay_one(const StoreView& st, char type, uint32_t base_ID, const ReadDesc& bd, bool base_fwd, bool node_fwd, uint8_t base_who,
                             const FoundEdge& e, hc_sr_member* out, uint8_t* who, uint32_t* n_out, int32_t* total_out) {
@@ -77,57 +43,23 @@ __device__ uint32_t lay_one(const StoreView& st, char type, uint32_t base_ID, co
     en[0].pos = 0;
     en[0].ins = 0;
     en[0].who = base_who;
-    en[0].m.read = base_ID;
-    en[0].m.pos = 0;
-    en[0].m.pad[0] = en[0].m.pad[1] = 0;
-    en[0].m.rev = base_fwd ? 0 : 1;
-    en[0].m.seq = type == 's' ? 0 : ((type == 'l') == base_fwd ? 1 : 2);  // :47-76
+    en[0].m = base_member(type, base_ID, base_fwd);  // :47-76
     en[0].len = en[0].m.seq == 2 ? bd.len2 : bd.len1;
-    const bool base_is_1 = e.read1 == base_ID, base_is_2 = e.read2 == base_ID;
-    if (!base_is_1 && !base_is_2) return HC_SR_EDGE_READ_MISMATCH;  // :108
-    const uint32_t current_id = base_is_1 ? e.read2 : e.read1;      // :104-110
-    if (current_id >= st.n_reads) return HC_SR_EDGE_BAD_VERTEX;
-    const ReadDesc cd = st.reads[current_id];
-    const bool cur_paired = (cd.flags & kReadPaired) != 0;
-    char current_type = type;
-    if (type == 's') current_type = cur_paired ? 'p' : 's';  // :114-122
-    else if (!cur_paired) return HC_SR_EDGE_READ_MISMATCH;    // src/Read.h:145-149
+    const int64_t base_len = en[0].len;
+    NodeLay nl;
+    const uint32_t st_node = lay_node(st, type, base_ID, base_len, node_fwd, e, nl);  // :101-238, shared with the clique kernels
+    if (st_node != HC_SR_EDGE_OK) return st_node;
     uint32_t n = 1;
-    const int64_t p1 = base_is_1 ? (int64_t)e.pos1 : -(int64_t)e.pos1;  // :142-147, :159-164
-    int64_t new_pos = p1, new_pos1 = p1;
-    Entry c;
-    c.who = base_who ^ 1;
-    c.m.read = current_id;
-    c.m.pos = 0;
-    c.m.pad[0] = c.m.pad[1] = 0;
-    c.m.rev = node_fwd ? 0 : 1;
-    if (current_type == 's') c.m.seq = 0;
-    else c.m.seq = node_fwd ? 1 : 2;  // :151-158
-    if (current_type == 'p') {
-        c.pos = new_pos1;
-        c.len = c.m.seq == 2 ? cd.len2 : cd.len1;
+    for (uint32_t k = 0; k < nl.n; k++) {
+        Entry c;
+        c.who = base_who ^ 1;
+        c.m = nl.m[k];
+        c.pos = nl.pos[k];
+        c.len = nl.len[k];
         c.ins = n;
         en[n++] = c;
     }
-    if (current_type == 'r' || current_type == 'p') {  // :171-188
-        c.m.seq = node_fwd ? 2 : 1;
-        if (current_type == 'p' || (base_is_1 && e.ord == '1') || (base_is_2 && e.ord == '2')) new_pos = e.pos2;
-        else new_pos = -(int64_t)e.pos2;
-    }
-    c.pos = new_pos;
-    c.len = c.m.seq == 2 ? cd.len2 : cd.len1;
-    c.ins = n;
-    en[n++] = c;
-    const int64_t base_len = en[0].len;
-    int64_t len1, len2;  // :225-240
-    if (current_type == 'p') {
-        if (new_pos < 0) return HC_SR_EDGE_PAIRED_NEG_POS;  // :227
-        len1 = -new_pos1;
-        len2 = max((int64_t)en[2].len + new_pos - base_len, (int64_t)en[1].len + new_pos1 - base_len);
-    } else {
-        len1 = -new_pos;
-        len2 = (int64_t)en[1].len + new_pos - base_len;
-    }
+    const int64_t len1 = nl.len1, len2 = nl.len2;
     const int64_t total_len = base_len + max(len1, (int64_t)0) + max(len2, (int64_t)0);  // :239-244
     if (total_len > INT32_MAX) return HC_SR_EDGE_BAD_GEOMETRY;
     // list order: (position ascending, insertion number descending)
@@ -266,17 +198,6 @@ __global__ __launch_bounds__(256) void sr_edge_compact_kernel(SrEdgeSlots S, uin
         L.first_member = m;
         layouts[l++] = L;
         for (uint32_t j = 0; j < L.n_members; j++) members[m++] = S.members[6 * i + 3 * k + j];
-    }
-}
-
-// :548-555 / :561-568 / :583-590: (index, startpos) of an entry at `pos` under trim position `trim`
-__device__ inline void sub_place(int32_t trim, int32_t pos, int32_t& index, int32_t& startpos) {
-    if (trim > pos) {
-        startpos = trim - pos;
-        index = 0;
-    } else {
-        startpos = 0;
-        index = pos - trim;
     }
 }
 

@@ -515,6 +515,15 @@ def sr_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fwd,
     return SR.host_edge_merge_layouts(edges, out_off, reads, pairs, vertex_read, vertex_fwd, SR.make_settings(min_clique_size=min_clique_size), ret)
 
 
+def sr_clique_merge_layouts(edges, out_off, reads, clique_off, clique_nodes, vertex_read, vertex_fwd, ret=None, min_clique_size=2):
+    """hc_host_sr_clique_merge_layouts: the host mirror of EdgeScorer.sr_clique_merge's layouts, filter and subread infos (sort_vertices,
+    filter_subreads and calcSubreadInfo, src/SRBuilder.cpp:33-285, 597-651, 536-595).  ret: the layouts' consensus return values."""
+    from . import consensus as SR
+
+    return SR.host_clique_merge_layouts(edges, out_off, reads, clique_off, clique_nodes, vertex_read, vertex_fwd,
+                                        SR.make_settings(min_clique_size=min_clique_size), ret)
+
+
 def sr_merge_next(reads, cons_seq, cons_qual, pairs, edge, vertex_read, vertex_fwd, **kw):
     """hc_host_sr_merge_next: the host mirror of EdgeScorer.sr_merge_next (process_cliques and mergeAlongEdges, src/SRBuilder.cpp:981-1001,
     1260-1380) on a ReadSet and the consensus bytes of the edge merge.  kw: merge_next.host_merge_next's further arguments."""

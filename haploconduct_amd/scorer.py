@@ -107,6 +107,19 @@ class EdgeScorer:
         st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
         return SR.edge_merge(self._ctx, pairs, vertex_read, vertex_fwd, st, cap)
 
+    def sr_clique_merge(self, clique_off, clique_nodes, vertex_read, vertex_fwd, min_qual=0.99, min_clique_size=2, error_correction=False,
+                        subreads_needed=False, n_threads=16, cap=None):
+        """hc_sr_clique_merge: constructSuperread (src/SRBuilder.cpp:654-748) for cliques of any size of the device graph, given as a CSR of
+        vertex ids — sort_vertices, filter_subreads, consensus and calcSubreadInfo.  Returns a consensus.SrCliqueLayouts with .result."""
+        from . import consensus as SR
+
+        st = SR.make_settings(min_qual, min_clique_size, error_correction, subreads_needed, n_threads)
+        return SR.clique_merge(self._ctx, clique_off, clique_nodes, vertex_read, vertex_fwd, st, cap)
+
+    def sr_clique_filter_on_host(self, on=True):
+        """hc_sr_clique_filter_on_host: a test switch — every filtered layout of sr_clique_merge goes to the host's filter."""
+        N.check(N.lib.hc_sr_clique_filter_on_host(self._ctx, 1 if on else 0), "sr_clique_filter_on_host")
+
     # -- the next iteration's store from super-reads (include/hcsr.h) -----------
     def sr_keep_device(self, on=True):
         """hc_sr_keep_device: set_reads keeps its raw arrays and sr_consensus its output on the device (off by default)."""

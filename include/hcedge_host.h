@@ -222,8 +222,9 @@ int hc_host_graph_write_text(hc_host_graph* g, uint32_t kind, const hc_graph_tex
                              const uint32_t* read_first_seq, uint64_t n_reads, char* dst, uint64_t cap, hc_graph_text_counts* counts);
 int hc_host_graph_free(hc_host_graph* g);
 
-/* Super-read consensus and edge merges on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table, hc_host_sr_edge_layouts,
- * hc_host_graph_merge_pairs, hc_host_sr_edge_merge_layouts): include/hcsr.h,
+/* Super-read consensus, edge merges and clique merges on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table,
+ * hc_host_sr_edge_layouts, hc_host_graph_merge_pairs, hc_host_sr_edge_merge_layouts, hc_host_sr_clique_merge_layouts,
+ * hc_host_sr_clique_filter): include/hcsr.h,
  * which includes this header's records. */
 
 #ifdef __cplusplus

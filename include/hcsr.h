@@ -6,7 +6,7 @@
  *
  * A LAYOUT is what sort_vertices (src/SRBuilder.cpp:33-285) hands to consensus: total_len and the members in list order
  * (positions ascending, the first is 0).  A MEMBER names a stored sequence instead of carrying strings.
- * Layouts of cliques of more than two vertices are left to the caller; those of edge merges: hc_sr_edge_merge.
+ * Layouts of edge merges: hc_sr_edge_merge; of cliques of any size: hc_sr_clique_merge.
  */
 #ifndef HCSR_H_
 #define HCSR_H_
@@ -116,8 +116,8 @@ int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const ui
  * (src/SRBuilder.cpp:654-698), which lays it out with sort_vertices (:33-285) and calls consensus.  The calls of this section
  * do that on the graph the context holds (hc_graph_resolve / hc_graph_load and the cleaning calls), for every combination of
  * single-end and paired reads.
- * Left to the caller: cliques of more than two vertices and filter_subreads (:597-651), clique enumeration, the
- * original-index maps (:750-843) and subreads.txt.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next.) */
+ * Cliques of more than two vertices and filter_subreads (:597-651): hc_sr_clique_merge, the next section.  Left to the caller: clique
+ * enumeration, the original-index maps (:750-843) and subreads.txt.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next.) */
 
 typedef struct hc_merge_pairs_stats {
     double ms_kernel; /* device call only: the target-column kernel, by events on the context's stream */
@@ -197,6 +197,92 @@ int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_
                                   const uint32_t* vertex_read, const uint8_t* vertex_fwd, const hc_sr_settings* settings,
                                   uint32_t* pair_status, uint64_t* first_layout, hc_sr_layout* layouts, hc_sr_member* members,
                                   const int32_t* ret, hc_sr_subread_info* subreads);
+
+/* ---- cliques of any size on the device graph: SRBuilder::cliquesToSuperreads -> process_cliques -> constructSuperread ----------
+ *
+ * constructSuperread (src/SRBuilder.cpp:654-748) for a clique of any number of vertices: the sort of the clique (:658), the type
+ * and base choice (:669-679), sort_vertices (:33-285) with getEdgeInfo(base, node) for every member (src/OverlapGraph.cpp:263-282),
+ * filter_subreads / sortVerticesByEndpos (:597-651) where the clique is larger than 3 * min_clique_size (:721), consensus
+ * (:413-535) and calcSubreadInfo (:536-595).
+ * Left to the caller: reading cliques.txt, remove_multi_occ and the minCliqueSize gate (:1056-1084; remove_multi_occ is a serial
+ * greedy pass over a text file), clique enumeration, the original-index maps (:750-843) and subreads.txt, and a clique form of
+ * hc_sr_merge_next (marks, trivials, FNO tables from these outputs). */
+
+/* Per-clique status: the HC_SR_EDGE_* values and two more.  Where several members of a clique fail, the status is that of the first
+ * failing vertex in the loop's order (ascending vertex, :658, :87) and within a vertex the reference's order of checks; the asserts
+ * behind the loop (:246-281, HC_SR_EDGE_BAD_GEOMETRY) count only if the loop passed.  The range checks run before the loop: a clique
+ * with a vertex >= n_vertices or a vertex_read beyond the store is HC_SR_EDGE_BAD_VERTEX and reads nothing further. */
+enum {
+    HC_SR_CLIQUE_TOO_SMALL = 6,       /* fewer than two vertices (assert, :656)                                                        */
+    HC_SR_CLIQUE_REPEATED_VERTEX = 7  /* a vertex listed twice: a stated tightening, as v == w is for pairs (a clique of exactly two
+                                         equal vertices reports HC_SR_EDGE_BAD_VERTEX, as hc_sr_edge_merge does)                       */
+};
+
+/* What filter_subreads did to a layout.  sortVerticesByEndpos ends in an unstable std::sort (:640); the selection walks the endpos
+ * groups from the largest down, and only a group that is cut depends on the order among its ties (host/SrCliqueFilter.h). */
+enum {
+    HC_SR_FILTER_NONE = 0,   /* clique.size() <= 3 * min_clique_size: every member is used                                             */
+    HC_SR_FILTER_GROUPS = 1, /* only whole groups of equal endpos were taken: the order among ties cannot matter                       */
+    HC_SR_FILTER_STABLE = 2, /* a group was cut in a layout of at most 16 entries: libstdc++'s std::sort is one insertion sort there,
+                                which is stable, so the cut takes the group's entries from the back of the list order                  */
+    HC_SR_FILTER_HOST = 3    /* a group was cut in a longer layout: decided by std::sort itself, on the host                           */
+};
+
+typedef struct hc_sr_clique_stats {
+    hc_sr_stats sr;              /* the consensus' share, as hc_sr_consensus reports it                                                 */
+    uint64_t n_filtered_layouts; /* layouts that went through filter_subreads                                                           */
+    uint64_t n_host_filters;     /* of them HC_SR_FILTER_HOST (device call: decided by host threads)                                    */
+    double ms_layout;            /* device call only: the layout, filter and subread kernels, by events on the context's stream         */
+    double ms_host_filter;       /* device call only: fetching, deciding and uploading the host-decided filters                         */
+} hc_sr_clique_stats; /* 64 bytes */
+
+/* constructSuperread for every clique i = clique_nodes[clique_off[i] .. clique_off[i + 1]) (process_cliques' clique_vec, :980, as a
+ * CSR of vertex ids, in any order inside a clique) on the context's graph.  N = clique_off[n_cliques] entries in all.
+ * Needs hc_set_reads and a graph without tied lists (HC_ERR_STATE otherwise).  HC_ERR_ARG: min_clique_size == 0 (with num == 0 the
+ * filter may drop the first list entry, a layout hc_sr_consensus refuses); n_vertices is not the graph's; descending clique_off;
+ * N >= 2^31 or 2^32 records or more.  vertex_read / vertex_fwd: as hc_sr_edge_merge takes them.
+ * A clique of two gives exactly what hc_sr_edge_merge gives for the same pair.
+ * Outputs, packed in clique order: clique_status[i]; first_layout (n_cliques + 1: one layout for type 's', two for 'p', 'l' then 'r');
+ * layouts (room for 2 n_cliques) and members / member_vertex / member_used (room for 2 N each): the FULL lists sort_vertices returned,
+ * as hc_sr_consensus takes them — member_vertex = sorted_vertices1 / sorted_vertices2, which set_sorted_clique keeps (:853-864);
+ * member_used = 1 where the member was handed to consensus (all unless clique.size() > 3 * min_clique_size, else filter_subreads' choice
+ * for num = 2 * min_clique_size); layout_filter (room for 2 n_cliques; may be NULL): HC_SR_FILTER_*.
+ * ret / status / out_off (2 n_cliques, 2 n_cliques, 2 n_cliques + 1) / cons_seq / cons_qual / cap / *n_bytes: hc_sr_consensus' outputs
+ * for the USED members of each layout with the layout's full total_len (:725-741), by the same code (with hc_sr_keep_device on, the bytes
+ * stay on the device exactly as after hc_sr_consensus); cap too small: HC_ERR_ARG with everything but the bytes filled.
+ * subreads (room for N): calcSubreadInfo on the FULL lists with trim_pos1 / trim_pos2 = the ret of the layouts (:748), one entry per
+ * clique vertex in ASCENDING VERTEX order at clique_off[i] (deterministic, not the unordered_map's order): a vertex's first entry in
+ * list 1 gives index1 / startpos1, its second entry in list 1 (a paired read in an 's' layout) or its entry in list 2 ('p') index2 /
+ * startpos2; a dummy is -1; a clique without layouts has all four -1.  stats may be NULL. */
+int hc_sr_clique_merge(hc_ctx* ctx, const uint64_t* clique_off, const uint32_t* clique_nodes, uint64_t n_cliques, const uint32_t* vertex_read,
+                       const uint8_t* vertex_fwd, uint64_t n_vertices, const hc_sr_settings* settings, uint32_t* clique_status,
+                       uint64_t* first_layout, hc_sr_layout* layouts, hc_sr_member* members, uint32_t* member_vertex, uint8_t* member_used,
+                       uint8_t* layout_filter, hc_sr_subread_info* subreads, int32_t* ret, uint32_t* status, uint64_t* out_off,
+                       uint8_t* cons_seq, uint8_t* cons_qual, uint64_t cap, uint64_t* n_bytes, hc_sr_clique_stats* stats);
+
+/* A test switch of the context, off by default: while on, hc_sr_clique_merge sends EVERY filtered layout to the host's filter.  The
+ * outputs must not change (layout_filter still reports the classification). */
+int hc_sr_clique_filter_on_host(hc_ctx* ctx, int on);
+
+/* The layouts, the filter's choice and the subread infos of hc_sr_clique_merge on the host (no device, no context): a graph as
+ * hc_graph_fetch returns it and the read table as hc_set_reads takes it.  It walks the reference's loops as written: std::list
+ * insertions, a std::set of selected vertices and std::sort with the reference's comparator on a vector in list order.  ret (per
+ * layout, what a consensus call returned for the USED members) is an INPUT of the subread infos; with ret NULL subreads is not written.
+ * stats (may be NULL): n_filtered_layouts and n_host_filters. */
+int hc_host_sr_clique_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, const uint64_t* seq_off,
+                                    const uint32_t* read_first_seq, uint32_t n_reads, const uint64_t* clique_off, const uint32_t* clique_nodes,
+                                    uint64_t n_cliques, const uint32_t* vertex_read, const uint8_t* vertex_fwd, const hc_sr_settings* settings,
+                                    uint32_t* clique_status, uint64_t* first_layout, hc_sr_layout* layouts, hc_sr_member* members,
+                                    uint32_t* member_vertex, uint8_t* member_used, uint8_t* layout_filter, const int32_t* ret,
+                                    hc_sr_subread_info* subreads, hc_sr_clique_stats* stats);
+
+/* filter_subreads' selection (:597-622) for ONE layout given as (vertex, endpos) per entry in list order: used[k] = 1 where entry k's
+ * vertex is selected; *filter = HC_SR_FILTER_GROUPS / _STABLE / _HOST by the shared group rule.  tie_order chooses how ties of
+ * sortVerticesByEndpos are ordered: 0 = std::sort with the reference's comparator (the reference), 1 = list order inside every group
+ * (a stable sort), 2 = reversed list order inside every group.  HC_ERR_ARG: n == 0, num > the layout's distinct vertices (the
+ * reference asserts, :619), or the base is no entry. */
+int hc_host_sr_clique_filter(const uint32_t* vertex, const int32_t* endpos, uint32_t n, uint32_t num, uint32_t base_vertex, int tie_order,
+                             uint8_t* used, uint32_t* filter);
 
 /* ---- self-overlapping paired super-reads: SRBuilder::merge_self_overlap (src/SRBuilder.cpp:872-955) --------------------
  *
@@ -325,7 +411,7 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
  * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
  * context's read store by the result.
- * Left to the caller: the original-index maps and subreads.txt (the subread infos of an edge merge: hc_sr_edge_merge); the FASTQ
+ * Left to the caller: the original-index maps and subreads.txt (the subread infos: hc_sr_edge_merge, hc_sr_clique_merge); the FASTQ
  * text itself.  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
  * clique that merge_self_overlap merged (:911-949) itself; hc_sr_merge_next below builds the list, the marks, the tips and the
  * shifted cliques from an edge merge's outputs.  (The self-overlap test between the consensus call and this one runs on the kept
@@ -438,7 +524,8 @@ int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in
  * arrival order (:1004-1011), which is not deterministic; one thread gives pair order.
  * Left to the caller: the original-index maps (:750-843, :1312-1369) and subreads.txt; the FASTQ text, including
- * removed_tip_sequences.fastq (the tips list names the vertices); cliques of more than two vertices. */
+ * removed_tip_sequences.fastq (the tips list names the vertices); this call for cliques of more than two vertices
+ * (hc_sr_clique_merge lays them out and merges them; the marks, trivials and FNO tables from ITS outputs are not built). */
 
 typedef struct hc_sr_merge_next_input {
     /* what hc_sr_edge_merge returned, unchanged: host arrays */
