@@ -621,10 +621,11 @@ static int ensure_sort_workspace(hc_ctx* c, uint64_t n) {
 
 }  // extern "C"
 
-// The locality order (hc_locality.hip) from this many candidates on: its index passes cost a fixed ~0.09 ms (a binary search per read) plus
-// ~0.13 ms per 10^8 records (the permutation), and pay from somewhere between C2's 2 * 10^6 (0.153 -> 0.187 ms, slower) and C3-lite's
+// The locality order (hc_locality.hip) from this many candidates on: when the threshold was derived its index passes cost a fixed ~0.09 ms
+// (a binary search per read, a scan) plus ~0.13 ms per 10^8 records (the permutation), and paid from somewhere between C2's 2 * 10^6 (0.153 -> 0.187 ms, slower) and C3-lite's
 // 2 * 10^7 (1.475 -> 1.387 ms); C3, 10^8: 6.56 -> 5.85 ms (profiles/r07_locality_order.md).  HC_LOCALITY=0 turns it off, HC_LOCALITY_MIN
-// moves the threshold (A/B and test knobs, read at every launch).
+// moves the threshold (A/B and test knobs, read at every launch).  (Since then: ~0.08 ms fixed — the scan's three kernels are gone — plus
+// ~0.08 ms per 10^8 records, profiles/r09_item_feed.md; the crossover was not measured again and the threshold stays.)
 static constexpr uint64_t kLocalityMinCandidates = 8000000;
 static bool locality_wanted(uint64_t n) {
     if (env::i(Knob::LOCALITY, 1) == 0) return false;
@@ -666,19 +667,17 @@ int hc_ctx_score(hc_ctx* c, uint32_t fmt, const void* d_in, uint64_t n, void* d_
         perm = perm_out;
     }
     const uint32_t* order_off = nullptr;
-    if (want_loc) {  // flag, run boundaries (R + 2), run starts (R + 1), then the launch's permutation (n)
+    if (want_loc) {  // flag, run boundaries (R + 2), the index passes' own words, then the launch's permutation (n, 16-byte aligned)
         const uint32_t R = c->loc_reads;
-        const size_t head = ((size_t)R + 2 + (size_t)R + 1 + 1 + 3) & ~(size_t)3;
-        const size_t tmp = hc::locality_index_temp_bytes(R);
+        const size_t head = (1 + (size_t)R + 2 + hc::locality_index_work_words(R) + 3) & ~(size_t)3;
         if ((head + n) * sizeof(uint32_t) > c->loc_ws.cap && c->scratch_used) HC_HIP(hipEventSynchronize(c->scratch_done));  // (as sink_rows)
         int rc = c->loc_ws.ensure((head + n) * sizeof(uint32_t));
-        if (rc == HC_OK) rc = c->loc_tmp.ensure(tmp ? tmp : 16);
         if (rc) return rc;
         uint32_t* flag = c->loc_ws.as<uint32_t>();
         uint32_t* bounds = flag + 1;
-        uint32_t* starts = bounds + R + 2;
+        uint32_t* work = bounds + R + 2;
         uint32_t* lperm = c->loc_ws.as<uint32_t>() + head;
-        HC_HIP(hc::launch_locality_index(c->loc_order.as<uint32_t>(), R, d_in, n, n_dev, bounds, starts, flag, lperm, c->loc_tmp.p, tmp, s));
+        HC_HIP(hc::launch_locality_index(c->loc_order.as<uint32_t>(), R, d_in, n, n_dev, bounds, work, flag, lperm, s));
         perm = lperm;
         order_off = flag;
     }

@@ -102,9 +102,9 @@ hipError_t launch_flush_rows(const void* src, void* dst_mapped, const unsigned l
 size_t locality_order_temp_bytes(uint32_t n_reads);
 hipError_t launch_locality_order(const uint8_t* bases, const uint64_t* raw_off, const uint32_t* read_first_seq, uint32_t n_reads, uint64_t* keys_a,
                                  uint64_t* keys_b, uint32_t* idx, uint32_t* order_out, void* temp, size_t temp_bytes, hipStream_t stream);
-size_t locality_index_temp_bytes(uint32_t n_reads);
+size_t locality_index_work_words(uint32_t n_reads);
 hipError_t launch_locality_index(const uint32_t* order, uint32_t n_reads, const void* in, uint64_t n, const unsigned long long* n_dev, uint32_t* bounds,
-                                 uint32_t* start, uint32_t* flag, uint32_t* perm, void* temp, size_t temp_bytes, hipStream_t stream);
+                                 uint32_t* work, uint32_t* flag, uint32_t* perm, hipStream_t stream);
 
 // hc_api.cpp: the x-space image of a score threshold with a guard band of 2^log2_width relative width (-49: the scoring path's), and the
 // log-probability table of the scoring path in its 16-bit-symbol layout (hc_device.h: two triangles of (K + 2) rows) for the Phred values
