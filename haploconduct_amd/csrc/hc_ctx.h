@@ -300,6 +300,13 @@ struct hc_ctx {
         hc_scratch entries, status, cnt, bytes, key, rank, overlap_pos, n_clique, visited, rewrite;
         hc_scratch t_kind, t_id, t_v_state, t_nodes, t_srs, t_sr_pair, t_clique_cnt, t_clique_off, t_clique_nodes, t_sub_off, t_sub, t_tips, temp;
     } sr_mn;
+    // hc_sr_clique_next (hc_api_sr_clique_next.cpp): grow-only scratch — the call's inputs, the host's verdicts (bad, own); the blocks of
+    // hc_sr_clique_next.h: Work by name; the row and subread sizes before their sums; the sorts' and scans' workspace.  The slots, the
+    // rewrites and the tables are sr_mn's: the two calls never run at once on one context.
+    struct SrCliqueNext {
+        hc_scratch off, nodes, cstatus, first_layout, layouts, mvertex, lay_status, out_off, sub, v_read, v_fwd, bad, own;
+        hc_scratch key_in, key, m_item, m_owner, m_cnt, m_off, sr_of, sub_cnt, pre_cnt, pre_off, it_key_in, it_key, it_val_in, it_val, temp;
+    } sr_cn;
 };
 
 namespace hc {

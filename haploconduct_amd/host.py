@@ -532,6 +532,22 @@ def sr_merge_next(reads, cons_seq, cons_qual, pairs, edge, vertex_read, vertex_f
     return MN.host_merge_next(reads, cons_seq, cons_qual, pairs, edge, vertex_read, vertex_fwd, **kw)
 
 
+def sr_clique_next(reads, cons_seq, cons_qual, clique_off, clique_nodes, merged, vertex_read, vertex_fwd, **kw):
+    """hc_host_sr_clique_next: the host mirror of EdgeScorer.sr_clique_next (process_cliques and cliquesToSuperreads, src/SRBuilder.cpp:981-1001,
+    1122-1233) on a ReadSet and the consensus bytes of the clique merge.  kw: clique_next.host_clique_next's further arguments."""
+    from . import clique_next as CN
+
+    return CN.host_clique_next(reads, cons_seq, cons_qual, clique_off, clique_nodes, merged, vertex_read, vertex_fwd, **kw)
+
+
+def sr_clique_select(clique_off, clique_nodes, n_vertices, min_clique_size=2, remove_multi_occ=False):
+    """hc_host_sr_clique_select: the gate in front of process_cliques (src/SRBuilder.cpp:1056-1084: remove_multi_occ, the singleton count,
+    minCliqueSize) over a CSR of cliques in file order.  Returns a clique_next.CliqueSelection."""
+    from . import clique_next as CN
+
+    return CN.host_clique_select(clique_off, clique_nodes, n_vertices, min_clique_size, remove_multi_occ)
+
+
 def graph_write_text(graph: HostGraph, kind, **kw):
     """hc_host_graph_write_text on a HostGraph: the mirror of Scorer.graph_write_text; (bytes, counts)."""
     return graph.write_text(kind, **kw)

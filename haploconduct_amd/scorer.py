@@ -156,6 +156,20 @@ class EdgeScorer:
             self._reads = None  # (the new reads live on the device: sr_next_reads_fetch)
         return res
 
+    def sr_clique_next(self, clique_off, clique_nodes, merged, vertex_read, vertex_fwd, keep_singletons=0, self_overlap=True, min_score=0.99,
+                       min_qual=0.99, min_overlap=15, n_threads=16):
+        """hc_sr_clique_next: the rest of SRBuilder::cliquesToSuperreads (src/SRBuilder.cpp:981-1001, 1122-1233) from what sr_clique_merge
+        returned (merged: its consensus.SrCliqueLayouts) — the self-overlap test, the `visited` marks, the trivial super-reads, the
+        numbering, the next store and the vertex / super-read tables of find-next-overlaps.  Returns a clique_next.CliqueNext (empty = True:
+        nothing survived, the old store is in place)."""
+        from . import clique_next as CN
+
+        res = CN.clique_next(self._ctx, clique_off, clique_nodes, merged, vertex_read, vertex_fwd, keep_singletons, self_overlap, min_score, min_qual,
+                             min_overlap, n_threads)
+        if not res.empty:
+            self._reads = None  # (the new reads live on the device: sr_next_reads_fetch)
+        return res
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

@@ -205,8 +205,8 @@ int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_
  * filter_subreads / sortVerticesByEndpos (:597-651) where the clique is larger than 3 * min_clique_size (:721), consensus
  * (:413-535) and calcSubreadInfo (:536-595).
  * Left to the caller: reading cliques.txt, remove_multi_occ and the minCliqueSize gate (:1056-1084; remove_multi_occ is a serial
- * greedy pass over a text file), clique enumeration, the original-index maps (:750-843) and subreads.txt, and a clique form of
- * hc_sr_merge_next (marks, trivials, FNO tables from these outputs). */
+ * greedy pass over a text file: hc_host_sr_clique_select), clique enumeration, the original-index maps (:750-843) and subreads.txt.
+ * The marks, the trivials, the next store and the FNO tables from these outputs: hc_sr_clique_next. */
 
 /* Per-clique status: the HC_SR_EDGE_* values and two more.  Where several members of a clique fail, the status is that of the first
  * failing vertex in the loop's order (ascending vertex, :658, :87) and within a vertex the reference's order of checks; the asserts
@@ -524,8 +524,8 @@ int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in
  * arrival order (:1004-1011), which is not deterministic; one thread gives pair order.
  * Left to the caller: the original-index maps (:750-843, :1312-1369) and subreads.txt; the FASTQ text, including
- * removed_tip_sequences.fastq (the tips list names the vertices); this call for cliques of more than two vertices
- * (hc_sr_clique_merge lays them out and merges them; the marks, trivials and FNO tables from ITS outputs are not built). */
+ * removed_tip_sequences.fastq (the tips list names the vertices).  This call for cliques of more than two vertices is
+ * hc_sr_clique_next, below, on hc_sr_clique_merge's outputs. */
 
 typedef struct hc_sr_merge_next_input {
     /* what hc_sr_edge_merge returned, unchanged: host arrays */
@@ -641,6 +641,126 @@ int hc_host_sr_merge_next(const hc_settings* ec_settings, const uint8_t* bases, 
                           const hc_sr_merge_next_input* in, const hc_sr_merge_next_settings* st, hc_sr_merge_next_output* out,
                           uint8_t* out_bases, uint8_t* out_quals, uint64_t cap, uint64_t* n_bytes, uint64_t* out_seq_off,
                           uint32_t* out_read_first_seq);
+
+/* ---- the rest of cliquesToSuperreads in one call: marks, trivials, the next store and the FNO tables -----------------------
+ *
+ * Between hc_sr_clique_merge and find-next-overlaps SRBuilder::cliquesToSuperreads (src/SRBuilder.cpp:1031-1235) judges the super-reads
+ * (process_cliques, :981-1001, with merge_self_overlap, :872-955), marks the vertices of the survivors (:1122-1136), walks the unvisited
+ * vertices for the trivial super-reads (:1145-1222; length, then N rate: this function has no inclusion and no tip test) and numbers
+ * the three groups (:1141-1142, :1219-1220, :1233).  hc_sr_clique_next does that on the device from what hc_sr_clique_merge returned,
+ * as hc_sr_merge_next does for an edge merge: it leaves the next store in the context and returns the tables of an hc_fno1_input.
+ * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in arrival
+ * order (:1004-1011), which is not deterministic; one thread gives clique order.
+ * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select), the original-index
+ * maps (:750-843, :1161-1216) and subreads.txt, the FASTQ text. */
+
+typedef struct hc_sr_clique_next_input {
+    /* what hc_sr_clique_merge took and returned, unchanged: host arrays */
+    const uint64_t* clique_off;         /* n_cliques + 1; N = clique_off[n_cliques]                                                     */
+    const uint32_t* clique_nodes;       /* N vertices, in any order inside a clique: process_cliques' clique_vec, :980                  */
+    uint64_t n_cliques;
+    const uint32_t* clique_status;      /* HC_SR_EDGE_* / HC_SR_CLIQUE_*: anything but HC_SR_EDGE_OK owns no super-read                 */
+    const uint64_t* first_layout;       /* n_cliques + 1: one layout = single-end, two = paired (:850-869)                              */
+    const hc_sr_layout* layouts;        /* first_layout[n_cliques] of them                                                              */
+    const hc_sr_member* members;        /* not read: the rows come from member_vertex, the bytes from out_off.  May be NULL.            */
+    const uint32_t* member_vertex;      /* n_members: sorted_vertices1 / sorted_vertices2 — the FULL lists set_sorted_clique keeps      */
+    uint64_t n_members;                 /* at most 2 N, what hc_sr_clique_merge has room for (HC_ERR_ARG beyond)                        */
+    const uint32_t* status;             /* HC_SR_* per layout: a layout that is not HC_SR_OK is an empty mate (:983, :999)              */
+    const uint64_t* out_off;            /* n_layouts + 1: cons_seq1 / cons_seq2 (:852, :863) among the KEPT consensus bytes             */
+    const hc_sr_subread_info* subreads; /* N: per clique its vertices' entries in ASCENDING VERTEX order, as hc_sr_clique_merge writes  */
+    /* the graph's vertices */
+    const uint32_t* vertex_read;        /* OverlapGraph::vertex_to_read as store indices, :1147                                         */
+    const uint8_t* vertex_fwd;          /* OverlapGraph::getOrientation, :1180                                                          */
+    uint64_t n_vertices;                /* OverlapGraph::getVertexCount, :1054, :1145                                                   */
+} hc_sr_clique_next_input;
+
+typedef struct hc_sr_clique_next_settings {
+    uint32_t keep_singletons; /* program_settings.keep_singletons, :1149                                                    */
+    uint32_t no_self_overlap; /* 1: merge_self_overlap (:985) is left out, every paired super-read stays paired             */
+    hc_sr_self_settings self; /* merge_self_overlap's constants (:873-874: min_score 0.99, min_overlap 15) and minQual      */
+} hc_sr_clique_next_settings; /* 32 bytes */
+
+typedef struct hc_sr_clique_next_output {
+    /* per clique (n_cliques entries each) */
+    uint32_t* clique_kind;   /* HC_SR_MN_*                                                                                              */
+    int32_t* clique_new_id;  /* Read id of the clique's super-read in the next store (:1142, :1233) or -1                               */
+    int32_t* overlap_pos;    /* merge_self_overlap's overlap_pos (:882) of a clique it merged, else -1                                  */
+    double* self_score;      /* overlap_score's value there (:886), else 0                                                              */
+    /* per vertex (n_vertices entries each) */
+    uint32_t* vertex_state;  /* HC_SR_MN_V_MERGED, _TRIVIAL, _SHORT, _N_RATE or _BAD                                                    */
+    hc_fno_read* nodes;      /* as hc_sr_merge_next_output.nodes (id: nodes_to_new_IDs, :1219; visited: SRBuilder::visited after :1222) */
+    /* per surviving super-read, single_SR_vec then paired_SR_vec (:1023-1024); room for n_cliques (+ 1 for the offsets) */
+    hc_fno_read* srs;           /* id = the new id, len1 / len2 = the mates' lengths, paired                                            */
+    uint32_t* sr_clique;        /* the clique it came from                                                                              */
+    uint64_t* clique_off;       /* n_srs + 1 offsets into clique_nodes                                                                  */
+    uint64_t* clique_nodes;     /* room for 2 N: get_sorted_clique(0) of a single (:864), get_sorted_clique(1) of a paired super-read
+                                   (:853) — member_vertex of the clique's FIRST layout in member order —, new_sorted_clique of a
+                                   self-merged one (:913-935) in the order stated below                                                */
+    uint64_t* subread_off;      /* n_srs + 1 offsets into subreads                                                                      */
+    hc_fno_subread* subreads;   /* room for N: the subreadMap (:857, :866), one entry per clique vertex in ascending vertex order;
+                                   after a self-merge index2 += overlap_pos where index2 >= 0 (:918-922)                               */
+    /* filled by the call */
+    uint64_t n_srs, n_singles, n_trivials, n_paired, n_self_merged;
+    uint64_t new_read_count;    /* SRBuilder::new_read_count, :1234                                                                     */
+    hc_sr_next_counts counts;   /* of the store: n_kept = new_read_count; the dropped counts over cliques and vertices together        */
+    hc_sr_self_stats self_stats;
+    double ms_device;           /* device call only: this section's own kernels, sorts and scans, by events on the context's stream    */
+    double ms_copy;             /* device call only: waiting for the copies of the inputs and of the tables                             */
+} hc_sr_clique_next_output;
+
+/* Needs hc_sr_keep_device on, a store whose raw arrays were kept and kept consensus bytes (HC_ERR_STATE otherwise).  HC_ERR_ARG:
+ * n_cliques + n_vertices >= 2^31 or N >= 2^31; clique_off that does not start at 0 or descends; first_layout[n_cliques] > 2 n_cliques;
+ * n_members > 2 N; the first layouts of the cliques that own a super-read (below) do not name ascending, disjoint member ranges in
+ * clique order (hc_sr_clique_merge packs them so; the owner of a member is found by bisection).  Any error leaves the old store usable.
+ * 1. The super-read of clique i (:981-1001).  clique_status != HC_SR_EDGE_OK: none.  One layout: single-end, its bytes at out_off of
+ *    that layout; two: paired.  A layout that is not HC_SR_OK, or an empty mate, drops it.  A paired super-read with two non-empty mates
+ *    goes through merge_self_overlap — hc_sr_merge_self_overlaps_kept's own run — and a merged one becomes the single-end read the kept
+ *    form appended (the kept bytes grow as there).  Then test_N_rate.  The kinds are HC_SR_MN_*.
+ *    Refused as HC_SR_MN_NONE, nothing read: a clique vertex or a vertex of the first layout's members >= n_vertices, fewer than two
+ *    vertices, another number of layouts than 1 or 2, a layout or a member range outside the arrays, descending first_layout or out_off.
+ * 2. visited[x] = 1 for every x of member_vertex of the FIRST layout of every super-read that survived 1, and only those (:1122-1136):
+ *    the full list, whatever member_used says (set_sorted_clique keeps sorted_vertices1, :853, :864).  Cliques may overlap.
+ * 3. Every unvisited vertex in vertex order (:1145-1222): HC_SR_MN_V_SHORT, then HC_SR_MN_V_N_RATE, else a trivial with
+ *    rev = !vertex_fwd[v] (:1180-1217).
+ * 4. Ids: the single-end super-reads in clique order from 0 (a self-merged clique at its clique's place), then the trivials in vertex
+ *    order, then the paired super-reads in clique order: hc_sr_set_next_reads' own numbering for that entry list, and the store is
+ *    replaced exactly as it replaces it (the same code from the gather on).  When nothing survives: HC_SR_NEXT_EMPTY, the outputs
+ *    filled, the old store kept.
+ * 5. After a self-merge (:911-935) every index2 >= 0 becomes index2 + overlap_pos, and the row lists, for each member of the first
+ *    layout, (vertex, index1) and, where the vertex's index2 >= 0, (vertex, new index2), ordered by index.  The order among EQUAL
+ *    indexes is this call's own: the entries are laid out by DESCENDING position of the vertex in the first layout's member list, a
+ *    vertex's index1 entry before its index2 entry, and then sorted by index with a stable sort.  For a clique of two this is
+ *    hc_sr_merge_next's documented order, which is the reference's; for more vertices the reference's order is the unordered_map's
+ *    iteration followed by an unstable std::sort, and find-next-overlaps does not read it (FindNextOverlaps.cpp:900-913 pushes one
+ *    pointer per listed vertex: membership with multiplicity is all that counts).
+ * A clique list of two-vertex cliques gives exactly what hc_sr_merge_next gives for the same pairs with ignore_inclusions =
+ * store_tips_separately = 0: every shared output and the store.
+ * The tables can be handed to hc_fno1_input as they are.  The work is a fixed number of launches whatever the sizes: a lane per clique
+ * vertex, clique, member, super-read or index entry, the owners by bisection, one stable radix sort of clique << 32 | vertex (so the
+ * caller's cliques need not be sorted) and one of super-read << 32 | (index + 2^31) over all self-merged cliques' entries. */
+int hc_sr_clique_next(hc_ctx* ctx, const hc_sr_clique_next_input* in, const hc_sr_clique_next_settings* st, hc_sr_clique_next_output* out);
+
+/* The same contract on the host (no device, no context): the current store as hc_set_reads takes it, the kept consensus bytes (n_cons
+ * each), in, st, out — and the four arrays of the next store as hc_host_sr_next_reads returns them (out_seq_off: room for
+ * 2 (n_cliques + n_vertices) + 1, out_read_first_seq: n_cliques + n_vertices + 1; cap / *n_bytes: count, then fetch).  It walks the
+ * reference's loops as written, over hc_host_sr_merge_self_overlaps and hc_host_sr_next_reads. */
+int hc_host_sr_clique_next(const hc_settings* ec_settings, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,
+                           const uint32_t* read_first_seq, uint32_t n_reads, const uint8_t* cons_seq, const uint8_t* cons_qual, uint64_t n_cons,
+                           const hc_sr_clique_next_input* in, const hc_sr_clique_next_settings* st, hc_sr_clique_next_output* out,
+                           uint8_t* out_bases, uint8_t* out_quals, uint64_t cap, uint64_t* n_bytes, uint64_t* out_seq_off,
+                           uint32_t* out_read_first_seq);
+
+/* The gate in front of process_cliques (src/SRBuilder.cpp:1056-1084) over the cliques of cliques.txt in file order, as a CSR: with
+ * remove_multi_occ a clique first loses the vertices that an earlier ACCEPTED clique used (:1065-1073); what is left counts as a
+ * singleton when it has one vertex (:1075-1077) and is accepted when it has at least min_clique_size (:1078-1084; used_nodes is set on
+ * acceptance only, and whatever remove_multi_occ says).  A clique left with no vertex is neither (with min_clique_size == 0 it is
+ * accepted, as the reference accepts it).  Serial by definition — every clique sees the ones accepted before it — and host only.
+ * Outputs: sel_off (room for n_cliques + 1) / sel_nodes (room for clique_off[n_cliques]): the accepted cliques, filtered, in file
+ * order; sel_index (room for n_cliques): the index of each in the input; *n_selected; *n_singletons.
+ * HC_ERR_ARG: a null array, clique_off that does not start at 0 or descends, a vertex >= n_vertices (the reference's bitset asserts). */
+int hc_host_sr_clique_select(const uint64_t* clique_off, const uint32_t* clique_nodes, uint64_t n_cliques, uint64_t n_vertices,
+                             uint32_t min_clique_size, int remove_multi_occ, uint64_t* sel_off, uint32_t* sel_nodes, uint64_t* sel_index,
+                             uint64_t* n_selected, uint64_t* n_singletons);
 
 #ifdef __cplusplus
 }
