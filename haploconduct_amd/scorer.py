@@ -28,6 +28,12 @@ class EdgeScorer:
             N.lib.hc_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
+    def reset(self, settings):
+        """hc_reset: the context takes new settings and is as after its creation (no reads: call set_reads again); its device memory stays."""
+        cs = settings.to_c()
+        N.check(N.lib.hc_reset(self._ctx, C.byref(cs)), "hc_reset")
+        self.settings, self._cs, self._reads = settings, cs, None
+
     def __del__(self):
         try:
             self.close()

@@ -8,6 +8,7 @@ import pytest
 import haploconduct_amd as hc
 from haploconduct_amd import synth
 from haploconduct_amd.records import OVERLAP_DTYPE, result_cls, result_n
+from tests import _band
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +35,8 @@ def check_parity(oracle, reads, settings, cand, expect_classes=None):
     assert np.array_equal(cls, ref["cls"]), "admission class differs (host-finalised)"
     dev = result_cls(res)
     assert ((dev == ref["cls"]) | (dev == 4)).all(), "device-side admission class differs"
+    # tightness: the device's class is the three-valued rule's — AMBIG where, and only where, an x lies in a band that still matters
+    assert np.array_equal(dev, _band.model_class(ref["x1"], ref["x2"], ref["mm"], ref["n"], settings)), "device class is not the band rule's"
     assert (dev == 4).mean() < 1e-3, "guard band should be (nearly) empty"
     assert np.array_equal(bits(score), bits(ref["score"])), "score not bit-exact"
     assert np.array_equal(bits(mrate), bits(ref["mismatch_rate"])), "mismatch_rate not bit-exact"
