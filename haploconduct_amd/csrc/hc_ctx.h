@@ -307,6 +307,21 @@ struct hc_ctx {
         hc_scratch off, nodes, cstatus, first_layout, layouts, mvertex, lay_status, out_off, sub, v_read, v_fwd, bad, own;
         hc_scratch key_in, key, m_item, m_owner, m_cnt, m_off, sr_of, sub_cnt, pre_cnt, pre_off, it_key_in, it_key, it_val_in, it_val, temp;
     } sr_cn;
+    // hc_sr_originals_* (hc_api_sr_originals.cpp): the kept dict (off: n_reads + 1 offsets, entries: n_entries hc_sr_original), which
+    // hc_sr_originals_next trades against next_off / next_entries; the call's inputs (in_*); the blocks of hc_sr_originals.h: Work by name;
+    // the text (sizes: the items' characters and their sum, text: n_text bytes of it, kept until the dict is replaced)
+    struct SrOriginals {
+        hc_scratch off, entries, next_off, next_entries;
+        uint64_t n_reads = 0, n_entries = 0;
+        bool valid = false;
+        hc_scratch in_kind, in_new_id, in_overlap_pos, in_first_layout, in_layouts, in_sr_clique, in_subread_off, in_subreads, in_vertex_state, in_nodes,
+            in_vertex_read, in_vertex_fwd;
+        hc_scratch cnt, cnt_off, key_in, key, val_in, val, cand, bits, flag, sel, n_sel, out_id, out_status, temp;
+        hc_scratch sizes, text;
+        uint64_t n_text = 0;
+        bool text_valid = false;
+        void replaced() { text_valid = false, n_text = 0; }
+    } sr_orig;
 };
 
 namespace hc {

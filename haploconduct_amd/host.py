@@ -551,3 +551,27 @@ def sr_clique_select(clique_off, clique_nodes, n_vertices, min_clique_size=2, re
 def graph_write_text(graph: HostGraph, kind, **kw):
     """hc_host_graph_write_text on a HostGraph: the mirror of Scorer.graph_write_text; (bytes, counts)."""
     return graph.write_text(kind, **kw)
+
+
+def sr_originals_next(off, entries, res, merged=None, vertex_read=None, vertex_fwd=None, first_it=False, n_threads=1, cap=None):
+    """hc_host_sr_originals_next: the host mirror of EdgeScorer.sr_originals_next (src/SRBuilder.cpp:750-806, :938-949, :1161-1216, :1312-1369)
+    on the dict (off, entries) of the store the merge call found.  res: what sr_merge_next / sr_clique_next returned, or an originals.Tables."""
+    from . import originals as OR
+
+    t = res if isinstance(res, OR.Tables) else OR.tables_from(res, merged, vertex_read, vertex_fwd, first_it)
+    return OR.host_next(off, entries, t, n_threads, cap)
+
+
+def sr_originals_text(off, entries):
+    """hc_host_sr_originals_text: the bytes of subreads.txt for a dict (the writers' loop, src/SRBuilder.cpp:1449-1463)."""
+    from . import originals as OR
+
+    return OR.host_text(off, entries)
+
+
+def sr_originals_parse(data):
+    """hc_host_sr_originals_parse: the bytes of a subreads.txt -> (off, entries), OverlapGraph::buildOriginalsDict's else branch
+    (src/OverlapGraph.cpp:807-838)."""
+    from . import originals as OR
+
+    return OR.host_parse(data)

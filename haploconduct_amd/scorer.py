@@ -176,6 +176,43 @@ class EdgeScorer:
             self._reads = None  # (the new reads live on the device: sr_next_reads_fetch)
         return res
 
+    def sr_originals_init(self):
+        """hc_sr_originals_init: the first iteration's dict of the current store (OverlapGraph::buildOriginalsDict with first_it,
+        src/OverlapGraph.cpp:772-797), kept on the device."""
+        from . import originals as OR
+
+        OR.init(self._ctx)
+
+    def sr_originals_load(self, off, entries):
+        """hc_sr_originals_load: the caller's dict (a CSR over the current store's reads, originals.ORIGINAL_DTYPE entries in ascending id
+        inside a read) becomes the kept one."""
+        from . import originals as OR
+
+        OR.load(self._ctx, off, entries)
+
+    def sr_originals_fetch(self):
+        """hc_sr_originals_fetch: (off, entries) of the kept dict."""
+        from . import originals as OR
+
+        return OR.fetch(self._ctx)
+
+    def sr_originals_next(self, res, merged, vertex_read, vertex_fwd, first_it=False):
+        """hc_sr_originals_next: the dict of the next store from the kept one and what sr_merge_next / sr_clique_next returned (res) for
+        the layouts of sr_edge_merge / sr_clique_merge (merged) — constructSuperread's loop over the originals (src/SRBuilder.cpp:750-806),
+        merge_self_overlap's shift (:938-949) and the trivials (:1161-1216, :1312-1369).  res may be an originals.Tables instead (merged is
+        then not read).  Returns an originals.OriginalsNext; the new dict replaces the kept one."""
+        from . import originals as OR
+
+        t = res if isinstance(res, OR.Tables) else OR.tables_from(res, merged, vertex_read, vertex_fwd, first_it)
+        return OR.next_dict(self._ctx, t)
+
+    def sr_originals_text(self):
+        """hc_sr_originals_write_text + hc_sr_originals_text_fetch: the bytes of subreads.txt for the kept dict (src/SRBuilder.cpp:1449-1463),
+        line k = read k, entries in ascending original id."""
+        from . import originals as OR
+
+        return OR.text(self._ctx)[0]
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

@@ -117,7 +117,8 @@ int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const ui
  * do that on the graph the context holds (hc_graph_resolve / hc_graph_load and the cleaning calls), for every combination of
  * single-end and paired reads.
  * Cliques of more than two vertices and filter_subreads (:597-651): hc_sr_clique_merge, the next section.  Left to the caller: clique
- * enumeration, the original-index maps (:750-843) and subreads.txt.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next.) */
+ * enumeration.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next; the original-index maps (:750-806) and
+ * subreads.txt: hc_sr_originals_next, on the subread infos this call returns.) */
 
 typedef struct hc_merge_pairs_stats {
     double ms_kernel; /* device call only: the target-column kernel, by events on the context's stream */
@@ -205,7 +206,8 @@ int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_
  * filter_subreads / sortVerticesByEndpos (:597-651) where the clique is larger than 3 * min_clique_size (:721), consensus
  * (:413-535) and calcSubreadInfo (:536-595).
  * Left to the caller: reading cliques.txt, remove_multi_occ and the minCliqueSize gate (:1056-1084; remove_multi_occ is a serial
- * greedy pass over a text file: hc_host_sr_clique_select), clique enumeration, the original-index maps (:750-843) and subreads.txt.
+ * greedy pass over a text file: hc_host_sr_clique_select), clique enumeration.  (The original-index maps (:750-806) and
+ * subreads.txt: hc_sr_originals_next, on the subread infos this call returns.)
  * The marks, the trivials, the next store and the FNO tables from these outputs: hc_sr_clique_next. */
 
 /* Per-clique status: the HC_SR_EDGE_* values and two more.  Where several members of a clique fail, the status is that of the first
@@ -411,8 +413,8 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
  * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
  * context's read store by the result.
- * Left to the caller: the original-index maps and subreads.txt (the subread infos: hc_sr_edge_merge, hc_sr_clique_merge); the FASTQ
- * text itself.  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
+ * Left to the caller: the FASTQ text itself.  (The original-index maps and subreads.txt: hc_sr_originals_next / hc_sr_originals_write_text,
+ * from the subread infos of hc_sr_edge_merge / hc_sr_clique_merge.)  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
  * clique that merge_self_overlap merged (:911-949) itself; hc_sr_merge_next below builds the list, the marks, the tips and the
  * shifted cliques from an edge merge's outputs.  (The self-overlap test between the consensus call and this one runs on the kept
  * bytes: hc_sr_merge_self_overlaps_kept.) */
@@ -523,8 +525,8 @@ int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint
  * hc_fno1_input (hcfno.h) ready to use.
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in
  * arrival order (:1004-1011), which is not deterministic; one thread gives pair order.
- * Left to the caller: the original-index maps (:750-843, :1312-1369) and subreads.txt; the FASTQ text, including
- * removed_tip_sequences.fastq (the tips list names the vertices).  This call for cliques of more than two vertices is
+ * Left to the caller: the FASTQ text, including removed_tip_sequences.fastq (the tips list names the vertices).  The original-index maps
+ * (:750-806, :1312-1369) and subreads.txt: hc_sr_originals_next, below, on this call's outputs.  This call for cliques of more than two vertices is
  * hc_sr_clique_next, below, on hc_sr_clique_merge's outputs. */
 
 typedef struct hc_sr_merge_next_input {
@@ -651,8 +653,8 @@ int hc_host_sr_merge_next(const hc_settings* ec_settings, const uint8_t* bases, 
  * as hc_sr_merge_next does for an edge merge: it leaves the next store in the context and returns the tables of an hc_fno1_input.
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in arrival
  * order (:1004-1011), which is not deterministic; one thread gives clique order.
- * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select), the original-index
- * maps (:750-843, :1161-1216) and subreads.txt, the FASTQ text. */
+ * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select), the FASTQ text.  The
+ * original-index maps (:750-806, :1161-1216) and subreads.txt: hc_sr_originals_next, below, on this call's outputs. */
 
 typedef struct hc_sr_clique_next_input {
     /* what hc_sr_clique_merge took and returned, unchanged: host arrays */
@@ -761,6 +763,150 @@ int hc_host_sr_clique_next(const hc_settings* ec_settings, const uint8_t* bases,
 int hc_host_sr_clique_select(const uint64_t* clique_off, const uint32_t* clique_nodes, uint64_t n_cliques, uint64_t n_vertices,
                              uint32_t min_clique_size, int remove_multi_occ, uint64_t* sel_off, uint32_t* sel_nodes, uint64_t* sel_index,
                              uint64_t* n_selected, uint64_t* n_singletons);
+
+/* ---- the original-read index maps on the device, and subreads.txt ----------------------------------------------------------
+ *
+ * OverlapGraph::original_ID_dict (src/OverlapGraph.cpp:768-846) is the one table the reference carries from an iteration to the next
+ * through a file: per read of the store, the reads of the FIRST iteration it is made of, each with its place in it.  constructSuperread
+ * folds the maps of a clique's reads into the super-read's (src/SRBuilder.cpp:750-806), merge_self_overlap shifts them (:938-949), a
+ * trivial super-read copies or reverses its read's (:1161-1216, :1312-1369), and the three writers append one line per new read to
+ * subreads.txt (:1449-1463, :1489-1503, :1537-1551).  Here the dict stays in the context: a CSR over the reads of a store,
+ * orig_off[n_reads + 1] + entries.
+ * Two things are this project's own.  (1) The reference's order inside a map, and inside a line, is libstdc++'s unordered_map
+ * iteration order; every reader puts the entries back into a map.  Here the entries of a read are in ASCENDING ORIGINAL ID, in the
+ * arrays and in the text.  (2) index2 / len2 of a single-end original are never set nor printed by the reference: here they are 0 on
+ * output and ignored on input.
+ * Left to the caller: the FASTQ text; FNO=3 and BranchReduction, which read the dict. */
+
+typedef struct hc_sr_original {
+    uint32_t id;            /* the original read's id                                                                   */
+    int32_t index1, index2; /* OriginalIndex::index1 / index2 (long there; a result outside int32 is HC_SR_ORIG_RANGE)  */
+    uint32_t len1, len2;    /* OriginalIndex::len1 / len2                                                               */
+    uint8_t paired;         /* OriginalIndex::is_paired                                                                 */
+    uint8_t forward;        /* OriginalIndex::forward                                                                   */
+    uint8_t pad[2];         /* 0                                                                                        */
+} hc_sr_original; /* 24 bytes */
+
+/* Per read of the new dict.  A read that is not OK has no entries. */
+enum {
+    HC_SR_ORIG_OK = 0,
+    HC_SR_ORIG_EMPTY_SOURCE = 1,   /* a trivial super-read whose read has an empty map: assert (subreads.size() > 0), :1178, :1329 */
+    HC_SR_ORIG_SEQ0_OF_PAIRED = 2, /* :801 calls get_seq(0) on a paired sub-read (a single-end original under a reverse vertex of a
+                                      paired read, not first_it): the assert of src/Read.h:145-149                                */
+    HC_SR_ORIG_RANGE = 3           /* an index left int32 (with HC_SR_ORIG_SEQ0_OF_PAIRED in the same read, that one is reported) */
+};
+/* hc_sr_originals_next: HC_OK is 0; reads with a status other than OK are no error of the arguments. */
+#define HC_SR_ORIG_SOME_FAILED 1
+
+/* What hc_sr_merge_next or hc_sr_clique_next returned and took, for both: an edge merge is the clique list with two vertices per pair
+ * (kind = pair_kind, new_id = pair_new_id, sr_clique = sr_pair). */
+typedef struct hc_sr_originals_input {
+    /* per source clique / pair (n_cliques entries; first_layout: n_cliques + 1) */
+    const uint32_t* kind;         /* HC_SR_MN_*: HC_SR_MN_SINGLE_SELF means merge_self_overlap merged it, :938-949                  */
+    const int32_t* new_id;        /* the super-read's id in the next store                                                         */
+    const int32_t* overlap_pos;   /* read for HC_SR_MN_SINGLE_SELF only                                                            */
+    const uint64_t* first_layout; /* two layouts: the second one's total_len is constructSuperread's len2 (:693, :788), else 0     */
+    uint64_t n_cliques;
+    const hc_sr_layout* layouts;
+    /* per surviving super-read */
+    const uint32_t* sr_clique;       /* the clique it came from                                                                    */
+    const uint64_t* subread_off;     /* n_srs + 1                                                                                  */
+    const hc_fno_subread* subreads;  /* per super-read its vertices in ASCENDING VERTEX order, the loop order of :752; index2 as the
+                                        merge call returned it (shifted after a self-merge: the call undoes that)                  */
+    uint64_t n_srs;
+    /* per vertex */
+    const uint32_t* vertex_state; /* HC_SR_MN_V_*: HC_SR_MN_V_TRIVIAL owns the new read nodes[v].id                                */
+    const hc_fno_read* nodes;     /* id of a trivial; len1 / len2 / paired of vertex_read[v] in the store the merge call found     */
+    const uint32_t* vertex_read;  /* indexes the kept dict                                                                         */
+    const uint8_t* vertex_fwd;
+    uint64_t n_vertices;
+    uint64_t new_read_count;      /* reads of the new dict                                                                         */
+    uint32_t first_it;            /* program_settings.first_it, :767                                                               */
+    uint32_t reserved;
+} hc_sr_originals_input;
+
+typedef struct hc_sr_originals_output {
+    uint64_t* orig_off; /* room for new_read_count + 1: the new dict's offsets                    */
+    uint32_t* status;   /* room for new_read_count: HC_SR_ORIG_*                                  */
+    uint64_t n_entries; /* entries of the new dict                                                */
+    uint64_t n_failed;  /* reads whose status is not HC_SR_ORIG_OK                                */
+    double ms_device;   /* device call only: kernels, sort and scans, by events on the stream     */
+    double ms_copy;     /* device call only: waiting for the copies of the inputs and the results */
+} hc_sr_originals_output;
+
+typedef struct hc_sr_originals_text_counts {
+    uint64_t n_bytes, n_lines;
+    double ms_device;
+} hc_sr_originals_text_counts;
+
+/* buildOriginalsDict with first_it (src/OverlapGraph.cpp:772-797) for the context's current store: read r gets the one entry
+ * (r, index1 = 0, forward, len1) and, paired, (index2 = 0, len2, paired).  One lane per read, the lengths from the store's
+ * descriptors.  HC_ERR_STATE: no store. */
+int hc_sr_originals_init(hc_ctx* ctx);
+
+/* Makes the caller's dict the kept one.  HC_ERR_STATE: no store; HC_ERR_ARG: n_reads is not the current store's number of reads,
+ * orig_off does not start at 0 or descends, 2^31 entries or more, ids that do not strictly ascend inside a read, paired or forward
+ * above 1.  A read with no entry is allowed (hc_sr_originals_next reports it where the reference asserts).  index2 / len2 of a
+ * single-end entry are stored as 0.  Any error leaves the kept dict as it was. */
+int hc_sr_originals_load(hc_ctx* ctx, const uint64_t* orig_off, const hc_sr_original* entries, uint64_t n_reads);
+
+/* The kept dict.  *n_reads / *n_entries are always filled (0 and HC_ERR_STATE when none is kept).  cap_reads = entries orig_off has
+ * room for beyond its first, cap_entries = room of entries; where either is too small or a buffer is NULL nothing is copied and
+ * HC_ERR_ARG is returned (count, then fetch). */
+int hc_sr_originals_fetch(hc_ctx* ctx, uint64_t* orig_off, uint64_t cap_reads, hc_sr_original* entries, uint64_t cap_entries,
+                          uint64_t* n_reads, uint64_t* n_entries);
+
+/* The dict of the NEXT store from the kept dict of the store the merge call found, which it then replaces.  It may run after the merge
+ * call has replaced the store: what it needs of the old reads is in `nodes`.
+ * New read new_id[c] of a surviving super-read k (c = sr_clique[k]; :750-806): its vertices in the order of `subreads`; for vertex v
+ * every entry e of the dict of vertex_read[v] whose id no earlier vertex supplied, with
+ *     fwd = vertex_fwd[v], i2 = the row's index2 before the self-merge shift, idx1 = index1 - startpos1, idx2 = i2 - startpos2,
+ *     e.forward = (e.forward == fwd), and
+ *     first_it:  e.index1 = idx1; paired e: e.index2 = idx2                                                            (:767-772)
+ *     fwd:       e.index1 += idx1; paired e: e.index2 += i2 >= 0 ? idx2 : idx1                                         (:773-783)
+ *     else, paired e, paired read:  e.index1 = len1(v) + idx1 - (e.len1 + e.index1),
+ *                                   e.index2 = len2(v) + (len2 > 0 || i2 >= 0 ? idx2 : idx1) - (e.len2 + e.index2)     (:786-794)
+ *           paired e, single read:  e.index1 = len1(v) + idx1 - (e.len1 + e.index1), e.index2 = len1(v) + idx1 - (e.len2 + e.index2)
+ *           single e, single read:  e.index1 = len1(v) + idx1 - (e.len1 + e.index1)                                    (:801)
+ *           single e, paired read:  HC_SR_ORIG_SEQ0_OF_PAIRED
+ *     HC_SR_MN_SINGLE_SELF: paired e: e.index2 += overlap_pos                                                          (:938-949)
+ * New read nodes[v].id of a trivial v (:1161-1216, :1312-1369): the dict of vertex_read[v] as it is for a forward vertex; for a reverse
+ * one forward is flipped, index1 = L1 - (index1 + len1) and, for a paired read, index2 = L2 - (index2 + len2), for a paired e in a
+ * single-end read index2 = L1 - (index2 + len2) (L1 / L2 = nodes[v].len1 / len2); an empty dict is HC_SR_ORIG_EMPTY_SOURCE.
+ * A status is decided by the entries that WIN (an entry the reference skips at :762 asserts nothing).
+ * HC_ERR_STATE: no kept dict.  HC_ERR_ARG: a null array, a subread row's node >= n_vertices, vertex_read[v] of such a vertex or of a
+ * trivial not below the kept dict's reads, sr_clique >= n_cliques, a new id not below new_read_count, descending subread_off,
+ * new_read_count or the candidate entries 2^31 or more.  Any error leaves the kept dict in place; HC_SR_ORIG_SOME_FAILED replaces it.
+ * A fixed number of launches whatever the sizes: a lane per source (a super-read's vertex, or a vertex) for its dict's length, one
+ * exclusive sum, a lane per candidate entry (its source by bisection) for the transform and the key new id << 32 | original id, one
+ * stable radix sort — among equal keys the smallest vertex stays first, the reference's winner —, the first of every run, one ordered
+ * selection, a gather, and the offsets by bisection. */
+int hc_sr_originals_next(hc_ctx* ctx, const hc_sr_originals_input* in, hc_sr_originals_output* out);
+
+/* The bytes of subreads.txt for the kept dict, on the device until the next hc_sr_originals_write_text or the next call that replaces
+ * the dict: line k is read k — "k", then per entry "\tID:+:index1:len1" or "\tID:-:index1,index2:len1,len2", then "\n" (:1449-1463) —
+ * entries in ascending original id.  hc_sr_originals_text_fetch copies bytes [first, first + count) out (a range outside the text:
+ * HC_ERR_ARG; no text: HC_ERR_STATE). */
+int hc_sr_originals_write_text(hc_ctx* ctx, hc_sr_originals_text_counts* counts);
+int hc_sr_originals_text_fetch(hc_ctx* ctx, uint64_t first, uint64_t count, char* dst);
+
+/* The same contracts on the host (no device, no context): the loops of the cited lines as written, then every map sorted by id.
+ * hc_host_sr_originals_next: the old dict (n_reads reads) in, the new one out — out_entries: room for cap entries; *out->n_entries is
+ * always filled, too small a cap or NULL: HC_ERR_ARG with the offsets and statuses filled (count, then fetch).  n_threads: super-reads
+ * and trivials are independent (0 or 1: one thread). */
+int hc_host_sr_originals_next(const uint64_t* orig_off, const hc_sr_original* entries, uint64_t n_reads, const hc_sr_originals_input* in,
+                              hc_sr_originals_output* out, hc_sr_original* out_entries, uint64_t cap, uint32_t n_threads);
+/* text: room for cap bytes; *n_bytes always filled (count, then fetch). */
+int hc_host_sr_originals_text(const uint64_t* orig_off, const hc_sr_original* entries, uint64_t n_reads, char* text, uint64_t cap,
+                              uint64_t* n_bytes);
+/* buildOriginalsDict's else branch (src/OverlapGraph.cpp:807-838) on the bytes of a subreads.txt: a line is split at tabs, its first
+ * field is the read's id, every further field is split at ':' and ',' with adjacent separators taken as one, 4 tokens = single-end,
+ * 6 = paired; original_ID_dict.insert keeps the FIRST line of an id and a map the first entry of an original id.  The dict has
+ * max id + 1 reads.  *n_reads / *n_entries always filled; cap_reads / cap_entries as hc_sr_originals_fetch.  HC_ERR_FORMAT, with
+ * *bad_line = the 0-based line: a field of another token count than 4 or 6 (the assert of :816), or a token std::stol / stoi or
+ * str_to_read_id would not take whole, or a value outside its type here. */
+int hc_host_sr_originals_parse(const char* text, uint64_t n_bytes, uint64_t* orig_off, uint64_t cap_reads, hc_sr_original* entries,
+                               uint64_t cap_entries, uint64_t* n_reads, uint64_t* n_entries, uint64_t* bad_line);
 
 #ifdef __cplusplus
 }
