@@ -159,6 +159,8 @@ static void free_store(hc_ctx* c) {
     c->have_reads = false;
     c->store_bytes = 0;
     c->loc_reads = 0;
+    c->srn.prev_clear();  // (hc_sr_fastq_write_text: the raw arrays go or are replaced with the store)
+    c->sr_fastq.drop();
 }
 
 int hc_destroy(hc_ctx* c) {

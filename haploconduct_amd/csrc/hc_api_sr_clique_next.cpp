@@ -58,7 +58,10 @@ extern "C" int hc_sr_clique_next(hc_ctx* c, const hc_sr_clique_next_input* in, c
     memset(&out->counts, 0, sizeof out->counts);
     memset(&out->self_stats, 0, sizeof out->self_stats);
     out->clique_off[0] = out->subread_off[0] = 0;
-    if (n_slots == 0) return HC_SR_NEXT_EMPTY;
+    if (n_slots == 0) {
+        N.prev_traded = false;  // (hc_sr_fastq_write_text: the store this call read is the one in place)
+        return HC_SR_NEXT_EMPTY;
+    }
     // the host's pass: the vertex range tests and the owners of the first layouts' members
     const hc::cn::In H{in->clique_off, in->clique_nodes, in->clique_status, in->first_layout, in->layouts, in->member_vertex, in->status, in->out_off,
                        in->subreads, nc, n_items, n_layouts, n_members, nv};
@@ -291,7 +294,10 @@ extern "C" int hc_sr_clique_next(hc_ctx* c, const hc_sr_clique_next_input* in, c
     out->ms_device = ms_device;
     out->ms_copy = ms_copy;
     if ((uint32_t)sums[0] != n_kept) return fail(HC_ERR_STATE, "the ranks and the gather's count of survivors disagree");
-    if (n_kept == 0) return HC_SR_NEXT_EMPTY;  // the old store stays
+    if (n_kept == 0) {  // the old store stays
+        N.prev_traded = false;
+        return HC_SR_NEXT_EMPTY;
+    }
     // the store, by hc_sr_set_next_reads' own tail
     if ((rc = hc::sr_next_store(c, n_kept, 0, (uint32_t)n_kept, (uint32_t)cn.n_seq, cn.n_bytes, cn))) return rc;
     out->counts = cn;  // (counts.ms_device: the gather and the histograms; ms_device: this section's own kernels)

@@ -44,7 +44,10 @@ extern "C" int hc_sr_merge_next(hc_ctx* c, const hc_sr_merge_next_input* in, con
     memset(&out->counts, 0, sizeof out->counts);
     memset(&out->self_stats, 0, sizeof out->self_stats);
     out->clique_off[0] = out->subread_off[0] = 0;
-    if (n_slots == 0) return HC_SR_NEXT_EMPTY;
+    if (n_slots == 0) {
+        N.prev_traded = false;  // (hc_sr_fastq_write_text: the store this call read is the one in place)
+        return HC_SR_NEXT_EMPTY;
+    }
     HC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     hc_ctx::SrMergeNext& W = c->sr_mn;
@@ -228,7 +231,10 @@ extern "C" int hc_sr_merge_next(hc_ctx* c, const hc_sr_merge_next_input* in, con
     out->ms_device = ms_device;
     out->ms_copy = ms_copy;
     if ((uint32_t)sums[0] != n_kept) return fail(HC_ERR_STATE, "the ranks and the gather's count of survivors disagree");
-    if (n_kept == 0) return HC_SR_NEXT_EMPTY;  // the old store stays
+    if (n_kept == 0) {  // the old store stays
+        N.prev_traded = false;
+        return HC_SR_NEXT_EMPTY;
+    }
     // 5. the store, by hc_sr_set_next_reads' own tail
     if ((rc = hc::sr_next_store(c, n_kept, 0, (uint32_t)n_kept, (uint32_t)cn.n_seq, cn.n_bytes, cn))) return rc;
     out->counts = cn;  // (counts.ms_device: the gather and the histograms; ms_device: this section's own kernels)

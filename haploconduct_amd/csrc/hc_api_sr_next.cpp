@@ -29,6 +29,8 @@ extern "C" int hc_sr_keep_device(hc_ctx* c, int on) {
             b->release();
         N.raw_valid = false;
         N.total = 0;
+        N.prev_clear();
+        c->sr_fastq.drop();
         N.h_off.clear();
         N.h_first.clear();
         c->sr.kept_valid = false;
@@ -49,6 +51,10 @@ int hc::sr_next_store(hc_ctx* c, uint64_t n, uint64_t n_extra, uint32_t n_kept, 
     int rc;
     float ms_b = 0;
     if ((rc = N.hist.ensure(512 * sizeof(unsigned long long)))) return rc;
+    N.prev_clear();  // the next_* blocks are about to be overwritten: whatever store they held is gone, and a FASTQ text made from it
+    c->sr_fastq.drop();
+    const uint32_t n_seq_old = (uint32_t)(N.h_off.size() - 1);
+    const uint64_t total_old = N.total;
     // the survivors' bytes, the new offsets and the byte histograms
     if ((rc = N.next_bases.ensure_exact(total)) || (rc = N.next_quals.ensure_exact(total)) ||
         (rc = N.next_off.ensure_exact(sizeof(uint64_t) * ((size_t)n_seq + 1))) || (rc = N.next_first.ensure_exact(sizeof(uint32_t) * ((size_t)n_kept + 1))))
@@ -94,6 +100,10 @@ int hc::sr_next_store(hc_ctx* c, uint64_t n, uint64_t n_extra, uint32_t n_kept, 
     N.h_first.swap(h_first);
     N.total = total;
     N.raw_valid = true;
+    N.prev_traded = true;  // the store this call read lies in the next_* blocks now
+    N.prev_reads = n_reads_old;
+    N.prev_seq = n_seq_old;
+    N.prev_total = total_old;
     cn.ms_device += ms_b;
     return HC_OK;
 }
@@ -111,7 +121,10 @@ extern "C" int hc_sr_set_next_reads(hc_ctx* c, const hc_sr_next_entry* entries, 
     hc_sr_next_counts cn;
     memset(&cn, 0, sizeof cn);
     if (counts) *counts = cn;
-    if (n == 0) return HC_SR_NEXT_EMPTY;
+    if (n == 0) {
+        N.prev_traded = false;  // (hc_sr_fastq_write_text: the store this call read is the one in place)
+        return HC_SR_NEXT_EMPTY;
+    }
     HC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const uint32_t n_reads_old = (uint32_t)(N.h_first.size() - 1);
@@ -163,7 +176,10 @@ extern "C" int hc_sr_set_next_reads(hc_ctx* c, const hc_sr_next_entry* entries, 
     cn.ms_device = ms_a;
     if (counts) *counts = cn;
     if (cn.n_kept != n_kept) return fail(HC_ERR_STATE, std::string(me) + "the statuses and the device's count of survivors disagree");
-    if (n_kept == 0) return HC_SR_NEXT_EMPTY;  // the old store stays
+    if (n_kept == 0) {  // the old store stays
+        N.prev_traded = false;
+        return HC_SR_NEXT_EMPTY;
+    }
     if ((rc = hc::sr_next_store(c, n, n_extra, n_kept, n_seq, total, cn))) return rc;
     if (counts) *counts = cn;
     return HC_OK;

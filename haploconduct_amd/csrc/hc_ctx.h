@@ -271,7 +271,24 @@ struct hc_ctx {
         std::vector<uint32_t> h_first;
         hc_scratch next_bases, next_quals, next_off, next_first;
         hc_scratch entries, status, cnt, bytes, cnt_off, byte_off, temp, hist, extra_seq, extra_qual;
+        // The store the last next-store call READ (hc_sr_fastq_write_text's tips are reads of it).  prev_traded: the call replaced the store,
+        // and that store's raw arrays are the next_* blocks it traded, prev_reads / prev_seq / prev_total of them.  Otherwise it is the
+        // current store: the call returned HC_SR_NEXT_EMPTY, or none ran since hc_set_reads.  Cleared wherever the next_* blocks are
+        // reallocated, overwritten or freed: the start of a gather, hc_set_reads, hc_sr_keep_device(ctx, 0), hc_reset.
+        bool prev_traded = false;
+        uint32_t prev_reads = 0, prev_seq = 0;
+        uint64_t prev_total = 0;
+        void prev_clear() { prev_traded = false, prev_reads = prev_seq = 0, prev_total = 0; }
     } srn;
+    // hc_sr_fastq_write_text / hc_sr_fastq_text_fetch (hc_api_sr_fastq.cpp): grow-only scratch — the items' characters (their exclusive
+    // sum after the scan), the scan's workspace, the counters, the tips' reads — and the text of the four files in one block, file f at
+    // [bound[f], bound[f + 1]), kept until the next hc_sr_fastq_write_text or until raw arrays it was made from are replaced (drop())
+    struct SrFastq {
+        hc_scratch sizes, temp, counters, tip_reads, text;
+        uint64_t bound[5] = {0, 0, 0, 0, 0};
+        bool valid = false;
+        void drop() { valid = false; }
+    } sr_fastq;
     // self-overlap merge (hc_api_sr.cpp: hc_sr_merge_self_overlaps): grow-only scratch; the consensus tables are rebuilt when min_qual or
     // the batch's quality values change (term index = the value itself)
     struct SrSelf {

@@ -575,3 +575,19 @@ def sr_originals_parse(data):
     from . import originals as OR
 
     return OR.host_parse(data)
+
+
+def sr_fastq_text(reads, file):
+    """hc_host_sr_fastq_text: the bytes a ReadSet's reads put into singles.fastq (file 0), paired1.fastq (1) or paired2.fastq (2), in
+    ascending id (src/SRBuilder.cpp:1434-1447, :1484-1487, :1528-1535)."""
+    from . import fastq_text as FQ
+
+    return FQ.host_fastq_text(reads, file)
+
+
+def sr_fastq_tips_text(reads, tip_reads):
+    """hc_host_sr_fastq_tips_text: the bytes of removed_tip_sequences.fastq for the reads tip_reads[k] of a ReadSet (writeTipsToFile,
+    src/SRBuilder.cpp:1386-1414)."""
+    from . import fastq_text as FQ
+
+    return FQ.host_fastq_tips_text(reads, tip_reads)

@@ -213,6 +213,15 @@ class EdgeScorer:
 
         return OR.text(self._ctx)[0]
 
+    def sr_fastq_text(self, tips=None, vertex_read=None):
+        """hc_sr_fastq_write_text + hc_sr_fastq_text_fetch: the bytes of singles.fastq, paired1.fastq and paired2.fastq for the current store
+        and of removed_tip_sequences.fastq for the tips of the last sr_merge_next (its .tips and the vertex_read it took), as written by
+        src/SRBuilder.cpp:1386-1556.  Returns a dict: "singles", "paired1", "paired2", "tips" (bytes), "n_records", "n_bytes" (per file, in
+        that order), "ms_device"."""
+        from . import fastq_text as FQ
+
+        return FQ.text(self._ctx, tips, vertex_read)
+
     def info(self):
         k, sb = C.c_uint32(), C.c_uint64()
         d = [C.c_double() for _ in range(4)]

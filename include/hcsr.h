@@ -394,7 +394,7 @@ int hc_sr_kept_load(hc_ctx* ctx, const uint8_t* seq, const uint8_t* qual, uint64
 /* Copies [off, off + n) of the kept consensus bytes out — the merged reads of hc_sr_merge_self_overlaps_kept for whoever
  * writes them as text (src/SRBuilder.cpp:1416-1556), off the critical path.  *n_kept = the kept size, always filled (0 when
  * nothing is kept: HC_ERR_STATE).  A range that does not lie inside the kept bytes: HC_ERR_ARG, nothing copied.  n = 0 asks for
- * the size alone.  Left to the caller: the FASTQ text itself. */
+ * the size alone.  Left to the caller: which bytes of them are whose read (the FASTQ text of a store: hc_sr_fastq_write_text). */
 int hc_sr_kept_fetch(hc_ctx* ctx, uint64_t off, uint64_t n, uint8_t* seq, uint8_t* qual, uint64_t* n_kept);
 
 /* The same contract on the host (no device, no context): overlap_score (src/EdgeCalculator.cpp:26-139) offset by offset and
@@ -413,8 +413,9 @@ int hc_host_sr_merge_self_overlaps(const hc_settings* ec_settings, const uint8_t
  * vertex order, the paired ones last), writes them as FASTQ (:1416-1556: decimal ids, the sequences as stored) and reads the
  * files again.  hc_sr_set_next_reads does the filtering, the numbering and the copying on the device and replaces the
  * context's read store by the result.
- * Left to the caller: the FASTQ text itself.  (The original-index maps and subreads.txt: hc_sr_originals_next / hc_sr_originals_write_text,
- * from the subread infos of hc_sr_edge_merge / hc_sr_clique_merge.)  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
+ * Left to the caller: the files themselves.  (The FASTQ text of the new store: hc_sr_fastq_write_text, the last section.  The
+ * original-index maps and subreads.txt: hc_sr_originals_next / hc_sr_originals_write_text, from the subread infos of hc_sr_edge_merge /
+ * hc_sr_clique_merge.)  With hc_sr_set_next_reads the caller also lists the entries: it omits the vertices of :1298-1311 and re-sorts a
  * clique that merge_self_overlap merged (:911-949) itself; hc_sr_merge_next below builds the list, the marks, the tips and the
  * shifted cliques from an edge merge's outputs.  (The self-overlap test between the consensus call and this one runs on the kept
  * bytes: hc_sr_merge_self_overlaps_kept.) */
@@ -525,7 +526,8 @@ int hc_host_sr_next_reads(const uint8_t* bases, const uint8_t* quals, const uint
  * hc_fno1_input (hcfno.h) ready to use.
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in
  * arrival order (:1004-1011), which is not deterministic; one thread gives pair order.
- * Left to the caller: the FASTQ text, including removed_tip_sequences.fastq (the tips list names the vertices).  The original-index maps
+ * Left to the caller: appending the texts to the files.  The FASTQ text, including removed_tip_sequences.fastq: hc_sr_fastq_write_text,
+ * the last section, which takes this call's tips list and vertex_read as they are.  The original-index maps
  * (:750-806, :1312-1369) and subreads.txt: hc_sr_originals_next, below, on this call's outputs.  This call for cliques of more than two vertices is
  * hc_sr_clique_next, below, on hc_sr_clique_merge's outputs. */
 
@@ -653,8 +655,8 @@ int hc_host_sr_merge_next(const hc_settings* ec_settings, const uint8_t* bases, 
  * as hc_sr_merge_next does for an edge merge: it leaves the next store in the context and returns the tables of an hc_fno1_input.
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in arrival
  * order (:1004-1011), which is not deterministic; one thread gives clique order.
- * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select), the FASTQ text.  The
- * original-index maps (:750-806, :1161-1216) and subreads.txt: hc_sr_originals_next, below, on this call's outputs. */
+ * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select).  The FASTQ text of the
+ * new store: hc_sr_fastq_write_text, the last section.  The original-index maps (:750-806, :1161-1216) and subreads.txt: hc_sr_originals_next, below, on this call's outputs. */
 
 typedef struct hc_sr_clique_next_input {
     /* what hc_sr_clique_merge took and returned, unchanged: host arrays */
@@ -776,7 +778,7 @@ int hc_host_sr_clique_select(const uint64_t* clique_off, const uint32_t* clique_
  * iteration order; every reader puts the entries back into a map.  Here the entries of a read are in ASCENDING ORIGINAL ID, in the
  * arrays and in the text.  (2) index2 / len2 of a single-end original are never set nor printed by the reference: here they are 0 on
  * output and ignored on input.
- * Left to the caller: the FASTQ text; FNO=3 and BranchReduction, which read the dict. */
+ * Left to the caller: FNO=3 and BranchReduction, which read the dict.  (The FASTQ text: hc_sr_fastq_write_text, the next section.) */
 
 typedef struct hc_sr_original {
     uint32_t id;            /* the original read's id                                                                   */
@@ -907,6 +909,64 @@ int hc_host_sr_originals_text(const uint64_t* orig_off, const hc_sr_original* en
  * str_to_read_id would not take whole, or a value outside its type here. */
 int hc_host_sr_originals_parse(const char* text, uint64_t n_bytes, uint64_t* orig_off, uint64_t cap_reads, hc_sr_original* entries,
                                uint64_t cap_entries, uint64_t* n_reads, uint64_t* n_entries, uint64_t* bad_line);
+
+/* ---- singles.fastq, paired1.fastq, paired2.fastq and removed_tip_sequences.fastq from the device ----------------------------
+ *
+ * The last writer family of SRBuilder (src/SRBuilder.cpp:1386-1556): every iteration ends by appending its reads to singles.fastq,
+ * paired1.fastq and paired2.fastq — the last iteration's singles.fastq IS the assembler's result — and the tips it removed to
+ * removed_tip_sequences.fastq.  hc_sr_fastq_write_text writes the four texts on the device from raw arrays the context keeps,
+ * without a base or quality byte crossing the link before the text itself does.
+ *
+ * Files 0 - 2 are the context's CURRENT store: whatever hc_set_reads, hc_sr_set_next_reads, hc_sr_merge_next or hc_sr_clique_next last
+ * loaded while hc_sr_keep_device was on.  Read r, in ascending r: a single-end read puts "@r\nSEQ\n+\nQUAL\n" into singles.fastq, a
+ * paired one "@r\nSEQ1\n+\nQUAL1\n" into paired1.fastq and the same with mate 2 into paired2.fastq; r in decimal, the bytes as stored.
+ * That IS the reference's files: the next store numbers the single-end super-reads from 0, then the trivial ones in vertex order, then
+ * the paired ones (:1142, :1231-1233, :1280, :1377-1378), and writeSinglesToFile, writeTrivialsToFile and writePairsToFile run in that
+ * order, each appending its reads in ascending id (:1484-1487, :1434-1447, :1528-1535) — so every file holds its reads in ascending id
+ * of the store, which is the order here.
+ * The reference opens its files in append mode; here a text is ONE iteration's contribution, and the caller appends or truncates.
+ *
+ * File 3 (writeTipsToFile, :1386-1414): tip k — new_ID = k, from 0 in every call — is read vertex_read[tips[k]], taken FORWARD whatever
+ * the vertex's orientation: tips_vec.push_back(*read) (:1302, :1309) copies the stored read.  A paired read writes
+ * "@k_1\nSEQ1\n+\nQ1\n@k_2\nSEQ2\n+\nQ2\n", a single-end one "@k\nSEQ\n+\nQ\n".  tips / vertex_read are hc_sr_merge_next_output.tips and
+ * hc_sr_merge_next_input.vertex_read as they are; n_tips = 0 with NULL pointers is allowed.
+ * The tips are reads of the store the last next-store call READ, not of the one it left: after a replacement that store's raw arrays
+ * are still on the device (the call trades blocks), and the context remembers it; after HC_SR_NEXT_EMPTY, or when no such call ran
+ * since hc_set_reads, it is the current store.  A later next-store call moves on: tips are then reads of the store THAT call read.
+ *
+ * HC_ERR_STATE: keeping is off, or no kept raw arrays.  HC_ERR_ARG: a tip vertex >= n_vertices, a vertex_read of a tip that is no read
+ * of that store (both found by a host pass over the tips before any launch), 2^32 tips or more.  An error leaves the kept text as it
+ * was.  The text stays in the context until the next hc_sr_fastq_write_text or until raw arrays it was made from are replaced
+ * (hc_set_reads, a next-store call that replaces the store, hc_sr_keep_device(ctx, 0), hc_reset); a fetch after that: HC_ERR_STATE.
+ * Four launches whatever the sizes: a lane per read and per tip for the records' characters, one exclusive sum that lays the four files
+ * behind one another, the boundaries, and a wave per record that copies sequence and quality with 16-byte stores on 16-byte boundaries
+ * of the text.  All sizes and offsets are 64-bit: a file may exceed 4 GiB.
+ * Left to the caller: the files themselves — opening, appending or truncating, compression. */
+
+enum { HC_SR_FASTQ_SINGLES = 0, HC_SR_FASTQ_PAIRED1 = 1, HC_SR_FASTQ_PAIRED2 = 2, HC_SR_FASTQ_TIPS = 3 };
+
+typedef struct hc_sr_fastq_counts {
+    uint64_t n_records[4]; /* '@' lines per file */
+    uint64_t n_bytes[4];   /* characters per file */
+    double ms_device;      /* this section's kernels and sums, by events on the context's stream */
+} hc_sr_fastq_counts;      /* 72 bytes */
+
+int hc_sr_fastq_write_text(hc_ctx* ctx, const uint32_t* tips, uint64_t n_tips, const uint32_t* vertex_read, uint64_t n_vertices,
+                           hc_sr_fastq_counts* counts);
+
+/* Copies bytes [first, first + count) of file HC_SR_FASTQ_* out.  A range outside the file, or file > 3: HC_ERR_ARG; count = 0 is OK,
+ * also for an empty file; no text: HC_ERR_STATE. */
+int hc_sr_fastq_text_fetch(hc_ctx* ctx, uint32_t file, uint64_t first, uint64_t count, char* dst);
+
+/* The same texts on the host (no device, no context) from a store as hc_set_reads takes it.  file: 0, 1 or 2.  text: room for cap bytes;
+ * *n_bytes is always filled, and where cap is too small or text is NULL nothing is copied and HC_ERR_ARG is returned (count, then fetch).
+ * HC_ERR_ARG also: a null array, a read that owns neither 1 nor 2 sequences, descending offsets. */
+int hc_host_sr_fastq_text(const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off, const uint32_t* read_first_seq,
+                          uint32_t n_reads, uint32_t file /* 0..2 */, char* text, uint64_t cap, uint64_t* n_bytes);
+/* writeTipsToFile (:1386-1414) for the reads tip_reads[k] of the store, k = new_ID: the caller maps vertices to reads itself.  A tip
+ * read >= n_reads: HC_ERR_ARG.  cap / *n_bytes as above (count, then fetch). */
+int hc_host_sr_fastq_tips_text(const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off, const uint32_t* read_first_seq,
+                               uint32_t n_reads, const uint32_t* tip_reads, uint64_t n_tips, char* text, uint64_t cap, uint64_t* n_bytes);
 
 #ifdef __cplusplus
 }
