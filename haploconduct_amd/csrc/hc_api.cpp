@@ -161,6 +161,7 @@ static void free_store(hc_ctx* c) {
     c->loc_reads = 0;
     c->srn.prev_clear();  // (hc_sr_fastq_write_text: the raw arrays go or are replaced with the store)
     c->sr_fastq.drop();
+    c->br.drop();  // (hc_br_evidence's tables were made from the old store)
 }
 
 int hc_destroy(hc_ctx* c) {
@@ -854,6 +855,8 @@ int hc_reset(hc_ctx* c, const hc_settings* settings) {
     c->reorder_mode = HC_REORDER_AUTO;
     c->graph.valid = false;
     c->graph.n_appended = 0;
+    c->br.orig_valid = false;  // (hc_br_set_original_reads: until replaced or hc_reset)
+    c->br.n_orig = 0;
     apply_settings(c, settings);
     return HC_OK;
 }

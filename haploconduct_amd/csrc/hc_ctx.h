@@ -339,6 +339,20 @@ struct hc_ctx {
         bool text_valid = false;
         void replaced() { text_valid = false, n_text = 0; }
     } sr_orig;
+    // hc_br_* (hc_api_br.cpp): the original reads (orig_bases, orig_off: n_orig + 1 offsets) until replaced or hc_reset; the call's vertex
+    // tables; grow-only work blocks, each carved into the arrays of hc_br.h: Work by the phase that sizes it (work_v: per vertex, edge and
+    // record; work_b: per branch, neighbour and pair; work_d: per diff slot in use; work_e: per item key); the prims' workspace; and the
+    // tables (t_*), `counts` of them, valid until the graph, the store or the dict's store is replaced (drop())
+    struct Br {
+        hc_scratch orig_bases, orig_off;
+        uint64_t n_orig = 0;
+        bool orig_valid = false;
+        hc_scratch vread, vfwd, work_v, work_b, work_d, work_e, temp, counters;
+        hc_scratch t_branches, t_nb, t_diff, t_ev_edge, t_ev_off, t_ev_ids, t_missing;
+        hc_br_counts counts{};
+        bool valid = false;
+        void drop() { valid = false; }
+    } br;
 };
 
 namespace hc {

@@ -48,6 +48,10 @@ hipError_t find_tips(const Graph& in, uint32_t max_tip_len, const hc_read_geom* 
 hipError_t find_branches(const Graph& in, hc_branch_counts* counts, void* temp, size_t temp_bytes, hipStream_t s);
 hipError_t commit_removed(const Graph& in, Graph& out, bool target_ordered, hc_edge_rec* removed, uint64_t n_removed, void* temp, size_t temp_bytes,
                           hipStream_t s);
+// sortAdjOut alone (hc_br_evidence): the records and seq of `in` in sortAdjOut's order — the target-order step of find_branches, its host
+// step for lists that repeat a target included — into out.edges / out.seq (room for in.E).  The order changes inside lists only: the
+// offsets and adj_in are not touched.  in.E > 0.
+hipError_t sort_adj_out(const Graph& in, Graph& out, uint64_t* n_tied_lists, void* temp, size_t temp_bytes, hipStream_t s);
 
 }  // namespace trans
 }  // namespace hc

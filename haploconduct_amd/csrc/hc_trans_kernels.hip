@@ -1092,5 +1092,25 @@ hipError_t commit_removed(const Graph& g, Graph& out, bool target_ordered, hc_ed
     return hipSuccess;
 }
 
+__global__ void k_permute_records(const uint32_t* __restrict__ perm, uint32_t n, const hc_edge_rec* __restrict__ E, const uint32_t* __restrict__ seq,
+                                  hc_edge_rec* __restrict__ E_out, uint32_t* __restrict__ seq_out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t k = perm[i];
+        E_out[i] = E[k];
+        seq_out[i] = seq[k];
+    }
+}
+
+hipError_t sort_adj_out(const Graph& g, Graph& out, uint64_t* n_tied_lists, void* temp, size_t temp_bytes_, hipStream_t s) {
+    Carve c{(char*)(((uintptr_t)temp + 255) & ~(uintptr_t)255)};
+    const Work w = layout(c, g.E, g.V);
+    if (c.used + 256 > temp_bytes_ || !g.E) return hipErrorInvalidValue;
+    TRY(hipMemsetAsync(w.counters, 0, 8 * sizeof(unsigned long long), s));
+    TRY(hipMemsetAsync(w.tied, 0, (size_t)g.V + 1, s));
+    TRY(std_sort_target_order(g, w, n_tied_lists, s));
+    hipLaunchKernelGGL(k_permute_records, grid_for(g.E), dim3(kBlock), 0, s, w.perm, g.E, g.edges, g.seq, out.edges, out.seq);
+    return hipGetLastError();
+}
+
 }  // namespace trans
 }  // namespace hc

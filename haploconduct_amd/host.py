@@ -591,3 +591,11 @@ def sr_fastq_tips_text(reads, tip_reads):
     from . import fastq_text as FQ
 
     return FQ.host_fastq_tips_text(reads, tip_reads)
+
+
+def br_evidence(graph, reads, orig_off, entries, original_bases, original_seq_off, vertex_read, vertex_fwd, settings, n_threads=1):
+    """hc_host_br_evidence: the host mirror of EdgeScorer.br_evidence + br_evidence_fetch (src/BranchReduction.cpp:229-743 for every branch,
+    :60-80) on a graph as graph_fetch returns it, a ReadSet, the dict over its reads and the original reads -> branch_evidence.BranchEvidence."""
+    from . import branch_evidence as BR
+
+    return BR.host_evidence(graph, reads, orig_off, entries, original_bases, original_seq_off, vertex_read, vertex_fwd, settings, n_threads)

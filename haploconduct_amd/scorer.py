@@ -213,6 +213,28 @@ class EdgeScorer:
 
         return OR.text(self._ctx)[0]
 
+    def br_set_original_reads(self, bases, seq_off):
+        """hc_br_set_original_reads: the sequences of --original_fastq (single-end, one byte per base, n + 1 offsets), kept on the device."""
+        from . import branch_evidence as BR
+
+        BR.set_original_reads(self._ctx, bases, seq_off)
+
+    def br_evidence(self, vertex_read, vertex_fwd, settings):
+        """hc_br_evidence: findBranchingEvidence (src/BranchReduction.cpp:229-743) for every branch of the device graph, from the kept store,
+        the kept dict and the original reads.  settings: branch_evidence.settings(...).  Leaves adj_out in target order.  Returns the counts
+        (a dict, "some_failed" among them); br_evidence_fetch returns the tables."""
+        from . import branch_evidence as BR
+
+        d, self._br_counts = BR.evidence(self._ctx, vertex_read, vertex_fwd, settings)
+        return d
+
+    def br_evidence_fetch(self):
+        """hc_br_evidence_fetch: the tables of the last br_evidence as a branch_evidence.BranchEvidence."""
+        from . import branch_evidence as BR
+
+        cn = getattr(self, "_br_counts", None)
+        return BR.fetch(self._ctx, cn if cn is not None else BR.hc_br_counts())
+
     def sr_fastq_text(self, tips=None, vertex_read=None):
         """hc_sr_fastq_write_text + hc_sr_fastq_text_fetch: the bytes of singles.fastq, paired1.fastq and paired2.fastq for the current store
         and of removed_tip_sequences.fastq for the tips of the last sr_merge_next (its .tips and the vertex_read it took), as written by

@@ -778,7 +778,8 @@ int hc_host_sr_clique_select(const uint64_t* clique_off, const uint32_t* clique_
  * iteration order; every reader puts the entries back into a map.  Here the entries of a read are in ASCENDING ORIGINAL ID, in the
  * arrays and in the text.  (2) index2 / len2 of a single-end original are never set nor printed by the reference: here they are 0 on
  * output and ignored on input.
- * Left to the caller: FNO=3 and BranchReduction, which read the dict.  (The FASTQ text: hc_sr_fastq_write_text, the next section.) */
+ * Left to the caller: FNO=3, which reads the dict.  (BranchReduction's read evidence: hc_br_evidence, the section behind this one's
+ * functions; the FASTQ text: hc_sr_fastq_write_text, the section after that.) */
 
 typedef struct hc_sr_original {
     uint32_t id;            /* the original read's id                                                                   */
@@ -909,6 +910,165 @@ int hc_host_sr_originals_text(const uint64_t* orig_off, const hc_sr_original* en
  * str_to_read_id would not take whole, or a value outside its type here. */
 int hc_host_sr_originals_parse(const char* text, uint64_t n_bytes, uint64_t* orig_off, uint64_t cap_reads, hc_sr_original* entries,
                                uint64_t cap_entries, uint64_t* n_reads, uint64_t* n_entries, uint64_t* bad_line);
+
+/* ---- read evidence for branching edges: the first half of BranchReduction::readBasedBranchReduction -------------------------
+ *
+ * POLYTE runs every iteration with --branch_reduction, so its branch step is readBasedBranchReduction (src/ViralQuasispecies.cpp:326-347,
+ * src/BranchReduction.cpp:41-227).  Its first half — findBranchingEvidence with buildDiffListOut, buildDiffListIn, findDiffPos and
+ * checkReadEvidence (:229-743), called for every in-branch and then every out-branch (:60-80) — reads the cleaned graph, the store's
+ * sequences, the original-read index maps and the reads of --original_fastq, and every result of it is independent of hash iteration
+ * order because the lists are sorted before use.  hc_br_evidence computes it on the device from what the context holds.  The second half
+ * (findBranchingComponents, countUniqueEvidence, the threshold file and the removals, :745-1272) walks unordered_maps in iteration
+ * order, and under --careful its result depends on that order: it stays with the caller, who fetches the tables below.
+ *
+ * A branch is a vertex with more than one in-neighbour (side HC_BR_IN) or more than one out-neighbour (HC_BR_OUT); its neighbours are
+ * sortAdjLists(adj_in) / sortAdjOut(adj_out) (:47-48), ascending.  The edge of a neighbour is getEdgeInfo's: the FIRST record
+ * node1 -> node (out) / node -> node1 (in) in list order after sortAdjOut; pos = its pos1, the neighbour's read = its read2 (out) /
+ * read1 (in), an index into the store.  The reference indexes original_ID_dict by vertex, which is the read wherever --add_duplicates
+ * is off; HERE THE DICT OF VERTEX v IS THE DICT OF READ vertex_read[v].  vertex_read / vertex_fwd mean what they mean for
+ * hc_sr_edge_merge (getOrientation(v) = vertex_fwd[v]).
+ *
+ * Restated as the reference has it:
+ *  - every neighbour sequence takes the orientation of node1, not its own (:414, :556); a reverse node1 reads the neighbour's stored
+ *    bytes back to front through build_rev_comp's mapping (a byte build_rev_comp exits on stays as it is);
+ *  - an in-branch compares its pairs from the back and records len - pos + startpos (:627), one beyond the position it found;
+ *  - result2 re-checks the sub-read itself: it differs from result1 only in which id must be in subreads1 (:304-321);
+ *  - the joint id is original_readcount + min(id, mate id) (:318);
+ *  - read_end uses the ORIGINAL read's full length, not the entry's len1 (:720);
+ *  - int(seq.size() - min_overlap_len) is a 64-bit difference cut to 32 bits (:449, :461, :605, :616);
+ *  - dist = 0.5 * (min + max) assigned to an int: it truncates toward zero (:521-530, :675-684);
+ *  - with exactly two neighbours and a missing inclusion pair final_branch is cleared (:330-332); the ++ on its begin() at :349 then
+ *    lands on end() in libstdc++, so nothing is stored for the branch;
+ *  - checkReadEvidence's early break (:733-737) makes its result "no covered position disagrees and at least one is covered", which does
+ *    not depend on the walk's order; the covered positions are one contiguous range of the sorted diff list;
+ *  - pos3 / pos4 of a missing edge are never set by the reference (src/Edge.h:41-56): 0 here. */
+
+enum { HC_BR_IN = 0, HC_BR_OUT = 1 };
+/* Per branch: the reference's asserts on this path, checked in the reference's order (the first that fails is reported). */
+enum {
+    HC_BR_OK = 0,
+    HC_BR_PAIRED_NEIGHBOUR = 1,   /* assert (!read->is_paired()), :412, :554                                                       */
+    HC_BR_REPEATED_NEIGHBOUR = 2, /* assert (node_i != node_j), :446; the same pair in the in-branch loop is refused alike         */
+    HC_BR_BAD_GEOMETRY = 3,       /* assert (len > 0), :471 / :625 (a relative position beyond the sequence included, where substr
+                                     throws); the inclusion asserts of an in-branch, :605 / :616                                    */
+    HC_BR_BAD_ORIGINAL = 4        /* get_read of a dict id that is no original read (:288, :306); the asserts :300 / :319         */
+};
+/* hc_br_evidence / hc_host_br_evidence: HC_OK is 0; branches with a status other than OK are no error of the arguments.  A failed branch
+ * contributes nothing: no evidence, no missing edge, no false mark, an empty final_branch and diff list, dist 0. */
+#define HC_BR_SOME_FAILED 1
+#define HC_BR_MAX_DIFFS 100u /* findDiffPos keeps at most 100 positions per pair, :703 */
+
+typedef struct hc_br_settings {
+    uint64_t se_count, pe_count;  /* program_settings.branch_SE_c / branch_PE_c: originals are numbered singles, /1 mates, /2 mates  */
+    uint64_t original_readcount;  /* program_settings.original_readcount (< 2^31)                                                    */
+    uint32_t min_overlap_len;     /* program_settings.min_overlap_len                                                                */
+    uint32_t reserved;            /* 0                                                                                               */
+    double edge_threshold;        /* program_settings.edge_threshold: the score of a missing edge                                    */
+} hc_br_settings; /* 40 bytes */
+
+typedef struct hc_br_branch {
+    uint32_t node;      /* the branching vertex                                                                                     */
+    uint8_t side;       /* HC_BR_IN / HC_BR_OUT                                                                                     */
+    uint8_t status;     /* HC_BR_*                                                                                                  */
+    uint8_t is_false;   /* member of false_in_branches / false_out_branches (:513, :667)                                            */
+    uint8_t pad;        /* 0                                                                                                        */
+    int32_t dist;       /* the int of :521-530 / :675-684                                                                           */
+    uint32_t nb_count;  /* final_branch without its front entry: branch_nb[nb_first, nb_first + nb_count); 0 where :330-332 cleared */
+    uint64_t nb_first;
+    uint64_t diff_first; /* the sorted, de-duplicated diff list (:532-533, :686-687): diff_pos[diff_first, diff_first + diff_count)  */
+    uint32_t diff_count;
+    uint32_t n_neighbours; /* neighbours.size()                                                                                      */
+} hc_br_branch; /* 40 bytes */
+
+typedef struct hc_br_counts {
+    uint64_t n_branches;  /* records of `branches`: in-branches in ascending vertex, then out-branches in ascending vertex (:60-80) */
+    uint64_t n_branch_nb; /* entries of branch_nb                                                                                   */
+    uint64_t n_diff;      /* entries of diff_pos                                                                                    */
+    uint64_t n_ev_edges;  /* keys of evidence_per_edge                                                                              */
+    uint64_t n_ev_ids;    /* ids in all its lists                                                                                   */
+    uint64_t n_missing;   /* missing_edges                                                                                          */
+    uint64_t n_items;     /* (branch, neighbour, entry of the neighbour's dict) triples of the branches that reach the evidence loop */
+    uint64_t n_failed;    /* branches whose status is not HC_BR_OK                                                                  */
+    double ms_device;     /* device call only: the target-order step, kernels, sorts and sums by events on the context's stream     */
+} hc_br_counts; /* 72 bytes */
+
+/* Count, then fetch: every pointer may be NULL (not wanted); a wanted table whose cap is below its count: HC_ERR_ARG, nothing copied.
+ *   branch_nb      the neighbours of every final_branch: the sorted list minus node_pair.first of every missing inclusion pair (:328-335)
+ *   diff_pos       per branch its diff list
+ *   ev_edge        evidence_per_edge's keys as pairs u, v (2 * cap_ev_edges entries) in ascending (u, v) — an edge is listed exactly when
+ *                  the reference's map has its key, an empty list included —, ev_off (cap_ev_edges + 1) into ev_ids, ids ascending; an
+ *                  edge stored from both its in-branch and its out-branch holds the intersection (:367-384)
+ *   missing_edges  (:476-511, :630-665) in push order: branches as above, pairs in (i, j) order; score = edge_threshold, pos1 = relative_pos, pos2 = 0,
+ *                  ord '-', ori1 / ori2 / read1 / read2 / v1 / v2 by :489-506 / :643-660, perc by the integer division of :487 / :641,
+ *                  len0 = len1 = len, len2 = 0, mismatch_rate = -1, pos3 = pos4 = 0 */
+typedef struct hc_br_tables {
+    hc_br_branch* branches;
+    uint64_t cap_branches;
+    uint32_t* branch_nb;
+    uint64_t cap_branch_nb;
+    int32_t* diff_pos;
+    uint64_t cap_diff;
+    uint32_t* ev_edge;
+    uint64_t* ev_off;
+    uint64_t cap_ev_edges;
+    uint32_t* ev_ids;
+    uint64_t cap_ev_ids;
+    hc_edge_rec* missing_edges;
+    uint64_t cap_missing;
+} hc_br_tables; /* 104 bytes */
+
+/* The sequences of --original_fastq as FastqStorage holds them: single-end (src/ViralQuasispecies.cpp:328-334), one byte per base,
+ * n_reads + 1 ascending offsets from 0.  They stay on the device until replaced or hc_reset.  HC_ERR_ARG: a null array, offsets that
+ * do not start at 0 or descend, 2^32 reads or more. */
+int hc_br_set_original_reads(hc_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint64_t n_reads);
+
+/* findBranchingEvidence for every branch of the graph the context holds.  HC_ERR_STATE unless the context has a graph (not one with
+ * hc_graph_resolve's tied lists), a store loaded while hc_sr_keep_device was on, a kept dict with as many reads as the store, and
+ * original reads.  HC_ERR_ARG: a null argument, n_vertices that is not the graph's, se_count + 2 * pe_count != the original reads (the
+ * assert of src/ViralQuasispecies.cpp:341), original_readcount >= 2^31, a vertex_read that is no read of the store, a neighbour's record
+ * whose read1 / read2 is no read of the store (checked for every neighbour, ahead of any status), 2^32 / 100 neighbour pairs or 2^31 items or more.
+ * SIDE EFFECT ON THE GRAPH: adj_out is left in target order — sortAdjOut's side effect (:48, src/GraphAlgos.cpp:831), by the step
+ * hc_graph_remove_branches uses, its host step for lists that repeat a target included.  Apart from that the graph is read, never
+ * written: no edge is removed and branching_edges is not touched.
+ * The tables stay on the device until the next hc_br_evidence, hc_graph_load / hc_graph_resolve, hc_set_reads or hc_reset; a fetch
+ * after that: HC_ERR_STATE.
+ * A fixed number of launches whatever the degrees and dict sizes (DESIGN.md §5 has the kernels): A — a lane per vertex and side, per
+ * neighbour and per branch, then a WAVE per pair of neighbour sequences that walks the overlap 64 positions at a time and ranks the
+ * differing lanes by ballot; B — per branch its status, dist and final_branch, one stable radix sort of branch << 32 | position for the
+ * diff lists; C — a lane per item (branch, neighbour, dict entry) with binary searches of node1's dict and of the diff list, up to two
+ * keys record << 33 | id << 1 | side; D — one stable sort of the keys, the intersection where both sides stored the edge, selections.
+ * A branch that fails only in C (HC_BR_BAD_ORIGINAL) is known after B has laid its lists out: the call then runs B - D once more with
+ * those branches failed (at most once: branches do not depend on one another). */
+int hc_br_evidence(hc_ctx* ctx, const uint32_t* vertex_read, const uint8_t* vertex_fwd, uint64_t n_vertices, const hc_br_settings* settings,
+                   hc_br_counts* counts);
+/* The tables of the last hc_br_evidence (cap_* in the struct).  HC_ERR_STATE: none kept. */
+int hc_br_evidence_fetch(hc_ctx* ctx, hc_br_tables* tables);
+
+/* The same on the host (no device, no context), following the reference's loops: the yardstick for the device call.  The graph as
+ * hc_graph_fetch returns it (adj_out in any order: the mirror sorts a copy as sortAdjOut does and leaves the caller's arrays alone), the
+ * store's raw arrays as hc_set_reads takes them, the dict as hc_sr_originals_fetch returns it (over n_reads reads), the original reads
+ * as hc_br_set_original_reads takes them.  counts is always filled; tables may be NULL (count, then fetch).  n_threads: branches are
+ * independent (0 or 1: one thread). */
+typedef struct hc_br_host_input {
+    const hc_edge_rec* edges;
+    const uint64_t* out_off;
+    const uint32_t* in_nodes;
+    const uint64_t* in_off;
+    uint64_t n_vertices;
+    const uint8_t* bases;
+    const uint64_t* seq_off;
+    const uint32_t* read_first_seq;
+    uint64_t n_reads;
+    const uint64_t* orig_off;
+    const hc_sr_original* entries;
+    const uint8_t* original_bases;
+    const uint64_t* original_seq_off;
+    uint64_t n_original_reads;
+    const uint32_t* vertex_read;
+    const uint8_t* vertex_fwd;
+} hc_br_host_input; /* 128 bytes */
+int hc_host_br_evidence(const hc_br_host_input* in, const hc_br_settings* settings, hc_br_counts* counts, hc_br_tables* tables,
+                        uint32_t n_threads);
 
 /* ---- singles.fastq, paired1.fastq, paired2.fastq and removed_tip_sequences.fastq from the device ----------------------------
  *
