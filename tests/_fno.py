@@ -207,3 +207,259 @@ def fno3_scenario(seed, n_single=12, n_paired=8, n_trivial=10, n_originals=60, f
         originals.append(o)
     return F.Fno3Input(srs, n_single, n_paired, n_trivial, originals, new_read_count=n, original_readcount=n_originals, flags=flags,
                        n_threads=n_threads)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Numeric edges of the device's sort keys (tests/test_fno_numeric_edges.py, tests/test_gpu_fno_numeric_edges.py).
+# Every number a line can carry at the widths the keys have to hold: std::to_string(int) has up to 11 characters, a sign
+# among them; an id below 10^10 up to 10 digits.
+I32 = [0, 1, 9, 10, 11, 99, 100, 101, 999, 1000, 99999, 100000, 999999999, 10 ** 9, 2 ** 31 - 1,
+       -1, -9, -10, -11, -99, -100, -999999999, -10 ** 9, -(2 ** 31 - 1), -2 ** 31]
+PERCS = [0, 1, 9, 10, 11, 99, 100, 101, 999]
+ORDS = ["-", "1", "2"]
+IDS = [0, 9, 10, 99, 100, 999, 1000, 9999, 10 ** 4, 99999, 10 ** 5, 999999, 10 ** 6, 10 ** 7 - 1, 10 ** 7, 10 ** 8 - 1, 10 ** 8, 10 ** 9 - 1, 10 ** 9,
+       2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 10 ** 10 - 1]  # every digit count from 1 to 10
+LOW_PAIR, HIGH_PAIR = (5, 7), (2 ** 33, 10 ** 10 - 2)
+FORCED_LABELS = [0, 9, 10, 10 ** 9 - 1, 10 ** 9, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 10 ** 10 - 1]
+
+
+def row(id1=5, id2=7, pos1=37, pos2=0, ord_="-", perc=50, len1=60, len2=0, p1=False, p2=False, score=1.0, src="graph", ori1=1, ori2=1,
+        vo1=1, vo2=1):
+    """One edge between two unvisited vertices as copied_scenario takes it: the line's columns, the types as `paired` of the two
+    vertices, where the edge comes from (graph / branching / nonedge), and for a stored non-edge the edge's and the vertices'
+    orientations (ori*, vo*)."""
+    return dict(id1=id1, id2=id2, pos1=pos1, pos2=pos2, ord=ord_, perc=perc, len1=len1, len2=len2, p1=bool(p1), p2=bool(p2),
+                score=0.0 if src == "nonedge" else score, src=src, ori1=ori1, ori2=ori2, vo1=vo1, vo2=vo2)
+
+
+def copied_scenario(rows, flags=F.RESOLVE_ORIENTATIONS, new_read_count=None, seed=0):
+    """An FNO=1 input without super-reads and without visited vertices: every edge is copied (src/FindNextOverlaps.cpp:44-68).  A
+    vertex per (id, type, orientation) that occurs — two vertices may carry one id, ids are what the caller says they are — and
+    another set of vertices for the stored non-edges, so that no edge of the graph stands in front of one (:702).  The rows are
+    shuffled first: the input must not lie in the order of the output, or a stable sort that ignores part of a key would go
+    unnoticed.  graph_edges are then laid vertex by vertex (adj_out order)."""
+    rng = np.random.default_rng(seed)
+    rows = [rows[i] for i in rng.permutation(len(rows))]
+    vertex, recs = {}, {"graph": [], "branching": [], "nonedge": []}
+
+    def v(id_, paired, ori, non):
+        return vertex.setdefault((int(id_), paired, int(ori), non), len(vertex))
+    for r in rows:
+        non = r["src"] == "nonedge"
+        recs[r["src"]].append((v(r["id1"], r["p1"], r["vo1"], non), v(r["id2"], r["p2"], r["vo2"], non), r["score"], r["pos1"], r["pos2"],
+                               r["len1"], r["len2"], r["perc"], ord(r["ord"]), r["ori1"], r["ori2"], 0))
+    nodes = np.zeros(len(vertex), F.FNO_READ_DTYPE)
+    for (id_, paired, ori, _), k in vertex.items():
+        nodes[k] = make_read(id_, 100, 100, int(paired), 0, ori)
+    edges = {k: np.array(x, F.FNO_EDGE_DTYPE) if x else np.zeros(0, F.FNO_EDGE_DTYPE) for k, x in recs.items()}
+    graph = edges["graph"][np.argsort(edges["graph"]["v1"], kind="stable")]
+    if new_read_count is None:
+        new_read_count = max(k[0] for k in vertex) + 1
+    return F.Fno1Input(nodes, np.zeros(0, F.FNO_READ_DTYPE), [], [], graph, branching_edges=edges["branching"], nonedges=edges["nonedge"],
+                       new_read_count=new_read_count, flags=flags)
+
+
+def copied_lines(inp):
+    """R1: the lines of an input in which every edge is copied, in walk order, as src/FindNextOverlaps.cpp:35-68 writes them, with
+    Python's str() of every number.  overlaps.txt is b"".join(sorted(set(lines))) — std::set<std::string> — and `copied` counts
+    len(lines)."""
+    assert len(inp.srs) == 0 and not inp.nodes["visited"].any() and inp.n_inclusion_groups == 0, "not a scenario of copied edges only"
+    joined = {frozenset((int(e["v1"]), int(e["v2"]))) for e in inp.graph_edges if e["score"] > 0}
+    sources = [inp.graph_edges, inp.branching_edges]
+    if not inp.flags & F.OPTIMIZE:  # :914
+        assert all(e["score"] == 0 and frozenset((int(e["v1"]), int(e["v2"]))) not in joined for e in inp.nonedges), "checkEdge would drop it (:702)"
+        sources.append(inp.nonedges)
+    lines = []
+    for e in np.concatenate(sources):
+        n1, n2 = inp.nodes[int(e["v1"])], inp.nodes[int(e["v2"])]
+        o1 = o2 = "+"
+        if inp.flags & F.RESOLVE_ORIENTATIONS and e["score"] == 0:  # :35-38
+            o1 = "+" if bool(e["ori1"]) == bool(n1["orientation"]) else "-"
+            o2 = "+" if bool(e["ori2"]) == bool(n2["orientation"]) else "-"
+        if inp.flags & F.NO_INCLUSIONS and e["perc"] == 100:  # :68
+            continue
+        cols = [int(n1["id"]), int(n2["id"]), int(e["pos1"]), int(e["pos2"]), chr(int(e["ord"])), o1, o2, int(e["perc"]), 0, int(e["len1"]), int(e["len2"]),
+                "p" if n1["paired"] else "s", "p" if n2["paired"] else "s"]
+        lines.append(("\t".join(str(c) for c in cols) + "\n").encode())
+    return lines
+
+
+def copied_text(inp):
+    """(overlaps.txt, counters) of R1."""
+    lines = copied_lines(inp)
+    return b"".join(sorted(set(lines))), {"n_lines": len(set(lines)), "copied": len(lines), "u2sr": 0, "v2sr": 0, "sr2sr": 0, "candidates": 0}
+
+
+LADDER_VALUES = {"pos1": I32, "pos2": I32, "len1": I32, "len2": I32, "perc": PERCS, "ord_": ORDS, "id1": IDS, "id2": IDS}
+LADDER_FIELDS = list(LADDER_VALUES)
+
+
+def ladder_rows(field, pair):
+    """All columns fixed but `field`, which runs over its whole list, on the pair of ids `pair` (an id ladder replaces one of the
+    two): once as edges of the graph and, under every one of the four `ori1 ori2` combinations, as stored non-edges — with the
+    vertices' orientations varied too, so that a '-' comes about both ways.  Edge::set_len keeps len1 > 0 and len2 >= 0 on the
+    non-edges."""
+    base = dict(id1=pair[0], id2=pair[1])
+    rows = [row(**{**base, field: x}) for x in LADDER_VALUES[field]]
+    for k, (s1, s2) in enumerate([(1, 1), (1, 0), (0, 1), (0, 0)]):  # the columns' signs: 1 -> '+'
+        vo1, vo2 = k & 1, (k >> 1) & 1
+        for x in LADDER_VALUES[field]:
+            if (field == "len1" and x <= 0) or (field == "len2" and x < 0):
+                continue
+            rows.append(row(**{**base, field: x}, src="nonedge", vo1=vo1, vo2=vo2, ori1=vo1 if s1 else 1 - vo1, ori2=vo2 if s2 else 1 - vo2))
+    return rows
+
+
+# the device's 256-bit key, from its definition (DESIGN.md §5; csrc/hc_fno_kernels.hip, "decimal text <-> order-preserving integers")
+def key_unsigned(v, places):
+    """The text of v followed by a tab as a number in base 11 with `places` places: digit d -> d + 1, nothing -> 0."""
+    s = str(v)
+    assert len(s) <= places
+    return sum((int(c) + 1) * 11 ** (places - 1 - i) for i, c in enumerate(s))
+
+
+def key_signed(x):
+    """The same with a sign: base 12, 11 places, '-' -> 1, digit d -> d + 2."""
+    return sum((1 if c == "-" else int(c) + 2) * 12 ** (10 - i) for i, c in enumerate(str(x)))
+
+
+SPLIT_BIT = {"id2": 6, "pos2": 22, "len1": 13}  # where the field's key is cut between two 64-bit words
+
+
+def field_key(field, x):
+    return key_unsigned(x, 10) if field == "id2" else key_signed(x)
+
+
+def split_kinds(field, values):
+    """(some two values' keys differ only below the field's split, some two only above it)"""
+    bit = SPLIT_BIT[field]
+    keys = sorted({field_key(field, x) for x in values})
+    below = any(a >> bit == b >> bit for a, b in zip(keys, keys[1:]))
+    highs = {}
+    for k in keys:
+        highs.setdefault(k & ((1 << bit) - 1), set()).add(k >> bit)
+    return below, any(len(h) > 1 for h in highs.values())
+
+
+STRADDLE_VALUES = {
+    # keys one or two apart over more than one multiple of 64, a nine-digit prefix of a ten-digit id (nothing against '0'), and the ladder
+    "id2": IDS + list(range(9876543000, 9876543200)) + [987654300, 987654301],
+    # 12^10 + 4 * 12^9 is a multiple of 2^22: "10..." against "24..." differ only above the split; neighbours only below it
+    "pos2": I32 + [100000000 + t for t in (0, 1, 7, 50)] + [240000000 + t for t in (0, 1, 7, 50)] + list(range(-2 ** 31, -2 ** 31 + 40)) +
+            list(range(1234567800, 1234567840)),
+    # 12^7 and above are multiples of 2^13: the first four characters differ only above the split; last digits of long numbers below it
+    "len1": I32 + [1000, 2000, 3000, 1001, 2001, -1000, -2000] + list(range(2147483600, 2147483648)) + list(range(-2 ** 31, -2 ** 31 + 40)),
+}
+
+
+def straddle_rows(field, pair=HIGH_PAIR):
+    """Lines that agree in every column but `field`, whose key is split between two words."""
+    base = dict(id1=pair[0], id2=pair[1], pos1=-2 ** 31, pos2=2 ** 31 - 1, len1=10 ** 9, len2=77, perc=999, ord_="2", p1=True, p2=True)
+    return [row(**{**base, field: x}) for x in STRADDLE_VALUES[field]]
+
+
+def tail_rows(pair=HIGH_PAIR):
+    """The bits at the bottom of the last word: lines that differ only in len2, only in type1, only in type2 (two vertices share an id,
+    one single-end, one paired), and whole lines repeated in the graph's and the branching edges' lists."""
+    base = dict(id1=pair[0], id2=pair[1], pos1=2 ** 31 - 1, pos2=-2 ** 31, len1=-2 ** 31, perc=101, ord_="1")
+    rows = [row(**base, len2=x, p1=a, p2=b) for x in I32 for a in (0, 1) for b in (0, 1)]
+    rows += [dict(r, src="branching") for r in rows[::3]] + rows[::5]
+    return rows
+
+
+PRODUCT_LISTS = dict(id1=[7, 2 ** 31 - 1, 10 ** 10 - 1], id2=[9, 2 ** 32, 9999999990], pos1=[-2 ** 31, 0, 10 ** 9], pos2=[-1, 100000000, 240000000],
+                     ord_=ORDS, perc=[100, 99], len1=[1, 1000, 2000, -11, 2 ** 31 - 1], len2=[0, -2 ** 31], p1=[0, 1], p2=[0, 1])
+
+
+def product_rows():
+    """3^5 * 2 * 5 * 2 * 2 * 2 = 19 440 distinct lines, a seventh of them twice: more than one 2 048-element tile of the radix sort
+    with every one of the four key words decisive somewhere."""
+    import itertools
+    names = list(PRODUCT_LISTS)
+    rows = [row(**dict(zip(names, c))) for c in itertools.product(*PRODUCT_LISTS.values())]
+    return rows + rows[::7]
+
+
+# ---- R2: ids are labels ---------------------------------------------------------------------------------------------------------
+def relabel(inp, f, new_read_count):
+    """The same scenario with every new id sent through the injective map f (dense id -> label): the ids of the unvisited vertices
+    and of the super-reads (a visited vertex's id is never read).  Both input types."""
+    import copy
+    out = copy.copy(inp)
+    if isinstance(inp, F.Fno1Input):
+        out.nodes = inp.nodes.copy()
+        keep = inp.nodes["visited"] == 0
+        out.nodes["id"][keep] = [f[int(i)] for i in inp.nodes["id"][keep]]
+    out.srs = inp.srs.copy()
+    out.srs["id"] = [f[int(i)] for i in inp.srs["id"]]
+    out.new_read_count = new_read_count
+    return out
+
+
+def relabel_text(text, f, resort):
+    """overlaps.txt with columns 1 and 2 sent through f; FNO=1 writes a std::set (resort), FNO=3 in walk order."""
+    lines = []
+    for l in text.split(b"\n")[:-1]:
+        a, b, rest = l.split(b"\t", 2)
+        lines.append(b"%d\t%d\t%s\n" % (f[int(a)], f[int(b)], rest))
+    return b"".join(sorted(lines) if resort else lines)
+
+
+def labels(seed, n, bound, forced=(), hot=()):
+    """An injective map of the dense ids 0 .. n - 1 into [0, bound) that uses every label in `forced`; the largest of them goes to
+    the dense id hot[0], the next to hot[1] and so on, the others to ids drawn at random."""
+    rng = np.random.default_rng(seed)
+    forced = sorted({x for x in forced if x < bound}, reverse=True)
+    assert len(forced) <= n <= bound
+    pool = set(forced)
+    while len(pool) < n:
+        pool.add(int(rng.integers(0, bound)))
+    rest = sorted(pool - set(forced))
+    hot = [int(i) for i in hot][:len(forced)]
+    dense = hot + [int(i) for i in rng.permutation(n) if int(i) not in hot]
+    return dict(zip(dense, forced + [rest[i] for i in rng.permutation(len(rest))]))
+
+
+def pair_sort_shape(new_read_count):
+    """(id_bits, first bit of the topmost 8-bit pass of the sort over 2 * id_bits bits, m): the walk's key of a pair is
+    lo << id_bits | hi, and two pairs with one hi whose lo agree modulo 2^m differ in that topmost pass alone (m = 0: it holds
+    all of lo)."""
+    id_bits = max(1, (new_read_count - 1).bit_length())
+    top = 8 * ((2 * id_bits - 1) // 8)
+    return id_bits, top, max(0, top - id_bits)
+
+
+def top_pass_family(new_read_count, count):
+    """Up to `count` labels below new_read_count, the largest one among them, that agree modulo 2^m (pair_sort_shape)."""
+    m = pair_sort_shape(new_read_count)[2]
+    return [new_read_count - 1 - (k << m) for k in range(count) if new_read_count - 1 - (k << m) >= 0]
+
+
+def spread_vertices(inp, n_nodes, first, last, seed=0):
+    """The same FNO=1 scenario on n_nodes vertices: its vertices are dealt over [0, n_nodes) — `first` to 0, `last` to n_nodes - 1 —
+    and the others are unvisited vertices no edge touches, with the next new ids."""
+    import copy
+    rng = np.random.default_rng(seed)
+    old_n = len(inp.nodes)
+    others = [u for u in range(old_n) if u not in (first, last)]
+    g = np.zeros(old_n, np.uint64)
+    g[first], g[last] = 0, n_nodes - 1
+    g[others] = np.sort(rng.choice(np.arange(1, n_nodes - 1), size=len(others), replace=False))
+    out = copy.copy(inp)
+    out.nodes = np.zeros(n_nodes, F.FNO_READ_DTYPE)
+    out.nodes["len1"] = 100
+    out.nodes["orientation"] = 1
+    free = np.ones(n_nodes, bool)
+    free[g.astype(np.int64)] = False
+    out.nodes["id"][free] = inp.new_read_count + np.arange(n_nodes - old_n, dtype=np.uint64)
+    out.nodes[g.astype(np.int64)] = inp.nodes
+    out.new_read_count = inp.new_read_count + n_nodes - old_n
+    out.clique_nodes = g[inp.clique_nodes.astype(np.int64)]
+    out.subreads = inp.subreads.copy()
+    out.subreads["node"] = g[inp.subreads["node"].astype(np.int64)]
+    for name in ("graph_edges", "branching_edges", "nonedges", "inclusion_edges"):
+        e = getattr(inp, name).copy()
+        e["v1"], e["v2"] = g[e["v1"].astype(np.int64)], g[e["v2"].astype(np.int64)]
+        setattr(out, name, e)
+    out.graph_edges = out.graph_edges[np.argsort(out.graph_edges["v1"], kind="stable")]  # adj_out order again
+    return out

@@ -40,6 +40,7 @@ def _launch(torch, sc, cd, locality, monkeypatch):
     assert ", 0, true>" in info.split(" encoding=")[0], info
     d_in = torch.from_numpy(cd.view(np.uint8).reshape(-1).copy()).cuda()
     d_out = torch.full((cd.size * 24,), 0xA5, dtype=torch.uint8, device="cuda")  # a pattern: a record not written shows
+    torch.cuda.synchronize()  # the context's stream does not wait for torch's: the fill must have landed before the kernel writes
     sc.score_cands_device(d_in.data_ptr(), cd.size, d_out.data_ptr())
     sc.synchronize()
     return d_out.cpu().numpy().tobytes()
