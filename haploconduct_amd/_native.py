@@ -144,6 +144,34 @@ class hc_sr_next_counts(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class hc_br_threshold(C.Structure):  # include/hcsr.h: hc_br_reduce
+    _fields_ = [("dist", C.c_int32), ("min_evidence", C.c_int32)]
+
+
+class hc_br_reduce_settings(C.Structure):
+    _fields_ = [("careful", C.c_uint32), ("diploid", C.c_uint32), ("verbose", C.c_uint32), ("reserved", C.c_uint32), ("thresholds", C.c_void_p),
+                ("n_thresholds", C.c_uint64)]
+
+
+class hc_br_reduce_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_components", "n_component_edges", "n_false_dropped", "n_no_threshold", "n_careful_dropped", "n_kept", "n_removed",
+                                          "n_missing_appended", "n_items_sorted", "n_host_finished")] + \
+               [("ms_device", C.c_double), ("ms_host_walk", C.c_double), ("ms_copy", C.c_double), ("ms_sort", C.c_double), ("ms_edit", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class hc_br_reduce_tables(C.Structure):
+    _fields_ = [("components", C.c_void_p), ("cap_components", C.c_uint64), ("comp_edge", C.c_void_p), ("comp_unique", C.c_void_p),
+                ("cap_comp_edges", C.c_uint64), ("removed", C.c_void_p), ("cap_removed", C.c_uint64)]
+
+
+class hc_br_host_graph_out(C.Structure):
+    _fields_ = [("edges", C.c_void_p), ("cap_edges", C.c_uint64), ("out_off", C.c_void_p), ("in_nodes", C.c_void_p), ("in_off", C.c_void_p),
+                ("branching", C.c_void_p), ("cap_branching", C.c_uint64), ("n_edges", C.c_uint64), ("n_branching", C.c_uint64)]
+
+
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
 _sr_tail = [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, C.POINTER(hc_sr_stats)]

@@ -1,7 +1,8 @@
 """Read evidence for branching edges (include/hcsr.h: hc_br_* and the host mirror hc_host_br_evidence): the first half of
 BranchReduction::readBasedBranchReduction — findBranchingEvidence with buildDiffListOut, buildDiffListIn, findDiffPos and checkReadEvidence
 (reference src/BranchReduction.cpp:229-743), for every in-branch and then every out-branch (:60-80).  Structures, dtypes and the plumbing
-shared by EdgeScorer.br_* (device) and host.br_evidence (the mirror)."""
+shared by EdgeScorer.br_* (device) and host.br_evidence (the mirror).  Behind them the second half (:82-227, :745-1272): reduce() /
+reduce_fetch() on a context, host_reduce() (the mirror hc_host_br_reduce) and parse_thresholds()."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -168,3 +169,131 @@ def host_evidence(graph, reads, orig_off, entries, original_bases, original_seq_
         N.check(rc, "hc_host_br_evidence")
     a.pop("_stand_ins")
     return BranchEvidence(counts=dict(cn.as_dict(), some_failed=rc == SOME_FAILED), **a)
+
+
+# ---- the reduction: hc_br_reduce / hc_br_reduce_fetch / hc_host_br_reduce / hc_host_br_parse_thresholds ---------------------------------
+
+COMPONENT_DTYPE = np.dtype([("dist", "<i4"), ("min_evidence", "<i4"), ("outcome", "<u4"), ("host_finished", "<u4"), ("edge_first", "<u8"),
+                            ("edge_count", "<u4"), ("pad", "<u4")])
+assert COMPONENT_DTYPE.itemsize == 32
+THRESHOLD_DTYPE = np.dtype([("dist", "<i4"), ("min_evidence", "<i4")])
+
+RED_KEPT, RED_NOT_KEPT, RED_NO_THRESHOLD, RED_CAREFUL = range(4)        # HC_BR_RED_*
+RED_HOST_NO_ROW, RED_HOST_SHARED_EDGE, RED_HOST_DIPLOID = 1, 2, 4       # HC_BR_RED_HOST_*
+
+for _name, _args in (("hc_br_reduce", [_vp, C.POINTER(N.hc_br_reduce_settings), C.POINTER(N.hc_br_reduce_counts)]),
+                     ("hc_br_reduce_fetch", [_vp, C.POINTER(N.hc_br_reduce_tables)]),
+                     ("hc_host_br_reduce", [C.POINTER(hc_br_host_input), C.POINTER(hc_br_tables), C.POINTER(N.hc_br_reduce_settings),
+                                            C.POINTER(N.hc_br_reduce_counts), C.POINTER(N.hc_br_reduce_tables), C.POINTER(N.hc_br_host_graph_out)]),
+                     ("hc_host_br_parse_thresholds", [C.c_char_p, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+                     ("hc_host_br_map_order", [C.c_uint64, _vp])):
+    getattr(N.lib, _name).restype = C.c_int
+    getattr(N.lib, _name).argtypes = _args
+
+
+@dataclass
+class BranchReduction:
+    """The tables of one reduction, as include/hcsr.h: hc_br_reduce_tables describes them."""
+    components: np.ndarray   # COMPONENT_DTYPE, in branching_components order
+    comp_edge: np.ndarray    # uint32 (n, 2), component by component
+    comp_unique: np.ndarray  # uint32 per comp_edge row
+    removed: np.ndarray      # uint32 (n, 2): edges_to_remove, sorted and unique
+    counts: dict
+
+    def component_edges(self, i):
+        c = self.components[i]
+        return self.comp_edge[int(c["edge_first"]):int(c["edge_first"]) + int(c["edge_count"])]
+
+
+def reduce_settings(thresholds, careful=False, diploid=True):
+    """thresholds: {dist: min_evidence}, or an array of THRESHOLD_DTYPE (parse_thresholds' result).  Returns (settings, what it points into)."""
+    if isinstance(thresholds, dict):
+        t = np.array(sorted(thresholds.items()), np.int32).reshape(-1, 2).copy().view(THRESHOLD_DTYPE).reshape(-1)
+    else:
+        t = _c(thresholds, THRESHOLD_DTYPE)
+    return N.hc_br_reduce_settings(int(bool(careful)), int(bool(diploid)), 0, 0, _ptr(t), t.size), t
+
+
+def parse_thresholds(text):
+    """hc_host_br_parse_thresholds: the bytes of an evidence_threshold_table.tsv -> THRESHOLD_DTYPE in ascending dist.  A line std::stoi would
+    throw on raises HcError with .bad_line (1-based)."""
+    if isinstance(text, str):
+        text = text.encode()
+    n, bad = C.c_uint64(0), C.c_uint64(0)
+    out = np.zeros(text.count(b"\n") + 1, THRESHOLD_DTYPE)
+    rc = N.lib.hc_host_br_parse_thresholds(text, len(text), out.ctypes.data, out.size, C.byref(n), C.byref(bad))
+    if rc:
+        try:
+            N.check(rc, "hc_host_br_parse_thresholds")
+        except N.HcError as e:
+            e.bad_line = int(bad.value)
+            raise
+    return out[:n.value].copy()
+
+
+def map_order(n):
+    """hc_host_br_map_order: the iteration order of the library's std::unordered_map< node_id_t, bool > after inserting 0 .. n - 1."""
+    out = np.zeros(max(n, 1), np.uint64)
+    N.check(N.lib.hc_host_br_map_order(n, out.ctypes.data), "hc_host_br_map_order")
+    return out[:n].tolist()
+
+
+def _reduce_tables(n_components, n_comp_edges, n_removed):
+    a = dict(components=np.zeros(max(n_components, 1), COMPONENT_DTYPE), comp_edge=np.zeros((max(n_comp_edges, 1), 2), np.uint32),
+             comp_unique=np.zeros(max(n_comp_edges, 1), np.uint32), removed=np.zeros((max(n_removed, 1), 2), np.uint32))
+    t = N.hc_br_reduce_tables(a["components"].ctypes.data, a["components"].size, a["comp_edge"].ctypes.data, a["comp_unique"].ctypes.data,
+                              a["comp_unique"].size, a["removed"].ctypes.data, a["removed"].shape[0])
+    return a, t
+
+
+def _reduction(a, cn):
+    return BranchReduction(a["components"][:cn.n_components].copy(), a["comp_edge"][:cn.n_component_edges].copy(),
+                           a["comp_unique"][:cn.n_component_edges].copy(), a["removed"][:cn.n_removed].copy(), cn.as_dict())
+
+
+def reduce(ctx, settings):
+    """hc_br_reduce on a context -> (counts as a dict, the counts structure)."""
+    st, keep = settings
+    cn = N.hc_br_reduce_counts()
+    N.check(N.lib.hc_br_reduce(ctx, C.byref(st), C.byref(cn)), "hc_br_reduce")
+    del keep
+    return cn.as_dict(), cn
+
+
+def reduce_fetch(ctx, cn):
+    a, t = _reduce_tables(cn.n_components, cn.n_component_edges, cn.n_removed)
+    N.check(N.lib.hc_br_reduce_fetch(ctx, C.byref(t)), "hc_br_reduce_fetch")
+    return _reduction(a, cn)
+
+
+def host_reduce(graph, reads, ev, settings):
+    """hc_host_br_reduce: the mirror.  graph: a dict as EdgeScorer.graph_fetch returns it; reads: a ReadSet; ev: a BranchEvidence; settings:
+    reduce_settings(...).  Returns (BranchReduction, the reduced graph as such a dict, the records appended to branching_edges)."""
+    from .host import EDGE_DTYPE
+
+    st, keep_t = settings
+    keep = dict(edges=_c(graph["edges"], EDGE_DTYPE), out_off=_c(graph["out_off"], np.uint64), in_nodes=_c(graph["in_nodes"], np.uint32),
+                in_off=_c(graph["in_off"], np.uint64), bases=_c(reads.bases, np.uint8), seq_off=_c(reads.seq_off, np.uint64),
+                read_first_seq=_c(reads.read_first_seq, np.uint32))
+    V, E = keep["out_off"].size - 1, keep["edges"].size
+    inp = hc_br_host_input()
+    for k, v in keep.items():
+        setattr(inp, k, _ptr(v))
+    for k in ("out_off", "in_off", "seq_off", "read_first_seq"):
+        setattr(inp, k, keep[k].ctypes.data)
+    inp.n_vertices, inp.n_reads = V, reads.n_reads
+    tk = dict(branches=_c(ev.branches, BRANCH_DTYPE), branch_nb=_c(ev.branch_nb, np.uint32), ev_edge=_c(ev.ev_edge, np.uint32), ev_off=_c(ev.ev_off, np.uint64),
+              ev_ids=_c(ev.ev_ids, np.uint32), missing_edges=_c(ev.missing_edges, EDGE_DTYPE))
+    n_rows = tk["ev_off"].size - 1
+    t = hc_br_tables(_ptr(tk["branches"]), tk["branches"].size, _ptr(tk["branch_nb"]), tk["branch_nb"].size, None, 0, _ptr(tk["ev_edge"]),
+                     tk["ev_off"].ctypes.data, n_rows, _ptr(tk["ev_ids"]), tk["ev_ids"].size, _ptr(tk["missing_edges"]), tk["missing_edges"].size)
+    a, rt = _reduce_tables(tk["branches"].size, tk["branch_nb"].size, tk["branch_nb"].size)  # the upper bounds: one call
+    g = dict(edges=np.zeros(max(E, 1), EDGE_DTYPE), out_off=np.zeros(V + 1, np.uint64), in_nodes=np.zeros(max(E, 1), np.uint32), in_off=np.zeros(V + 1, np.uint64))
+    br = np.zeros(max(E + tk["missing_edges"].size, 1), EDGE_DTYPE)
+    go = N.hc_br_host_graph_out(g["edges"].ctypes.data, g["edges"].size, g["out_off"].ctypes.data, g["in_nodes"].ctypes.data, g["in_off"].ctypes.data,
+                                br.ctypes.data, br.size, 0, 0)
+    cn = N.hc_br_reduce_counts()
+    N.check(N.lib.hc_host_br_reduce(C.byref(inp), C.byref(t), C.byref(st), C.byref(cn), C.byref(rt), C.byref(go)), "hc_host_br_reduce")
+    del keep_t
+    g["edges"], g["in_nodes"] = g["edges"][:go.n_edges].copy(), g["in_nodes"][:go.n_edges].copy()
+    return _reduction(a, cn), g, br[:go.n_branching].copy()

@@ -378,6 +378,7 @@ static void clean_commit(hc_ctx::Graph& g, const hc::trans::Graph& out) {
     g.in_off.swap(g.in_off_next);
     g.n_edges = out.E;
     g.n_tied = 0;  // the lists are in the reference's order now
+    g.edits++;
 }
 
 int hc_graph_remove_inclusions(hc_ctx* c, hc_clean_counts* counts) {
@@ -487,6 +488,39 @@ static int commit_removed(hc_ctx* c, const char* who, const hc::trans::Graph& in
     clean_commit(g, out);
     return HC_OK;
 }
+
+}  // extern "C"
+
+// hc_br_reduce's edit (hc_api_br.cpp): n_missing records of d_missing are appended to branching_edges, then the listed records leave the
+// graph with their adj_in entries and follow them (src/BranchReduction.cpp:83-85, :217-225).  rec / in_pos on the device, checked by the
+// caller: distinct, below the graph's edges.
+int hc::graph_remove_records(hc_ctx* c, const char* who, const uint32_t* d_rec, const uint32_t* d_in_pos, uint64_t n, const hc_edge_rec* d_missing,
+                             uint64_t n_missing) {
+    hc_ctx::Graph& g = c->graph;
+    c->graph_text.drop();
+    int rc = grow_keeping(g.branching, g.n_branching * sizeof(hc_edge_rec), (g.n_branching + n_missing + n + 1) * sizeof(hc_edge_rec), c->stream);
+    if (rc) return rc;
+    hc::trans::Graph in, out;
+    if (g.n_edges && (rc = clean_prepare(c, in, out))) return rc;
+    if (n_missing)
+        HC_HIP(hipMemcpyAsync(g.branching.as<hc_edge_rec>() + g.n_branching, d_missing, n_missing * sizeof(hc_edge_rec), hipMemcpyDeviceToDevice, c->stream));
+    g.n_branching += n_missing;
+    if (!g.n_edges) {
+        HC_HIP(hipStreamSynchronize(c->stream));
+        return n ? fail(HC_ERR_ARG, std::string(who) + ": records to remove from a graph without edges") : HC_OK;
+    }
+    const hipError_t e = hc::trans::remove_records(in, out, d_rec, d_in_pos, (uint32_t)n, g.branching.as<hc_edge_rec>() + g.n_branching, g.clean_temp.p,
+                                                   g.clean_temp.cap, c->stream);
+    if (e != hipSuccess) {
+        g.valid = false;
+        return fail(HC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    g.n_branching += n;
+    clean_commit(g, out);
+    return HC_OK;
+}
+
+extern "C" {
 
 int hc_graph_remove_tips(hc_ctx* c, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts) {
     if (!c || !counts || (n_reads && !reads)) return fail(HC_ERR_ARG, "hc_graph_remove_tips: null argument");

@@ -123,5 +123,51 @@ hipError_t launch_ev_edges(const In& I, const Work& W, hipStream_t s);          
 hipError_t launch_missing(const In& I, const Work& W, hipStream_t s);                  // n_p lanes
 hipError_t launch_assemble(const Work& W, hipStream_t s);                              // n_b lanes
 
+
+// ---- hc_br_reduce (hc_br_reduce_kernels.hip) --------------------------------------------------------------------------------------------
+// A COMPONENT EDGE e: edge k of component c at cm_first[c] + k (the host's CSR of branching_components).  An ITEM i: id k of component edge
+// e at ce_off[e] + k.  A ROW: an edge of the evidence tables (t_ev_edge, ascending (u, v)).
+enum { kRedBadRead = 0, kRedBadId, kRedNotFound, kRedCounters = 4 };
+constexpr uint32_t kNoRow = 0xffffffffu;
+
+struct Red {
+    // per final_branch neighbour (n_nb): the slot it was gathered from, its record; out: len1, len2, overlap len0
+    const uint32_t *nb_sel, *sl_rec;
+    int32_t* tri;
+    uint64_t n_nb;
+    // the evidence tables
+    const uint32_t* ev_edge;
+    const uint64_t* ev_off;
+    const uint32_t* ev_ids;
+    uint64_t n_rows;
+    // per component edge (n_ce; ce_len n_ce + 1 with its exclusive sum in ce_off)
+    uint32_t *ce_u, *ce_v, *ce_comp, *ce_row, *ce_count;
+    uint64_t *ce_len, *ce_off;
+    uint8_t* ce_remove;
+    uint64_t n_ce;
+    // per component (n_c; cm_first n_c + 1)
+    uint64_t* cm_first;
+    int32_t* cm_minev;
+    uint8_t *cm_no_row, *cm_keep;
+    uint64_t n_c;
+    // per item (n_items; uniq n_items + 1, summed in place)
+    uint64_t *key_in, *key, *uniq;
+    uint32_t *val_in, *val;
+    uint64_t n_items, id_limit;  // id_limit = 2 * original_readcount: every id is below it
+    int id_bits;
+    // per removed pair (n_rm): out: its record and its adj_in entry
+    uint32_t *rm_u, *rm_v, *rm_rec, *rm_in;
+    uint64_t n_rm;
+    unsigned long long* counters;
+};
+
+hipError_t launch_red_triples(const Graph& g, const Store& st, const Red& R, hipStream_t s);  // n_nb lanes
+hipError_t launch_red_rows(const Red& R, hipStream_t s);                                     // n_ce lanes
+hipError_t launch_red_keys(const Red& R, hipStream_t s);                                     // n_items lanes
+hipError_t launch_red_unique(const Red& R, hipStream_t s);                                   // n_items lanes
+hipError_t launch_red_counts(const Red& R, hipStream_t s);                                   // n_ce lanes
+hipError_t launch_red_decide(const Red& R, hipStream_t s);                                   // n_c lanes
+hipError_t launch_red_find(const Graph& g, const Red& R, hipStream_t s);                     // n_rm waves
+
 }  // namespace br
 }  // namespace hc

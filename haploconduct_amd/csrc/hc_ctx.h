@@ -225,6 +225,7 @@ struct hc_ctx {
         uint64_t n_branching = 0, n_tip_reads = 0;
         uint64_t n_vertices = 0, n_edges = 0, n_tied = 0;
         uint64_t n_appended = 0;  // records hc_graph_append has put into adm
+        uint64_t edits = 0;       // cleaning calls that replaced the lists (what hc_br_reduce checks its tables against)
         bool valid = false;
         // hc_graph_append copies through two page-locked buffers on the context's stream and does not wait for the copy
         hc_scratch h_stage[2] = {hc_scratch(hipHostMallocDefault), hc_scratch(hipHostMallocDefault)};
@@ -351,11 +352,22 @@ struct hc_ctx {
         hc_scratch t_branches, t_nb, t_diff, t_ev_edge, t_ev_off, t_ev_ids, t_missing;
         hc_br_counts counts{};
         bool valid = false;
-        void drop() { valid = false; }
+        // hc_br_reduce: what of hc_br_evidence's work it reads (the slots' records, the kept slots; valid with the tables and while the
+        // graph has not been edited since), its own carved block and page-locked staging, and its tables for hc_br_reduce_fetch (host)
+        const uint32_t *sl_rec = nullptr, *nb_sel = nullptr;
+        uint64_t graph_edits = 0, settings_orc = 0;
+        hc_scratch red_work, red_pin = hc_scratch(hipHostMallocDefault);
+        std::vector<hc_br_component> red_comps;
+        std::vector<uint32_t> red_comp_edge, red_comp_unique, red_removed;
+        bool red_valid = false;
+        void drop() { valid = false, red_valid = false; }
     } br;
 };
 
 namespace hc {
+// hc_api_stage.cpp: the graph edit of hc_br_reduce
+int graph_remove_records(hc_ctx* c, const char* who, const uint32_t* d_rec, const uint32_t* d_in_pos, uint64_t n, const hc_edge_rec* d_missing,
+                         uint64_t n_missing);
 // hc_api_sr.cpp: hc_sr_consensus in parts, for the calls whose layouts are on the device already (hc_api_sr_edge.cpp).
 // hc_sr_consensus = its own checks + sr_consensus_begin + sr_consensus_room + the upload of layouts and members + sr_consensus_run.
 // `me` prefixes the error texts.  *ret_late (may be NULL): a layout failed late and its ret is no longer the device's.

@@ -48,6 +48,11 @@ hipError_t find_tips(const Graph& in, uint32_t max_tip_len, const hc_read_geom* 
 hipError_t find_branches(const Graph& in, hc_branch_counts* counts, void* temp, size_t temp_bytes, hipStream_t s);
 hipError_t commit_removed(const Graph& in, Graph& out, bool target_ordered, hc_edge_rec* removed, uint64_t n_removed, void* temp, size_t temp_bytes,
                           hipStream_t s);
+// OverlapGraph::removeEdge for n listed records (hc_br_reduce): the records rec[k] of `in` (distinct) leave with the adj_in entries in_pos[k]
+// (distinct); removed[k] = record rec[k], and the rest goes to `out` with both lists in the order they had (the compaction of
+// commit_removed).  in.E > 0.
+hipError_t remove_records(const Graph& in, Graph& out, const uint32_t* rec, const uint32_t* in_pos, uint32_t n, hc_edge_rec* removed, void* temp,
+                          size_t temp_bytes, hipStream_t s);
 // sortAdjOut alone (hc_br_evidence): the records and seq of `in` in sortAdjOut's order — the target-order step of find_branches, its host
 // step for lists that repeat a target included — into out.edges / out.seq (room for in.E).  The order changes inside lists only: the
 // offsets and adj_in are not touched.  in.E > 0.

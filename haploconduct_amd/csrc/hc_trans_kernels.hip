@@ -1092,6 +1092,32 @@ hipError_t commit_removed(const Graph& g, Graph& out, bool target_ordered, hc_ed
     return hipSuccess;
 }
 
+__global__ void k_drop_listed(const uint32_t* __restrict__ rec, const uint32_t* __restrict__ in_pos, uint32_t n, const hc_edge_rec* __restrict__ E,
+                              uint8_t* __restrict__ keep, uint8_t* __restrict__ in_keep, hc_edge_rec* __restrict__ removed) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        keep[rec[i]] = 0;
+        in_keep[in_pos[i]] = 0;
+        removed[i] = E[rec[i]];
+    }
+}
+
+hipError_t remove_records(const Graph& g, Graph& out, const uint32_t* rec, const uint32_t* in_pos, uint32_t n, hc_edge_rec* removed, void* temp,
+                          size_t temp_bytes_, hipStream_t s) {
+    Carve c{(char*)(((uintptr_t)temp + 255) & ~(uintptr_t)255)};
+    const Work w = layout(c, g.E, g.V);
+    if (c.used + 256 > temp_bytes_ || !g.E || n > g.E) return hipErrorInvalidValue;
+    TRY(hipMemsetAsync(w.counters, 0, 8 * sizeof(unsigned long long), s));
+    TRY(hipMemsetAsync(w.keep, 1, g.E, s));
+    TRY(hipMemsetAsync(w.in_keep, 1, g.E, s));
+    hipLaunchKernelGGL(k_owner, grid_for(g.E), dim3(kBlock), 0, s, g.out_off, g.V, g.E, w.src, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_owner, grid_for(g.E), dim3(kBlock), 0, s, g.in_off, g.V, g.E, w.in_owner, (uint32_t*)nullptr);
+    if (n) hipLaunchKernelGGL(k_drop_listed, grid_for(n), dim3(kBlock), 0, s, rec, in_pos, n, g.edges, w.keep, w.in_keep, removed);
+    TRY(hipGetLastError());
+    TRY(emit(g, out, w.keep, nullptr, w.in_keep, w, s));
+    if ((uint64_t)g.E - n != out.E) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
 __global__ void k_permute_records(const uint32_t* __restrict__ perm, uint32_t n, const hc_edge_rec* __restrict__ E, const uint32_t* __restrict__ seq,
                                   hc_edge_rec* __restrict__ E_out, uint32_t* __restrict__ seq_out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {

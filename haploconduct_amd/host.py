@@ -599,3 +599,11 @@ def br_evidence(graph, reads, orig_off, entries, original_bases, original_seq_of
     from . import branch_evidence as BR
 
     return BR.host_evidence(graph, reads, orig_off, entries, original_bases, original_seq_off, vertex_read, vertex_fwd, settings, n_threads)
+
+
+def br_reduce(graph, reads, evidence, settings):
+    """hc_host_br_reduce: the host mirror of EdgeScorer.br_reduce (src/BranchReduction.cpp:82-227, :745-1272) on a graph as graph_fetch returns
+    it, a ReadSet and a branch_evidence.BranchEvidence -> (BranchReduction, the reduced graph, the records appended to branching_edges)."""
+    from . import branch_evidence as BR
+
+    return BR.host_reduce(graph, reads, evidence, settings)

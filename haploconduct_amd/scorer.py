@@ -235,6 +235,22 @@ class EdgeScorer:
         cn = getattr(self, "_br_counts", None)
         return BR.fetch(self._ctx, cn if cn is not None else BR.hc_br_counts())
 
+    def br_reduce(self, settings):
+        """hc_br_reduce: the second half of readBasedBranchReduction (src/BranchReduction.cpp:82-227, :745-1272) on the tables of the last
+        br_evidence: the device graph loses edges_to_remove, branching_edges gains the missing edges and the removed records.  settings:
+        branch_evidence.reduce_settings(...).  Returns the counts (a dict); br_reduce_fetch returns the tables."""
+        from . import branch_evidence as BR
+
+        d, self._br_reduce_counts = BR.reduce(self._ctx, settings)
+        return d
+
+    def br_reduce_fetch(self):
+        """hc_br_reduce_fetch: the tables of the last br_reduce as a branch_evidence.BranchReduction."""
+        from . import branch_evidence as BR
+
+        cn = getattr(self, "_br_reduce_counts", None)
+        return BR.reduce_fetch(self._ctx, cn if cn is not None else N.hc_br_reduce_counts())
+
     def sr_fastq_text(self, tips=None, vertex_read=None):
         """hc_sr_fastq_write_text + hc_sr_fastq_text_fetch: the bytes of singles.fastq, paired1.fastq and paired2.fastq for the current store
         and of removed_tip_sequences.fastq for the tips of the last sr_merge_next (its .tips and the vertex_read it took), as written by

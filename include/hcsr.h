@@ -918,8 +918,9 @@ int hc_host_sr_originals_parse(const char* text, uint64_t n_bytes, uint64_t* ori
  * checkReadEvidence (:229-743), called for every in-branch and then every out-branch (:60-80) — reads the cleaned graph, the store's
  * sequences, the original-read index maps and the reads of --original_fastq, and every result of it is independent of hash iteration
  * order because the lists are sorted before use.  hc_br_evidence computes it on the device from what the context holds.  The second half
- * (findBranchingComponents, countUniqueEvidence, the threshold file and the removals, :745-1272) walks unordered_maps in iteration
- * order, and under --careful its result depends on that order: it stays with the caller, who fetches the tables below.
+ * (findBranchingComponents, countUniqueEvidence, the threshold file and the removals, :82-227 and :745-1272) is hc_br_reduce, the
+ * section behind this one: it walks unordered_maps in iteration order, and its result depends on that order, so that walk runs on the
+ * host in real libstdc++ maps and only the order-free part — the unique-evidence filter and the graph edit — runs on the device.
  *
  * A branch is a vertex with more than one in-neighbour (side HC_BR_IN) or more than one out-neighbour (HC_BR_OUT); its neighbours are
  * sortAdjLists(adj_in) / sortAdjOut(adj_out) (:47-48), ascending.  The edge of a neighbour is getEdgeInfo's: the FIRST record
@@ -1069,6 +1070,163 @@ typedef struct hc_br_host_input {
 } hc_br_host_input; /* 128 bytes */
 int hc_host_br_evidence(const hc_br_host_input* in, const hc_br_settings* settings, hc_br_counts* counts, hc_br_tables* tables,
                         uint32_t n_threads);
+
+/* ---- the reduction: the second half of BranchReduction::readBasedBranchReduction ------------------------------------------------
+ *
+ * hc_br_reduce runs src/BranchReduction.cpp:82-227 with findBranchingComponents, extendComponentOut / In and countUniqueEvidence
+ * (:745-1272) on the tables the last hc_br_evidence left on the device, and edits the device graph in place like every other cleaning
+ * call: POLYTE's branch step is hc_br_evidence, hc_br_reduce and nothing else.
+ *
+ * What depends on unordered_map iteration order is small and serial and runs on the HOST, in std::unordered_map< node_id_t, ... >
+ * objects that receive the reference's inserts in the reference's order (:753-781): which in-branch starts a component, the depth-first
+ * walk, `dist` (:806-833, :906-925: from the starting branch and the last top-level neighbour the walk extended), the order of
+ * branching_components that the --careful chain (:163-204) reads, and the tie order of the diploid rule's at most four (mapID, count)
+ * pairs (:1100-1122).  THE RESULT IS THEREFORE PINNED TO libstdc++'s std::unordered_map (its bucket counts, its rehash points, its
+ * insertion at the front of the element list): built against another standard library the call still follows the cited lines, but
+ * tests/golden/branch_reduce.json — its recorded iteration order for keys 0..40 first — would have to be recorded again from a
+ * reference built with that library.
+ * What is large does not depend on order and runs on the DEVICE.  countUniqueEvidence's filter (:1053-1096) pops, per round, every front
+ * equal to the minimum and keeps it only where exactly one list had it; the lists ascend without repeats, so the count of an edge is the
+ * number of its ids that occur in NO OTHER LIST OF THE SAME COMPONENT: one stable radix sort of component | id over the ids of all
+ * component edges, a comparison with both neighbours, a sum per edge.
+ *
+ * As the reference has it:
+ *  - a branch whose nb_count is 0 is no branch here (:762, :773); a component that holds a false branch is not listed: all its edges are
+ *    removed (:849-855, :928-932);
+ *  - len1 / len2 of :815-816 / :910-911 are Read::get_len() of the record's read1 / read2 (both mates of a paired read), the record is
+ *    getEdgeInfo's: the first outnode -> node in target order;
+ *  - every kept neighbour of a skipped component appends the component once more (:172-177: continue, not break); the list is sorted
+ *    and de-duplicated afterwards (:206-207), so this shows in no result;
+ *  - the diploid rule sorts its pairs with std::sort by count alone (:1104): for four entries that is an insertion sort, ties stay in
+ *    the map's iteration order; :1164 compares pairs.at(0) - pairs.at(1), the two SMALLEST counts, with 0.5 * min_evidence;
+ *  - countUniqueEvidence consumes evidence_per_edge (pop_front, :1088), so a later component would find the list of a shared edge
+ *    empty.  No edge lies in two listed components: a branch is in one component, and the walk that reaches the branch at one end of an
+ *    edge goes on to the branch at the other end (the trailing out-branches of :882 are those no in-branch lists).  The call looks for
+ *    such an edge all the same (one sort of the component edges, on the host in the walk; of the marks only the no-row one is a kernel's) and would finish its components on the host from the lists themselves;
+ *  - a component edge without a key in evidence_per_edge (:1029-1031, also unreachable from hc_br_evidence's tables) shortens
+ *    evidence_status, so that index k of it no longer belongs to edge k.  Where the reference then calls at() on the missing key, front()
+ *    on an empty list or max_element on an empty vector, the call returns HC_ERR_ARG; otherwise it goes on as the reference does.
+ * OverlapGraph::removeEdge (src/OverlapGraph.cpp:104-147) erases the FIRST record u -> v in list order — the graph is in target order,
+ * so the first of the run of equal targets — and the FIRST entry u of adj_in[v] in adj_in's own order; edges_to_remove holds a pair
+ * once, so of a repeated (u, v) exactly one record leaves and its twins stay.  adj_in keeps its order otherwise.  checkEdge's assert on
+ * the score (:242) is not restated. */
+
+typedef struct hc_br_threshold {
+    int32_t dist;         /* field 1 of a line of evidence_threshold_table.tsv */
+    int32_t min_evidence; /* field 3                                           */
+} hc_br_threshold; /* 8 bytes */
+
+typedef struct hc_br_reduce_settings {
+    uint32_t careful; /* program_settings.careful                                                                      */
+    uint32_t diploid; /* program_settings.diploid                                                                      */
+    uint32_t verbose; /* 0: reserved (the reference's prints are not made)                                             */
+    uint32_t reserved;
+    const hc_br_threshold* thresholds; /* evidence_threshold_map (:134-155); a later entry for the same dist wins       */
+    uint64_t n_thresholds;             /* 0: HC_ERR_ARG, the exit(1) of :157                                            */
+} hc_br_reduce_settings; /* 32 bytes */
+
+/* What became of a listed component in the chain of :163-204. */
+enum {
+    HC_BR_RED_KEPT = 0,         /* countUniqueEvidence returned true: the component is in components_kept           */
+    HC_BR_RED_NOT_KEPT = 1,     /* it returned false                                                                */
+    HC_BR_RED_NO_THRESHOLD = 2, /* evidence_threshold_map has no entry for dist: all edges removed (:193-201)       */
+    HC_BR_RED_CAREFUL = 3       /* a neighbouring component was kept earlier: all edges removed (:172-177)          */
+};
+/* Why the host finished a component (bits; 0: the device's counts and its general rule decided it). */
+enum { HC_BR_RED_HOST_NO_ROW = 1, HC_BR_RED_HOST_SHARED_EDGE = 2, HC_BR_RED_HOST_DIPLOID = 4 };
+
+typedef struct hc_br_component {
+    int32_t dist;
+    int32_t min_evidence;   /* -1: no threshold entry, or not looked up (HC_BR_RED_CAREFUL)                          */
+    uint32_t outcome;       /* HC_BR_RED_*                                                                           */
+    uint32_t host_finished; /* HC_BR_RED_HOST_* bits; the mirror sets the same bits for the same components         */
+    uint64_t edge_first;    /* comp_edge[edge_first, edge_first + edge_count): sorted, unique (:837-847)             */
+    uint32_t edge_count;
+    uint32_t pad;           /* 0 */
+} hc_br_component; /* 32 bytes */
+
+typedef struct hc_br_reduce_counts {
+    uint64_t n_components;       /* branching_components                                                              */
+    uint64_t n_component_edges;  /* their edges                                                                       */
+    uint64_t n_false_dropped;    /* components dropped for a false branch (:849-855, :928-932)                        */
+    uint64_t n_no_threshold;     /* HC_BR_RED_NO_THRESHOLD                                                            */
+    uint64_t n_careful_dropped;  /* HC_BR_RED_CAREFUL                                                                 */
+    uint64_t n_kept;             /* HC_BR_RED_KEPT                                                                    */
+    uint64_t n_removed;          /* edges_to_remove after :206-207 = records that left the graph                      */
+    uint64_t n_missing_appended; /* missing_edges appended to branching_edges (:83-85)                                */
+    uint64_t n_items_sorted;     /* evidence ids of all component edges (device call: the radix sort's items)         */
+    uint64_t n_host_finished;    /* components with host_finished != 0                                                */
+    double ms_device;            /* device call only: kernels, sort, sums and the edit by events                      */
+    double ms_host_walk;         /* device call only: the component walk and the chain, by the host's clock           */
+    double ms_copy;              /* device call only: waiting for the copies between host and device                  */
+    double ms_sort;              /* device call only: the radix sort's share of ms_device                             */
+    double ms_edit;              /* device call only: the edit's share of ms_device (the pairs' records, compaction)   */
+} hc_br_reduce_counts; /* 120 bytes */
+
+/* Count, then fetch: every pointer may be NULL (not wanted); a wanted table whose cap is below its count: HC_ERR_ARG, nothing copied.
+ *   components   in branching_components order
+ *   comp_edge    pairs u, v (2 * cap_comp_edges entries), component by component
+ *   comp_unique  per comp_edge entry its unique-evidence count (unique_evidence_per_edge's list length); 0 for a component
+ *                countUniqueEvidence was not called for (HC_BR_RED_NO_THRESHOLD, HC_BR_RED_CAREFUL)
+ *   removed      edges_to_remove after sort and unique, pairs u, v (2 * cap_removed entries) */
+typedef struct hc_br_reduce_tables {
+    hc_br_component* components;
+    uint64_t cap_components;
+    uint32_t* comp_edge;
+    uint32_t* comp_unique;
+    uint64_t cap_comp_edges;
+    uint32_t* removed;
+    uint64_t cap_removed;
+} hc_br_reduce_tables; /* 56 bytes */
+
+/* The file loop of :137-155 on the bytes of an evidence_threshold_table.tsv: lines end at '\n' (getline); an empty line or one that
+ * starts with '#' is skipped; fields are split at tabs, field 1 is dist and field 3 min_evidence, each read as std::stoi reads it
+ * (leading white space, a sign, digits; what follows the digits is ignored); a later line for the same dist wins.  out: room for cap
+ * entries, in ascending dist; *n is always the number of distinct dists (count, then fetch: HC_ERR_ARG with nothing copied where cap is
+ * too small or out is NULL).  A line std::stoi would throw on — no digits, a missing third field, a value outside int —: HC_ERR_ARG and
+ * *bad_line = its 1-based number.  bad_line may be NULL. */
+int hc_host_br_parse_thresholds(const char* text, uint64_t len, hc_br_threshold* out, uint64_t cap, uint64_t* n, uint64_t* bad_line);
+
+/* HC_ERR_STATE unless the tables of the last hc_br_evidence are still valid (hc_br_evidence_fetch's conditions) and the store it read is
+ * still the context's.  HC_ERR_ARG: a null argument, an empty threshold table, tables the reference would end on (above).
+ * In order: missing_edges are appended to the device's branching_edges (:83-85); the components, the unique evidence, the decisions;
+ * edges_to_remove sorted and de-duplicated (:206-207); those records leave the device graph and are appended to branching_edges in that
+ * (u, v) order (:217-225).  The graph stays in the target order hc_br_evidence left it in, and hc_graph_fetch,
+ * hc_graph_fetch_branching_edges, hc_graph_write_text, hc_graph_merge_pairs, hc_sr_clique_merge and hc_fno1_run work on it as they do
+ * after hc_graph_remove_branches.  The evidence tables are spent afterwards: a second hc_br_reduce or an hc_br_evidence_fetch returns
+ * HC_ERR_STATE; hc_br_reduce_fetch serves until the next hc_br_evidence, hc_graph_load / hc_graph_resolve, hc_set_reads or hc_reset.
+ * A pair of edges_to_remove without a record in the graph (the exit(1) of :219-222, :1252-1257; unreachable from hc_br_evidence's
+ * tables): HC_ERR_ARG, the graph and branching_edges untouched, the tables spent.
+ * A fixed number of launches whatever the degrees and list sizes: a lane per final_branch neighbour for (len1, len2,
+ * overlap len0) of its record; the host's walk; a lane per component edge for its row of ev_edge (bisection) and its list length, one
+ * exclusive sum, a lane per evidence item for the key component << id bits | id (only the bits in use are sorted), one stable radix
+ * sort, a lane per sorted item against both neighbours, one exclusive sum and a lane per edge for its count, a lane per component for
+ * the general rule of :1243-1271; the host's chain; a wave per removed pair for its record (bisection) and its adj_in entry (the first
+ * match by ballot), then the compaction hc_graph_remove_branches uses. */
+int hc_br_reduce(hc_ctx* ctx, const hc_br_reduce_settings* settings, hc_br_reduce_counts* counts);
+/* The tables of the last hc_br_reduce (cap_* in the struct).  HC_ERR_STATE: none kept. */
+int hc_br_reduce_fetch(hc_ctx* ctx, hc_br_reduce_tables* tables);
+
+/* The same on the host (no device, no context): the mirror and the yardstick, the reference statement by statement on one thread.
+ * in: the graph and the store as hc_host_br_evidence takes them (adj_out in any order: the mirror sorts a copy as sortAdjOut does; the
+ * dict and the original reads are not read); ev: tables as hc_br_evidence_fetch / hc_host_br_evidence fill them, cap_* = their counts.
+ * counts is always filled.  tables and graph may be NULL; count, then fetch — or one call with room for the upper bounds: components <=
+ * branches, component edges and removed pairs <= branch_nb entries, edges <= the graph's, branching <= missing + the graph's edges. */
+typedef struct hc_br_host_graph_out {
+    hc_edge_rec* edges;   /* the reduced graph in target order                        */
+    uint64_t cap_edges;
+    uint64_t* out_off;    /* n_vertices + 1                                           */
+    uint32_t* in_nodes;   /* room for cap_edges                                       */
+    uint64_t* in_off;     /* n_vertices + 1                                           */
+    hc_edge_rec* branching; /* what the call appends to branching_edges, in order     */
+    uint64_t cap_branching;
+    uint64_t n_edges, n_branching; /* always filled                                   */
+} hc_br_host_graph_out; /* 72 bytes */
+int hc_host_br_reduce(const hc_br_host_input* in, const hc_br_tables* ev, const hc_br_reduce_settings* settings, hc_br_reduce_counts* counts,
+                      hc_br_reduce_tables* tables, hc_br_host_graph_out* graph);
+/* std::unordered_map< node_id_t, bool > filled with keys 0 .. n - 1 ascending: its iteration order into order (room for n).  What the
+ * host's walk depends on, for tests that pin it. */
+int hc_host_br_map_order(uint64_t n, uint64_t* order);
 
 /* ---- singles.fastq, paired1.fastq, paired2.fastq and removed_tip_sequences.fastq from the device ----------------------------
  *
