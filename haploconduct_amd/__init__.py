@@ -12,3 +12,4 @@ from ._native import HcError, lib, lib_path, device_count, version  # noqa: F401
 from .records import OVERLAP_DTYPE, RESULT_DTYPE, Settings, CLS_NAMES  # noqa: F401
 from .readstore import ReadSet  # noqa: F401
 from .scorer import EdgeScorer  # noqa: F401
+from . import cliques  # noqa: F401

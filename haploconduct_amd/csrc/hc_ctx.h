@@ -241,6 +241,16 @@ struct hc_ctx {
         bool valid = false;
         void drop() { valid = false, n_bytes = 0; }
     } graph_text;
+    // hc_graph_cliques / hc_graph_cliques_fetch (hc_api_cliques.cpp): grow-only scratch — the pair keys and the rank keys (two blocks
+    // each, the sorts' in and out), the simple adjacency (off, nbr, rank, order, kind), the roots' counts and their sums, the counters,
+    // the prims' workspace, the waves' slices — and the CSR, kept until the next hc_graph_cliques or the next call that replaces or
+    // edits the graph (drop())
+    struct Cliques {
+        hc_scratch keys_a, keys_b, rank_a, rank_b, off, nbr, rank, order, kind, cnt_c, cnt_e, counters, temp, slices, clique_off, clique_nodes;
+        uint64_t n_cliques = 0, n_entries = 0;
+        bool valid = false;
+        void drop() { valid = false, n_cliques = n_entries = 0; }
+    } cliques;
     // The consensus tables of one call path on the device (hc_api_sr.cpp: sr_tables): the log10 terms by term index, q_of itself, the
     // table of one- and two-member columns — and what they were built for.
     struct SrTables {

@@ -571,6 +571,14 @@ class EdgeScorer:
             N.check(N.lib.hc_graph_text_fetch(self._ctx, first, n, _ptr(out[first:first + n])), "hc_graph_text_fetch")
         return out.tobytes(), c.as_dict()
 
+    def graph_cliques(self, root_cap=0, max_entries=0, n_threads=16, fetch=True):
+        """hc_graph_cliques + hc_graph_cliques_fetch: the maximal cliques of the device graph (the graph of graph.txt) as a cliques.Cliques —
+        what quick-cliques computes for the reference, in the call's own order.  root_cap: the largest root degree the device takes (0:
+        the default), max_entries: the budget (0: 2^31 - 1).  fetch=False leaves the CSR on the device and returns the counts."""
+        from . import cliques as CL
+
+        return CL.graph_cliques(self._ctx, root_cap, max_entries, n_threads, fetch)
+
     def graph_fetch(self):
         """hc_graph_fetch of the graph the device holds: edges, out_off, in_nodes, in_off, seq, inclusions."""
         from .host import EDGE_DTYPE

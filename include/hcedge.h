@@ -667,6 +667,73 @@ int hc_graph_write_text(hc_ctx* ctx, uint32_t kind, const hc_graph_text_settings
  * no text kept: HC_ERR_STATE. */
 int hc_graph_text_fetch(hc_ctx* ctx, uint64_t first, uint64_t count, char* dst);
 
+/* ---- maximal cliques of the device graph ------------------------------------------------------------------------------------
+ * What the reference gets by shelling out to quick-cliques on graph.txt (src/ViralQuasispecies.cpp:397-410, `qc
+ * --algorithm=degeneracy`) and reading cliques.txt back: every maximal clique of the graph writeGraphToFile describes
+ * (src/OverlapGraph.cpp:322-385).  Vertices 0 .. n_vertices - 1; an undirected pair {i, j} for every out-record i -> j with
+ * inclusions[i] == 0 and inclusions[j] == 0, once however many records carry it (i -> j and j -> i, repeats).  An isolated vertex —
+ * an inclusion vertex too — is a clique of one (qc prints them, src/SRBuilder.cpp:1075-1077 counts them).  The pair set does not
+ * depend on list order, so a graph with tied lists is accepted.  The reference's two asserts come back as hc_graph_write_text
+ * reports them: HC_OK, counts->status != 0, nothing kept, (bad_v, bad_pos) the first such place in file order.
+ *
+ * ORDER.  The set of cliques is the tool's; the order is this call's own, not quick-cliques' (its bucket-list degeneracy order and
+ * swap-based set layout are one serial dependency chain).  With remove_multi_occ, and in the numbering of the super-reads, a
+ * pipeline driven by this call therefore makes its own deterministic choices where the reference makes qc's.  (The reference's
+ * logged clique_count is n_cliques + 2: qc prints two text lines to stdout, and src/SRBuilder.cpp:1057 counts them.)  The rule,
+ * in one header for host and device (haploconduct_amd/csrc/host/CliqueRule.h):
+ *  1. rank(v) = the position of v in ascending (degree, id), degree in the pair graph above.
+ *  2. The ROOT of a clique is its member of least rank.
+ *  3. Cliques are grouped by root, roots in ascending rank.  A root with P = {} and X = {} yields {v}; P = {} and X != {}: nothing.
+ *  4. Inside a root: Bron-Kerbosch with pivoting from R = {v}, P = the neighbours of greater rank, X = those of smaller rank, over
+ *     local indices = the neighbours in ascending vertex id.  The pivot is the member of P | X with the most neighbours in P, ties to
+ *     the smallest local index; the candidates are P \ N(pivot) in ascending local index, each moved to X after its sub-tree.
+ *  5. Inside a clique, vertices ascend.
+ *
+ * hc_graph_cliques leaves the graph as it found it and keeps the result on the device as a CSR — clique_off[n_cliques + 1] (uint64),
+ * clique_nodes[n_entries] (uint32), exactly what hc_host_sr_clique_select and hc_sr_clique_merge take — until the next
+ * hc_graph_cliques, hc_graph_load, hc_graph_resolve, hc_graph_remove_* or hc_br_reduce.
+ * Limits (HC_ERR_ARG): n_cliques, n_entries and 2 * n_pairs below 2^31. */
+#define HC_CLIQUES_OK 0u
+#define HC_CLIQUES_SELF_LOOP 1u           /* assert (j != i), src/OverlapGraph.cpp:355          */
+#define HC_CLIQUES_INCLUSION_HAS_EDGES 2u /* assert (it2->empty()), :346                        */
+#define HC_CLIQUES_OVER_BUDGET 3u         /* more than max_entries entries: nothing kept        */
+
+#define HC_CLIQUES_DEFAULT_ROOT_CAP 1024u
+#define HC_CLIQUES_MAX_ROOT_CAP 2048u /* a larger root_cap is taken as this: 2 MiB of scratch a wave, 2 GiB on 256 CUs */
+
+typedef struct hc_cliques_settings {
+    /* The largest sub-problem universe d = deg(root) the device takes; a larger root is enumerated by the host's per-root routine
+     * (counts->n_host_roots).  0: HC_CLIQUES_DEFAULT_ROOT_CAP = 1024 — a wave's scratch is d * ceil(d / 64) words of bit matrix and
+     * 3 * ceil(d / 64) words per stack level, d + 1 levels: 0.5 MiB at 1024, times the waves launched (4 per CU at that size, 8 or 16 for slices
+     * below 64 / 8 KiB: 0.5 GiB on 256 CUs), and sized for min(root_cap, the graph's largest degree), never per root.  A value above HC_CLIQUES_MAX_ROOT_CAP = 2048 is
+     * taken as 2048 (the slice grows with d squared; a hub of larger degree is the host's).  Like the context's other work blocks the
+     * slices and the call's arrays are grow-only: they stay allocated until hc_destroy. */
+    uint32_t root_cap;
+    uint32_t n_threads;   /* host parts: the host-route roots; the mirror's roots (0: 1) */
+    /* A budget on n_entries (0: 2^31 - 1).  More: HC_OK, status = HC_CLIQUES_OVER_BUDGET, nothing kept.  Not optional: a perturbed
+     * interval graph of a few thousand vertices can hold tens of gigabytes of maximal cliques.  The count pass stops early (one
+     * global counter, which a wave adds to and tests every 32 roots; a root is abandoned once its own count passes the budget); the verdict is
+     * deterministic because the total is. */
+    uint64_t max_entries;
+} hc_cliques_settings;
+
+typedef struct hc_cliques_counts {
+    uint32_t status, pad;     /* HC_CLIQUES_*                                              */
+    uint64_t bad_v, bad_pos;  /* as hc_graph_text_counts                                   */
+    uint64_t n_pairs;         /* undirected pairs of the graph enumerated                  */
+    uint64_t n_cliques, n_entries;
+    uint64_t n_singletons;    /* cliques of one                                            */
+    uint64_t max_clique;      /* vertices of the largest clique                            */
+    uint64_t n_host_roots;    /* roots with P != {} and degree > root_cap                  */
+    double ms_device;         /* kernels, sorts and scans, by events                       */
+    double ms_host;           /* the host-route roots and their splice                     */
+} hc_cliques_counts;
+
+int hc_graph_cliques(hc_ctx* ctx, const hc_cliques_settings* settings, hc_cliques_counts* counts);
+/* The kept CSR into the caller's arrays (room for n_cliques + 1 / n_entries of the last counts); either may be NULL.  Synchronous.
+ * Nothing kept: HC_ERR_STATE. */
+int hc_graph_cliques_fetch(hc_ctx* ctx, uint64_t* clique_off, uint32_t* clique_nodes);
+
 /* PCI bus id of a device ("0000:c1:00.0"), for callers that place the host threads feeding it on its NUMA node
  * (/sys/bus/pci/devices/<id>/numa_node); the stage does (HC_NUMA=0 turns that off). */
 int hc_device_bus_id(int32_t device, char* bus_id, uint32_t cap);

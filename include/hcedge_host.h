@@ -221,6 +221,13 @@ int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_re
 int hc_host_graph_write_text(hc_host_graph* g, uint32_t kind, const hc_graph_text_settings* st, const uint8_t* bases, const uint64_t* seq_off,
                              const uint32_t* read_first_seq, uint64_t n_reads, char* dst, uint64_t cap, hc_graph_text_counts* counts);
 int hc_host_graph_free(hc_host_graph* g);
+/* The maximal cliques of hc_graph_fetch's arrays (edges, out_off, inclusions or NULL), with the contract, the order and the statuses
+ * of hc_graph_cliques (include/hcedge.h): no device, no context; settings->root_cap is not read (every root is the host's).
+ * clique_off: room for cap_cliques + 1 offsets, clique_nodes: room for cap_entries vertices.  Count, then fetch: both NULL is the
+ * count (HC_OK, counts filled); a buffer with too little room: HC_ERR_ARG with counts filled and nothing written. */
+int hc_host_graph_cliques(const hc_edge_rec* edges, const uint64_t* out_off, uint64_t n_vertices, const uint8_t* inclusions,
+                          const hc_cliques_settings* settings, uint64_t* clique_off, uint32_t* clique_nodes, uint64_t cap_cliques,
+                          uint64_t cap_entries, hc_cliques_counts* counts);
 
 /* Super-read consensus, edge merges and clique merges on the host (hc_host_sr_consensus, hc_host_sr_column, hc_host_sr_table,
  * hc_host_sr_edge_layouts, hc_host_graph_merge_pairs, hc_host_sr_edge_merge_layouts, hc_host_sr_clique_merge_layouts,

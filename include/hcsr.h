@@ -116,8 +116,8 @@ int hc_host_sr_edge_layouts(const hc_edge_rec* edges, uint64_t n_edges, const ui
  * (src/SRBuilder.cpp:654-698), which lays it out with sort_vertices (:33-285) and calls consensus.  The calls of this section
  * do that on the graph the context holds (hc_graph_resolve / hc_graph_load and the cleaning calls), for every combination of
  * single-end and paired reads.
- * Cliques of more than two vertices and filter_subreads (:597-651): hc_sr_clique_merge, the next section.  Left to the caller: clique
- * enumeration.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next; the original-index maps (:750-806) and
+ * Cliques of more than two vertices and filter_subreads (:597-651): hc_sr_clique_merge, the next section.  Clique enumeration
+ * (quick-cliques on graph.txt): hc_graph_cliques (include/hcedge.h), on the same graph.  (The `visited` marks and the trivial super-reads of :1260-1373: hc_sr_merge_next; the original-index maps (:750-806) and
  * subreads.txt: hc_sr_originals_next, on the subread infos this call returns.) */
 
 typedef struct hc_merge_pairs_stats {
@@ -206,7 +206,8 @@ int hc_host_sr_edge_merge_layouts(const hc_edge_rec* edges, const uint64_t* out_
  * filter_subreads / sortVerticesByEndpos (:597-651) where the clique is larger than 3 * min_clique_size (:721), consensus
  * (:413-535) and calcSubreadInfo (:536-595).
  * Left to the caller: reading cliques.txt, remove_multi_occ and the minCliqueSize gate (:1056-1084; remove_multi_occ is a serial
- * greedy pass over a text file: hc_host_sr_clique_select), clique enumeration.  (The original-index maps (:750-806) and
+ * greedy pass over a text file: hc_host_sr_clique_select).  The cliques themselves: hc_graph_cliques (include/hcedge.h), whose
+ * hc_graph_cliques_fetch arrays are this call's clique_off / clique_nodes.  (The original-index maps (:750-806) and
  * subreads.txt: hc_sr_originals_next, on the subread infos this call returns.)
  * The marks, the trivials, the next store and the FNO tables from these outputs: hc_sr_clique_next. */
 
@@ -655,7 +656,8 @@ int hc_host_sr_merge_next(const hc_settings* ec_settings, const uint8_t* bases, 
  * as hc_sr_merge_next does for an edge merge: it leaves the next store in the context and returns the tables of an hc_fno1_input.
  * The semantics are the reference's with N_THREADS = 1: with more threads process_cliques concatenates per-thread blocks in arrival
  * order (:1004-1011), which is not deterministic; one thread gives clique order.
- * Left to the caller: clique enumeration, the text of cliques.txt (the gate behind it: hc_host_sr_clique_select).  The FASTQ text of the
+ * Left to the caller: the text of cliques.txt (the cliques: hc_graph_cliques, include/hcedge.h; the gate behind the file:
+ * hc_host_sr_clique_select).  The FASTQ text of the
  * new store: hc_sr_fastq_write_text, the last section.  The original-index maps (:750-806, :1161-1216) and subreads.txt: hc_sr_originals_next, below, on this call's outputs. */
 
 typedef struct hc_sr_clique_next_input {
