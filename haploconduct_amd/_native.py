@@ -90,6 +90,27 @@ class hc_branch_counts(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class hc_label_settings(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("n_reads", C.c_uint64)]
+
+
+class hc_label_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("edges_before", "edges_after", "conflict_count", "n_moved", "n_switched", "tries", "best_try",
+                                          "n_components", "n_inconsistent", "n_host_vertices", "n_host_edges")] + \
+               [(k, C.c_uint32) for k in ("status", "bad_v", "bad_pos", "pad")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+LABEL_STATUS = ("OK", "DUPLICATE_EDGE", "REPEATED_RECORD")  # HC_LABEL_*
+
+
+def label_settings(resolve_orientations=True, add_duplicates=False, n_reads=0):
+    """hc_label_settings from the two switches (HC_FLAG_RESOLVE_ORIENTATIONS = 0x2, HC_FLAG_ADD_DUPLICATES = 0x1)."""
+    return hc_label_settings((0x2 if resolve_orientations else 0) | (0x1 if add_duplicates else 0), int(n_reads))
+
+
 class hc_graph_text_settings(C.Structure):
     _fields_ = [("edge_threshold", C.c_double), ("merge_contigs", C.c_double), ("n_singles", C.c_uint64)]
 
@@ -256,6 +277,8 @@ _sig = {
     "hc_graph_fetch_inclusion_edges": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hc_graph_remove_tips": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(hc_tip_counts)]),
     "hc_graph_remove_branches": (C.c_int, [_vp, C.POINTER(hc_branch_counts)]),
+    "hc_graph_label_vertices": (C.c_int, [_vp, C.POINTER(hc_label_settings), C.POINTER(hc_label_counts)]),
+    "hc_graph_fetch_orientations": (C.c_int, [_vp, _vp, C.c_uint64]),
     "hc_graph_fetch_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_graph_fetch_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
     "hc_graph_write_text": (C.c_int, [_vp, C.c_uint32, C.POINTER(hc_graph_text_settings), C.POINTER(hc_graph_text_counts)]),

@@ -174,7 +174,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     g.valid = false;
     g.have_groups = false;
     g.n_branching = g.n_tip_reads = 0;
-    c->graph_text.drop(), c->cliques.drop();  // (hc_graph_write_text's text was the old graph's)
+    c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
     const uint32_t m = (uint32_t)n, V = (uint32_t)n_vertices;
     hipStream_t s = c->stream;
@@ -324,7 +324,7 @@ int hc_graph_load(hc_ctx* c, const hc_edge_rec* edges, const uint64_t* out_off, 
     g.valid = false;
     g.have_groups = false;
     g.n_branching = g.n_tip_reads = 0;
-    c->graph_text.drop(), c->cliques.drop();  // (hc_graph_write_text's text was the old graph's)
+    c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
     int rc;
     const size_t E1 = E ? E : 1;
@@ -490,6 +490,9 @@ static int commit_removed(hc_ctx* c, const char* who, const hc::trans::Graph& in
 }
 
 }  // extern "C"
+
+int hc::graph_clean_prepare(hc_ctx* c, hc::trans::Graph& in, hc::trans::Graph& out) { return clean_prepare(c, in, out); }
+void hc::graph_clean_commit(hc_ctx* c, const hc::trans::Graph& out) { clean_commit(c->graph, out); }
 
 // hc_br_reduce's edit (hc_api_br.cpp): n_missing records of d_missing are appended to branching_edges, then the listed records leave the
 // graph with their adj_in entries and follow them (src/BranchReduction.cpp:83-85, :217-225).  rec / in_pos on the device, checked by the

@@ -251,6 +251,15 @@ struct hc_ctx {
         bool valid = false;
         void drop() { valid = false, n_cliques = n_entries = 0; }
     } cliques;
+    // hc_graph_label_vertices / hc_graph_fetch_orientations (hc_api_label.cpp): grow-only scratch — one block carved into the arrays of
+    // hc_label.h: Work, the prims' workspace, the counters — and vertex_orientations, n_orient bytes of them, kept until the next
+    // hc_graph_load / hc_graph_resolve (drop())
+    struct Label {
+        hc_scratch work, temp, counters, orient;
+        uint64_t n_orient = 0;
+        bool valid = false;
+        void drop() { valid = false, n_orient = 0; }
+    } label;
     // The consensus tables of one call path on the device (hc_api_sr.cpp: sr_tables): the log10 terms by term index, q_of itself, the
     // table of one- and two-member columns — and what they were built for.
     struct SrTables {
@@ -375,6 +384,13 @@ struct hc_ctx {
 };
 
 namespace hc {
+namespace trans {
+struct Graph;
+}
+// hc_api_stage.cpp: what every call that rewrites the graph does first and last (hc_api_label.cpp) — the *_next buffers and the views of
+// both graphs; the trade of the buffers once `out` is complete
+int graph_clean_prepare(hc_ctx* c, trans::Graph& in, trans::Graph& out);
+void graph_clean_commit(hc_ctx* c, const trans::Graph& out);
 // hc_api_stage.cpp: the graph edit of hc_br_reduce
 int graph_remove_records(hc_ctx* c, const char* who, const uint32_t* d_rec, const uint32_t* d_in_pos, uint64_t n, const hc_edge_rec* d_missing,
                          uint64_t n_missing);

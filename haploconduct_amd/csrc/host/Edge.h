@@ -53,6 +53,35 @@ public:
         pos3 = -pos3;
         pos4 = -pos4;
     }
+    // src/Edge.h:90-121: ++, --, +- or -+ to --, ++, -+ or +-; true when the edge changed direction on the way
+    bool switch_edge_orientation() {
+        bool ori_changed = false;
+        std::swap(pos1, pos3);
+        std::swap(pos2, pos4);
+        ori1 = !ori1;
+        ori2 = !ori2;
+        if (pos1 < 0 || (pos1 == 0 && vertex1 > vertex2)) {
+            std::swap(read1, read2);
+            std::swap(vertex1, vertex2);
+            std::swap(ori1, ori2);
+            pos1 = -pos1;
+            if (pos2 < 0) {
+                ord = '1';
+                pos2 = -pos2;
+            } else if (ord != '-') {
+                ord = '2';
+            }
+            ori_changed = true;
+        } else {
+            if (pos2 < 0) {
+                pos2 = -pos2;
+                ord = '2';
+            } else if (ord != '-') {
+                ord = '1';
+            }
+        }
+        return ori_changed;
+    }
 
 private:
     double score = 0;

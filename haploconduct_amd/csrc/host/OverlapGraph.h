@@ -139,6 +139,9 @@ public:
     // (GFA only): bases, seq_off (n_seq + 1), read_first_seq (n_reads + 1)
     void writeText(uint32_t kind, const hc_graph_text_settings& st, const uint8_t* bases, const uint64_t* seq_off, const uint32_t* read_first_seq,
                    uint64_t n_reads, std::string& out, hc_graph_text_counts& counts) const;
+    // vertexLabellingHeuristic with labelVertices and sortVerticesByIndegree (src/GraphAlgos.cpp:150-349), then checkDuplicateEdges
+    // (src/OverlapGraph.cpp:578-605), with the contract of hc_graph_label_vertices (include/hcedge.h); the labels go to vertex_orientations
+    void vertexLabellingHeuristic(const hc_label_settings& st, hc_label_counts& counts);
     double checkEdge(node_id_t v, node_id_t w, bool reverse_allowed) const;                   // :233-259
     // :608-719 (--add_duplicates; called at the end of construct_edges, EdgeCalculator.cpp:650-652): every edge once more
     // between the vertices of the reverse-complemented reads.  The mirrored edges carry no reverse offsets and no
@@ -167,8 +170,12 @@ public:
     std::vector<std::vector<Edge>> inclusion_edges;       // removeInclusions' groups (for FNO1)
     std::vector<Edge> branching_edges;                    // what removeTips / removeBranches removed, in removal order (for FNO)
     std::vector<uint8_t> tip_reads;                       // Read::is_tip() by read index (Read::m_is_tip in the reference)
+    std::vector<uint8_t> vertex_orientations;             // getOrientation(v); written by vertexLabellingHeuristic alone
 
 private:
+    struct LabelTry;  // host/Labelling.cpp
+    std::vector<node_id_t> sortVerticesByIndegree() const;                                              // src/GraphAlgos.cpp:150-176
+    void labelVertices(LabelTry& out, std::vector<uint8_t>& orientations, int rand_seed);              // :250-349
     uint64_t sortAdjOut();      // src/GraphAlgos.cpp:806-833
     void ensure_slots() const;  // after adopt_csr the index is built lazily
     mutable EdgeSlotIndex slots;  // kept in step with adj_out by addEdge / removeEdgeWithOri

@@ -12,6 +12,14 @@ namespace hc {
 int set_last_error(int status, const std::string& what);  // hc_api.cpp (or the sanitizer build's stub)
 }
 
+// hc_host_graph (include/hcedge_host.h): a bare graph with the reads its edges point at (hc_host_api.cpp; host/Labelling.cpp)
+struct hc_host_graph {
+    hc::ProgramSettings ps;
+    std::unique_ptr<hc::OverlapGraph> graph;
+    std::vector<hc::Read> reads;
+    hc::InsertCounters counters;
+};
+
 namespace {
 using namespace hc;
 

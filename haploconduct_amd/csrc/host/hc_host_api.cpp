@@ -17,13 +17,6 @@ struct hc_fastq {
     std::vector<uint64_t> ids;
 };
 
-struct hc_host_graph {
-    ProgramSettings ps;
-    std::unique_ptr<OverlapGraph> graph;
-    std::vector<Read> reads;
-    InsertCounters counters;
-};
-
 namespace hc {
 std::string sfo_to_overlaps(const char* sfo_text, size_t sfo_bytes, long ns, long np, uint64_t& n_lines);  // Sfo2Overlaps.cpp
 std::string sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, long ns, long np, uint64_t& n_lines);

@@ -95,6 +95,10 @@ _sig = {
     "hc_host_graph_get_inclusion_edges": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hc_host_graph_remove_tips": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(N.hc_tip_counts)]),
     "hc_host_graph_remove_branches": (C.c_int, [_vp, C.POINTER(N.hc_branch_counts)]),
+    "hc_host_graph_label_vertices": (C.c_int, [_vp, C.POINTER(N.hc_label_settings), C.POINTER(N.hc_label_counts)]),
+    "hc_host_graph_get_orientations": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "hc_host_label_rand": (C.c_int, [C.c_uint32, _vp, C.c_uint64]),
+    "hc_host_label_shuffle": (C.c_int, [C.c_uint32, _vp, C.c_uint64]),
     "hc_host_graph_get_branching_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_host_graph_get_tip_reads": (C.c_int, [_vp, _vp, C.c_uint64]),
     "hc_host_graph_write_text": (C.c_int, [_vp, C.c_uint32, C.POINTER(N.hc_graph_text_settings), _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64,
@@ -301,6 +305,15 @@ class HostGraph:
         c = N.hc_branch_counts()
         N.check(N.lib.hc_host_graph_remove_branches(self._h, C.byref(c)), "hc_host_graph_remove_branches")
         return c.as_dict()
+
+    def label_vertices(self, resolve_orientations=True, add_duplicates=False, n_reads=0):
+        """OverlapGraph::vertexLabellingHeuristic + checkDuplicateEdges (src/GraphAlgos.cpp:150-349, src/OverlapGraph.cpp:578-605) with the
+        contract of hc_graph_label_vertices.  Returns (vertex_orientations as bytes, hc_label_counts as a dict)."""
+        st, c = N.label_settings(resolve_orientations, add_duplicates, n_reads), N.hc_label_counts()
+        N.check(N.lib.hc_host_graph_label_vertices(self._h, C.byref(st), C.byref(c)), "hc_host_graph_label_vertices")
+        fwd = np.zeros(self.V, np.uint8)
+        N.check(N.lib.hc_host_graph_get_orientations(self._h, fwd.ctypes.data if self.V else None, self.V), "hc_host_graph_get_orientations")
+        return fwd, c.as_dict()
 
     def branching_edges(self):
         """OverlapGraph::branching_edges: what removeTips / removeBranches removed so far, in removal order."""

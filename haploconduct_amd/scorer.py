@@ -497,6 +497,21 @@ class EdgeScorer:
         N.check(N.lib.hc_graph_load(self._ctx, _ptr(e), _ptr(oo), _ptr(inn), _ptr(io), oo.size - 1, e.shape[0],
                                     None if inc is None else _ptr(inc)), "hc_graph_load")
 
+    def graph_label_vertices(self, resolve_orientations=True, add_duplicates=False, n_reads=0):
+        """hc_graph_label_vertices: OverlapGraph::vertexLabellingHeuristic + checkDuplicateEdges on the device graph; returns the counts
+        (counts["status"]: N.LABEL_STATUS).  The labels: graph_orientations()."""
+        st, c = N.label_settings(resolve_orientations, add_duplicates, n_reads), N.hc_label_counts()
+        N.check(N.lib.hc_graph_label_vertices(self._ctx, C.byref(st), C.byref(c)), "hc_graph_label_vertices")
+        return c.as_dict()
+
+    def graph_orientations(self):
+        """hc_graph_fetch_orientations: vertex_orientations of the last graph_label_vertices, one byte per vertex (the vertex_fwd of the
+        merge calls)."""
+        V, _ = self._graph_size()
+        fwd = np.zeros(V, np.uint8)
+        N.check(N.lib.hc_graph_fetch_orientations(self._ctx, _ptr(fwd) if V else None, V), "hc_graph_fetch_orientations")
+        return fwd
+
     def graph_remove_inclusions(self):
         """hc_graph_remove_inclusions: OverlapGraph::removeInclusions on the device graph; returns the counts."""
         c = N.hc_clean_counts()

@@ -548,7 +548,7 @@ int hc_graph_fetch_edges(hc_ctx* ctx, uint64_t first, uint64_t count, hc_edge_re
  * in the reference's list order (target order, std::sort's order in lists with repeated targets), adj_in as the branch the
  * reference took leaves it; seq follows the records.  hc_graph_fetch reports no tied lists afterwards (their order is settled).
  * These calls clean what they are given: whether the reference would have re-labelled the graph first
- * (vertexLabellingHeuristic) is the caller's question. */
+ * (vertexLabellingHeuristic) is answered by hc_graph_label_vertices below, which a default-settings caller runs before them. */
 typedef struct hc_clean_counts {
     uint64_t edges_before, edges_after; /* OverlapGraph::edge_count before and after the call                       */
     uint64_t transitive_count;          /* |T_k|, the edges of the last findTransEdges pass                          */
@@ -576,6 +576,63 @@ int hc_graph_remove_transitive(hc_ctx* ctx, uint32_t remove_trans, uint32_t bran
  * edges (room for cap records).  Any output may be NULL; *n_groups / *n_edges are always set. */
 int hc_graph_fetch_inclusion_edges(hc_ctx* ctx, uint32_t* group_vertex, uint64_t* group_off, hc_edge_rec* edges, uint64_t cap,
                                    uint64_t* n_groups, uint64_t* n_edges);
+
+/* ---- vertex labelling on the device graph: OverlapGraph::vertexLabellingHeuristic + checkDuplicateEdges ---------------------
+ * The step between sortEdges and the cleaning calls (src/ViralQuasispecies.cpp:297-309): src/GraphAlgos.cpp:150-349 with
+ * Edge::switch_edge_orientation (src/Edge.h:90-121), addEdge / removeEdgeWithOri (src/OverlapGraph.cpp:94-101, 150-194) and, at the
+ * end, checkDuplicateEdges (:578-605), on the graph the context holds (hc_graph_resolve's or hc_graph_load's; tied lists are refused
+ * with HC_ERR_STATE as the cleaning calls refuse them).  Afterwards hc_graph_fetch returns the re-labelled graph — records, adj_out and
+ * adj_in in the reference's list order, seq following the records — and hc_graph_fetch_orientations the vertex_orientations bytes
+ * (OverlapGraph::getOrientation: the vertex_fwd of include/hcsr.h), which stay on the device until the next hc_graph_load /
+ * hc_graph_resolve.
+ *   HC_FLAG_ADD_DUPLICATES: label 1 for v < n_reads, 0 otherwise, no edge touched (:186-192).  Neither flag: every label 1.
+ *   HC_FLAG_RESOLVE_ORIENTATIONS without ADD_DUPLICATES (:193-246).  The rules, all of them the reference's:
+ *   - A try labels every component by BFS from its vertex of least (in-degree, id), which keeps label 1; a vertex first reached over
+ *     an edge takes its neighbour's label when the first record between them (getEdgeInfo: the node's list, then the neighbour's) has
+ *     ori1 == ori2, the other label otherwise.  The neighbours of a node are adj_in in list order, then the targets of adj_out in list
+ *     order, shuffled by std::srand(try); std::random_shuffle — glibc's rand and libstdc++'s shuffle, restated with a private state:
+ *     the caller's generator is never reseeded.  A component without an odd cycle gets the same labels in every try.
+ *   - One try runs when it leaves no conflict, 100 otherwise (a component with an odd cycle conflicts under every labelling).
+ *   - A try then visits every record in list order with the record's CURRENT ori1 / ori2: both equal to the labels: nothing; class
+ *     (ori1 == ori2) against the labels: a conflict, the record is listed for deletion as it is; else the record is switched
+ *     (switch_edge_orientation) — in place when it keeps its direction, in EVERY try, or as a switched copy listed for moving when it
+ *     turns round (pos1 < 0, or pos1 == 0 and vertex1 > vertex2, after the switch), the original staying as it is.
+ *   - So a record's final state is the replay of all tries in order; the moved and deleted lists are those of the best try — the
+ *     first with the strictly smallest number of conflicts — with the copies as the records stood at that try; a record moved or
+ *     deleted at the best try leaves whatever later tries did to it.
+ *   - All moves first, in list order (source ascending, position ascending): the original leaves adj_out[u] and the first u leaves
+ *     adj_in[v]; the copy is appended to adj_out[v] and v to adj_in[u].  Then the deletions, the same way without the appends.  Hence
+ *     every out-list ends as its remaining records in order, then the copies moved in, by (old source, old position); every in-list
+ *     as its entries minus the first k of each value (k = records of that pair that left), then the pushed values in move order.
+ *   - A list holding two records of one (target, ori1 == ori2 class) makes removeEdgeWithOri's first match another record than the
+ *     classified one: status HC_LABEL_REPEATED_RECORD with the place of the first record that repeats an earlier one of its list,
+ *     the graph and the kept orientations untouched (hc_graph_resolve never leaves such a graph; hc_graph_load may).  One pair in
+ *     both classes is legal and makes its component inconsistent.
+ *   checkDuplicateEdges (all three branches): an out-list with the same target in two adjacent records is where the reference's
+ *   assert (:596) fails: status HC_LABEL_DUPLICATE_EDGE with the place of the second record, HC_OK, the graph re-labelled all the same.
+ * The components, the labels of the consistent ones, the conflict counts, the replay and the rebuild run on the device in a fixed
+ * number of launches; the BFS tries of the inconsistent components run on the context's hc_settings.n_threads host threads over
+ * their fetched lists. */
+#define HC_LABEL_OK 0u
+#define HC_LABEL_DUPLICATE_EDGE 1u  /* assert (j != j_prev), src/OverlapGraph.cpp:596                      */
+#define HC_LABEL_REPEATED_RECORD 2u /* two records of one (source, target, class): refused, nothing changed */
+typedef struct hc_label_settings {
+    uint32_t flags;   /* HC_FLAG_RESOLVE_ORIENTATIONS, HC_FLAG_ADD_DUPLICATES as hc_settings has them; others are ignored */
+    uint64_t n_reads; /* fastq_storage->get_readcount(), read only with ADD_DUPLICATES (:186-192)                         */
+} hc_label_settings;
+typedef struct hc_label_counts {
+    uint64_t edges_before, edges_after;
+    uint64_t conflict_count;               /* :232 / :244; 0 in the branches that leave it unset                              */
+    uint64_t n_moved, n_switched;          /* |min_edges_to_be_moved|; records that stay in their list with ori1 switched      */
+    uint64_t tries, best_try;              /* labelVertices calls; the try whose lists were applied (1-based); 0 outside :193  */
+    uint64_t n_components, n_inconsistent; /* components (isolated vertices included); those with an odd cycle                 */
+    uint64_t n_host_vertices, n_host_edges; /* what the host's walk had to read (the mirror: 0)                               */
+    uint32_t status, bad_v, bad_pos, pad;  /* HC_LABEL_*; the first place in list order (vertex, position in its out-list)     */
+} hc_label_counts;
+int hc_graph_label_vertices(hc_ctx* ctx, const hc_label_settings* settings, hc_label_counts* counts);
+/* vertex_orientations of the last hc_graph_label_vertices, one byte per vertex; n_vertices must be the graph's.  None kept (no call
+ * since the graph was put there, or the call refused it): HC_ERR_STATE. */
+int hc_graph_fetch_orientations(hc_ctx* ctx, uint8_t* vertex_fwd, uint64_t n_vertices);
 
 /* ---- removeTips + removeBranches on the device graph ---------------------------------------------------------------
  * OverlapGraph::removeTips (src/GraphAlgos.cpp:543-637) and OverlapGraph::removeBranches (:835-936), the two steps between

@@ -211,6 +211,18 @@ int hc_host_graph_get_inclusion_edges(hc_host_graph* g, uint64_t* off, uint64_t 
  * contract of hc_graph_remove_tips / hc_graph_remove_branches (include/hcedge.h); counts may be NULL.  cc_rounds stays 0. */
 int hc_host_graph_remove_tips(hc_host_graph* g, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts);
 int hc_host_graph_remove_branches(hc_host_graph* g, hc_branch_counts* counts);
+/* OverlapGraph::vertexLabellingHeuristic (src/GraphAlgos.cpp:150-349) and checkDuplicateEdges (src/OverlapGraph.cpp:578-605) on the bare
+ * graph, with the contract and the statuses of hc_graph_label_vertices (include/hcedge.h): the reference's statements in its order — the
+ * loop `while (count < 100 && delete_count > 0)`, the in-place switches of every try, removeEdgeWithOri + addEdge — on one thread.
+ * n_host_vertices / n_host_edges stay 0.  hc_host_graph_get_orientations: vertex_orientations, one byte per vertex (all 1 before the
+ * first call, as the reference's bitset starts). */
+int hc_host_graph_label_vertices(hc_host_graph* g, const hc_label_settings* settings, hc_label_counts* counts);
+int hc_host_graph_get_orientations(hc_host_graph* g, uint8_t* vertex_fwd, uint64_t n_vertices);
+/* The generator behind the labelling's shuffle, for the tests: the first n values of rand() after srand(seed) (glibc's TYPE_3
+ * generator restated with its own state), and the permutation srand(seed); std::random_shuffle applies to n elements (element i of the
+ * result is element perm[i] of the input). */
+int hc_host_label_rand(uint32_t seed, int32_t* out, uint64_t n);
+int hc_host_label_shuffle(uint32_t seed, uint32_t* perm, uint64_t n);
 /* OverlapGraph::branching_edges so far (room for cap records; *n_out is always set) and Read::is_tip() of reads [0, n_reads). */
 int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint64_t cap, uint64_t* n_out);
 int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads);
