@@ -13,3 +13,4 @@ from .records import OVERLAP_DTYPE, RESULT_DTYPE, Settings, CLS_NAMES  # noqa: F
 from .readstore import ReadSet  # noqa: F401
 from .scorer import EdgeScorer  # noqa: F401
 from . import cliques  # noqa: F401
+from . import cycles  # noqa: F401

@@ -144,6 +144,7 @@ int hc_br_evidence(hc_ctx* c, const uint32_t* vertex_read, const uint8_t* vertex
         ms_device += ms;
         g.edges_out.swap(g.edges_next);
         g.o_out.swap(g.seq_next);
+        g.sorted_at = ~0ull;  // the lists have left hc_graph_sort_edges' order (this swap does not pass through the cleaning calls' commit)
     }
     Work W{};
     hc::br::In I{};

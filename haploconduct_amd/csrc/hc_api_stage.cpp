@@ -176,6 +176,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     g.n_branching = g.n_tip_reads = 0;
     c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
+    g.sorted_at = ~0ull, c->cycles.drop();  // (and hc_graph_sort_edges' stamp, hc_graph_remove_cycles' pairs)
     const uint32_t m = (uint32_t)n, V = (uint32_t)n_vertices;
     hipStream_t s = c->stream;
     const size_t m1 = m ? m : 1;
@@ -326,6 +327,7 @@ int hc_graph_load(hc_ctx* c, const hc_edge_rec* edges, const uint64_t* out_off, 
     g.n_branching = g.n_tip_reads = 0;
     c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
+    g.sorted_at = ~0ull, c->cycles.drop();  // (and hc_graph_sort_edges' stamp, hc_graph_remove_cycles' pairs)
     int rc;
     const size_t E1 = E ? E : 1;
     if ((rc = g.edges_out.ensure(E1 * sizeof(hc_edge_rec))) || (rc = g.o_out.ensure(E1 * 4)) || (rc = g.in_nodes.ensure(E1 * 4)) ||

@@ -226,6 +226,7 @@ struct hc_ctx {
         uint64_t n_vertices = 0, n_edges = 0, n_tied = 0;
         uint64_t n_appended = 0;  // records hc_graph_append has put into adm
         uint64_t edits = 0;       // cleaning calls that replaced the lists (what hc_br_reduce checks its tables against)
+        uint64_t sorted_at = ~0ull;  // `edits` when hc_graph_sort_edges left its order (hc_graph_remove_cycles' stamp); ~0: never
         bool valid = false;
         // hc_graph_append copies through two page-locked buffers on the context's stream and does not wait for the copy
         hc_scratch h_stage[2] = {hc_scratch(hipHostMallocDefault), hc_scratch(hipHostMallocDefault)};
@@ -260,6 +261,17 @@ struct hc_ctx {
         bool valid = false;
         void drop() { valid = false, n_orient = 0; }
     } label;
+    // hc_graph_sort_edges / hc_graph_remove_cycles / hc_graph_fetch_cycle_pairs (hc_api_cycles.cpp): grow-only scratch — one block carved
+    // into the per-graph arrays of the sort or of hc_cycles.h: Work, one into those of the compact CSR (sized once its records are
+    // counted) and one into the radix form's keys (only for a graph with a list longer than hc_cycles.h: kRankMax), the prims'
+    // workspace, the counters, the page-locked blocks the host walks (try 1; the compact CSR's columns) — and the pairs of the last
+    // hc_graph_remove_cycles (u << 32 | v, ascending), valid until the graph is replaced
+    struct Cycles {
+        hc_scratch work, work_sub, work_radix, temp, counters, pin = hc_scratch(hipHostMallocDefault), pin_sub = hc_scratch(hipHostMallocDefault);
+        std::vector<uint64_t> pairs;
+        bool valid = false;
+        void drop() { valid = false, pairs.clear(); }
+    } cycles;
     // The consensus tables of one call path on the device (hc_api_sr.cpp: sr_tables): the log10 terms by term index, q_of itself, the
     // table of one- and two-member columns — and what they were built for.
     struct SrTables {

@@ -14,6 +14,8 @@ struct GraphParams {
     const uint32_t* vtx;  // vertex id of every read, nullptr = identity
     uint32_t n_vertices;
     uint32_t ignore_inclusions;  // --ignore_inclusions: mark OverlapGraph::inclusions (EdgeCalculator.cpp:459-468)
+    // hc_graph_sort_edges: Read::get_len() by read index, read instead of `reads` by the sortEdges key (mode 2); nullptr: from `reads`
+    const uint32_t* len_by_read = nullptr;
 };
 
 size_t graph_temp_bytes(uint32_t m, uint32_t V);

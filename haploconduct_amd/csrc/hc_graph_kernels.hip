@@ -185,9 +185,14 @@ __global__ __launch_bounds__(256) void order_keys_kernel(GraphParams gp, const h
     if (mode == 0) key32[k] = (uint32_t)e.v1;
     else if (mode == 1) key32[k] = (uint32_t)e.v2;
     else {
-        const ReadDesc d1 = g_load_desc(gp.reads + e.read1), d2 = g_load_desc(gp.reads + e.read2);
-        const uint32_t l1 = d1.len1 + ((d1.flags & kReadPaired) ? d1.len2 : 0u);  // Read::get_len, src/Read.h:203-212
-        const uint32_t l2 = d2.len1 + ((d2.flags & kReadPaired) ? d2.len2 : 0u);
+        uint32_t l1, l2;
+        if (gp.len_by_read) {  // the caller's lengths (hc_graph_sort_edges)
+            l1 = gp.len_by_read[e.read1], l2 = gp.len_by_read[e.read2];
+        } else {
+            const ReadDesc d1 = g_load_desc(gp.reads + e.read1), d2 = g_load_desc(gp.reads + e.read2);
+            l1 = d1.len1 + ((d1.flags & kReadPaired) ? d1.len2 : 0u);  // Read::get_len, src/Read.h:203-212
+            l2 = d2.len1 + ((d2.flags & kReadPaired) ? d2.len2 : 0u);
+        }
         const uint32_t nonoverlap = l1 + l2 - 2u * (uint32_t)e.len0;
         key64[k] = ((uint64_t)(uint32_t)e.v1 << 32) | nonoverlap;
     }

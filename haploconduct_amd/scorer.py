@@ -594,6 +594,20 @@ class EdgeScorer:
 
         return CL.graph_cliques(self._ctx, root_cap, max_entries, n_threads, fetch)
 
+    def graph_sort_edges(self, len_by_read):
+        """hc_graph_sort_edges: OverlapGraph::sortEdges (src/OverlapGraph.cpp:722-764) on the device graph, whatever order it is in;
+        len_by_read[r] = total length of read r.  Returns the counts (n_edges, n_tied_lists)."""
+        from . import cycles as CY
+
+        return CY.graph_sort_edges(self._ctx, len_by_read)
+
+    def graph_remove_cycles(self, remove_edges=True):
+        """hc_graph_remove_cycles + hc_graph_fetch_cycle_pairs: OverlapGraph::cycleRemovalHeuristic on the device graph as hc_graph_sort_edges
+        left it.  Returns a cycles.CycleRemoval (pairs = the lines of cycles.txt, counts)."""
+        from . import cycles as CY
+
+        return CY.graph_remove_cycles(self._ctx, remove_edges)
+
     def graph_fetch(self):
         """hc_graph_fetch of the graph the device holds: edges, out_off, in_nodes, in_off, seq, inclusions."""
         from .host import EDGE_DTYPE

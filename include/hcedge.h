@@ -676,6 +676,72 @@ int hc_graph_fetch_branching_edges(hc_ctx* ctx, hc_edge_rec* edges, uint64_t cap
 /* Read::is_tip() of reads [0, n_reads): one byte each (reads no hc_graph_remove_tips call has seen: 0). */
 int hc_graph_fetch_tip_reads(hc_ctx* ctx, uint8_t* is_tip, uint64_t n_reads);
 
+/* ---- the second sortEdges and cycleRemovalHeuristic on the device graph ---------------------------------------------------
+ * The two steps between branch removal / branch reduction and the graph's files (src/ViralQuasispecies.cpp:359-367), on the graph
+ * the context holds.
+ *
+ * hc_graph_sort_edges is OverlapGraph::sortEdges (src/OverlapGraph.cpp:722-764) on that graph, whatever order it is in: every out-list
+ * by (len_by_read[read1] + len_by_read[read2] - 2 len0 in unsigned arithmetic, vertex2), every in-list rebuilt as the sources in
+ * ascending vertex and list order; seq follows the records.  len_by_read[r] = Read::get_len() of read r, as for
+ * hc_host_graph_sort_edges; a record whose read1 / read2 is >= n_reads: HC_ERR_ARG, the graph untouched.  Records equal in both keys
+ * follow the rules of hc_graph_resolve: a list of at most 16 records keeps their incoming order (std::sort is an insertion sort
+ * there); a longer list that holds fully tied records is fetched, sorted by the host's sortEdges code from its incoming order, and
+ * written back — counts->n_tied_lists says how many there were, and no tied list is left behind.  Kept orientations, branching_edges
+ * and tip flags survive the call.  The keys, the radix sorts and the in-list rebuild are hc_graph_resolve's. */
+typedef struct hc_sort_counts {
+    uint64_t n_edges;
+    uint64_t n_tied_lists;
+} hc_sort_counts;
+int hc_graph_sort_edges(hc_ctx* ctx, const uint32_t* len_by_read, uint64_t n_reads, hc_sort_counts* counts);
+
+/* hc_graph_remove_cycles is OverlapGraph::cycleRemovalHeuristic with findCycles, dfs_helper and sortVerticesByIndegree
+ * (src/GraphAlgos.cpp:150-176, 352-541), reportCycle (src/OverlapGraph.cpp:548-562) and removeEdge (:104-147);
+ * settings->remove_edges is !error_correction (src/ViralQuasispecies.cpp:360-366).  The rules, all of them the reference's:
+ *   - A try is a depth-first walk from every unvisited root, the roots in ascending (in-degree, id).
+ *   - A vertex's neighbours are the targets of its out-list, reordered per try: try 1 by (pos1 ascending, target ascending), try 2 by
+ *     (score descending, target), try 3 by (len0 descending, target), try 4 by (mismatch_rate ascending, target); try t = 5 .. 20: the
+ *     list's targets in list order through the permutation std::srand(t); std::random_shuffle applies to a sequence of that length
+ *     (the generator is restated with a state of its own: the caller's is never reseeded).
+ *   - Reaching a vertex that is on the current path records the pair (parent, vertex) in a set; a self-loop is such a pair.
+ *   - One try runs when it finds nothing, 20 otherwise; the applied set is that of the first try with the strictly smallest size.
+ *   - With remove_edges every pair, in ascending (u, v), loses its FIRST record u -> v in list order and the first u of adj_in[v];
+ *     the record is appended to branching_edges.  A pair the list repeats keeps its later records, as in the reference.
+ *   - cycles.txt is one line "u<TAB>v" per pair in that order, and no file when there is none: hc_graph_fetch_cycle_pairs returns the
+ *     pairs of the last call (u, v interleaved; room for cap pairs, *n_pairs always set), the caller writes the file.
+ *   - graph_depth (:374-375) is written by the reference and read nowhere: not reported.
+ * The list order the shuffles and "first record" read is sortEdges': the call takes only a graph that hc_graph_sort_edges left and no
+ * call has edited or reordered since — the cleaning calls, hc_graph_label_vertices, hc_br_evidence (target order), hc_br_reduce —
+ * (HC_ERR_STATE, status HC_CYCLES_NOT_SORTED), and refuses tied lists as the cleaning calls do.  A NaN score or
+ * mismatch_rate makes the comparators of tries 2 and 4 no order: with more than one try, status HC_CYCLES_NAN_KEY with the place of the
+ * first such record, HC_OK, the graph untouched.
+ * The walk runs on the host, iteratively; what surrounds it runs on the device in a fixed number of launches: the roots' order, try 1's
+ * target column (ranked inside lists while none is longer than 1024 records, by radix sorts otherwise), and — only when try 1 found a
+ * pair — the weak components (one union-find pass, one compress pass), the compact CSR of
+ * the components that own a pair (a component acyclic in try 1 is acyclic in every try), its 19 other target columns, and the edit.
+ * Tries 2 - 20 walk that compact CSR on hc_settings.n_threads threads. */
+#define HC_CYCLES_TRIES 20u
+#define HC_CYCLES_OK 0u
+#define HC_CYCLES_NAN_KEY 1u    /* a NaN score / mismatch_rate with cycles present: refused, nothing changed */
+#define HC_CYCLES_NOT_SORTED 2u /* the graph is not in hc_graph_sort_edges' order: refused                    */
+typedef struct hc_cycles_settings {
+    uint32_t remove_edges; /* cycleRemovalHeuristic's argument */
+    uint32_t pad;
+} hc_cycles_settings;
+typedef struct hc_cycles_counts {
+    uint64_t edges_before, edges_after;
+    uint64_t backedge_count;          /* OverlapGraph::backedge_count, :526                                          */
+    uint64_t tries, best_try;         /* findCycles calls; the try whose set was applied (1-based)                   */
+    uint64_t try_size[20];            /* |findCycles(t)| for the tries that ran                                      */
+    uint64_t n_flagged_components;    /* weak components that own a pair of try 1                                    */
+    uint64_t n_host_vertices, n_host_edges; /* the compact CSR tries 2 - 20 had to read (0 with one try)             */
+    uint32_t status, bad_v, bad_pos, pad; /* HC_CYCLES_*; NAN_KEY: the first place in list order (vertex, position)  */
+    /* wall milliseconds of the call's phases (the mirror: 0): try 1's kernels and copies; its walk; components, compact CSR, columns
+     * and their copy; the walks of tries 2 - 20; the edit */
+    double ms_first_device, ms_first_walk, ms_sub_device, ms_sub_walk, ms_edit;
+} hc_cycles_counts;
+int hc_graph_remove_cycles(hc_ctx* ctx, const hc_cycles_settings* settings, hc_cycles_counts* counts);
+int hc_graph_fetch_cycle_pairs(hc_ctx* ctx, uint32_t* pairs, uint64_t cap, uint64_t* n_pairs);
+
 /* ---- graph.txt, digraph.txt and the GFA files from the device graph -----------------------------------------------------
  * OverlapGraph::writeGraphToFile (src/OverlapGraph.cpp:322-385, the input of quick-cliques), writeDiGraphToFile (:388-409) and
  * write2GFA (:468-543), which the reference calls in every iteration (src/ViralQuasispecies.cpp:312, 388-392): the bytes of the

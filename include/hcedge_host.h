@@ -223,6 +223,23 @@ int hc_host_graph_get_orientations(hc_host_graph* g, uint8_t* vertex_fwd, uint64
  * result is element perm[i] of the input). */
 int hc_host_label_rand(uint32_t seed, int32_t* out, uint64_t n);
 int hc_host_label_shuffle(uint32_t seed, uint32_t* perm, uint64_t n);
+/* OverlapGraph::cycleRemovalHeuristic (src/GraphAlgos.cpp:150-176, 352-541; src/OverlapGraph.cpp:104-147, 548-562) on hc_graph_fetch's
+ * arrays, with the contract and the statuses of hc_graph_remove_cycles (include/hcedge.h): no device, no context; the same iterative
+ * walk and the same order rules, with plain sorts, every try over the whole graph (n_threads threads for tries 2 - 20, 0 = 1).  The
+ * graph afterwards goes to edges_out / out_off_out / in_nodes_out / in_off_out (room for the input's sizes; the input's copy without
+ * remove_edges), the removed records in (u, v) order to `removed` and the pairs (u, v interleaved) to `pairs`, both with room for
+ * cap_pairs; any output may be NULL.  More pairs than cap_pairs: HC_ERR_ARG with counts filled and nothing written.  n_flagged_components /
+ * n_host_vertices / n_host_edges are what the device call's compact CSR would hold.  A graph not in sortEdges' order is walked as it is. */
+int hc_host_graph_remove_cycles(const hc_edge_rec* edges, const uint64_t* out_off, const uint32_t* in_nodes, const uint64_t* in_off,
+                                uint64_t n_vertices, const hc_cycles_settings* settings, uint32_t n_threads, hc_edge_rec* edges_out,
+                                uint64_t* out_off_out, uint32_t* in_nodes_out, uint64_t* in_off_out, hc_edge_rec* removed, uint32_t* pairs,
+                                uint64_t cap_pairs, hc_cycles_counts* counts);
+/* findCycles(t) alone (t = 1 .. 20) on the same arrays: the set in ascending (u, v); *n_pairs is always set. */
+int hc_host_graph_find_cycles(const hc_edge_rec* edges, const uint64_t* out_off, const uint64_t* in_off, uint64_t n_vertices, uint32_t t,
+                              uint32_t* pairs, uint64_t cap_pairs, uint64_t* n_pairs);
+/* The permutation table hc_graph_remove_cycles hands to the device for lists of `len` records: 16 rows of len entries, row t - 5 the
+ * permutation of try t (hc_host_label_shuffle(t, ., len)). */
+int hc_host_cycles_perm_table(uint32_t len, uint32_t* table);
 /* OverlapGraph::branching_edges so far (room for cap records; *n_out is always set) and Read::is_tip() of reads [0, n_reads). */
 int hc_host_graph_get_branching_edges(hc_host_graph* g, hc_edge_rec* edges, uint64_t cap, uint64_t* n_out);
 int hc_host_graph_get_tip_reads(hc_host_graph* g, uint8_t* is_tip, uint64_t n_reads);
