@@ -162,6 +162,7 @@ static void free_store(hc_ctx* c) {
     c->srn.prev_clear();  // (hc_sr_fastq_write_text: the raw arrays go or are replaced with the store)
     c->sr_fastq.drop();
     c->br.drop();  // (hc_br_evidence's tables were made from the old store)
+    c->fastq.valid = false;  // (hc_fastq_fetch: the arrays described the old store)
 }
 
 int hc_destroy(hc_ctx* c) {

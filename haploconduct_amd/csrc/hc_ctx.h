@@ -312,6 +312,18 @@ struct hc_ctx {
         uint64_t prev_total = 0;
         void prev_clear() { prev_traded = false, prev_reads = prev_seq = 0, prev_total = 0; }
     } srn;
+    // hc_set_reads_from_fastq_text / hc_fastq_fetch (hc_api_fastq.cpp): grow-only scratch — the three files' text (singles, paired1,
+    // paired2), their newline counts per tile (the counts' exclusive sum after the scan) and line starts; by read the ids, the tokens'
+    // spans and the not-plain flags; by sequence the lengths and their sum; the counters; the scan's workspace — and what hc_fastq_fetch
+    // hands out, valid from a successful call until the store is replaced or released
+    struct Fastq {
+        hc_scratch text[3], tiles[3], line_start[3], ids, tok_off, tok_len, not_plain, lens, off, counters, temp, hist;
+        uint64_t chunk_bytes = 0;  // hc_fastq_set_chunk_bytes (0: the default)
+        std::vector<uint64_t> read_ids, seq_off;
+        std::vector<uint32_t> first;
+        hc_fastq_counts counts{};
+        bool valid = false;
+    } fastq;
     // hc_sr_fastq_write_text / hc_sr_fastq_text_fetch (hc_api_sr_fastq.cpp): grow-only scratch — the items' characters (their exclusive
     // sum after the scan), the scan's workspace, the counters, the tips' reads — and the text of the four files in one block, file f at
     // [bound[f], bound[f + 1]), kept until the next hc_sr_fastq_write_text or until raw arrays it was made from are replaced (drop())

@@ -79,6 +79,65 @@ static std::vector<int> device_list(const ProgramSettings& ps) {
 
 void EdgeCalculator::bind_here() const { bind_thread_to(m_node_cpus); }
 
+// hc_ec_fastq_on_device: process-wide, off by default
+static std::atomic<bool> g_fastq_on_device{false};
+void fastq_on_device(bool on) { g_fastq_on_device.store(on); }
+bool fastq_on_device() { return g_fastq_on_device.load(); }
+
+// The store of a deferred FastqStorage (hc_ec_fastq_on_device): the files are mapped and read on the device (hc_set_reads_from_fastq_text),
+// and the storage adopts what hc_fastq_fetch returns — no base and no quality comes to the host.  Files that cannot be mapped, an input
+// the device does not take (HC_ERR_NOT_ON_DEVICE) and an input the reader refuses all go to the host reader, today's path, without a
+// message: it owns every error.
+static void store_from_fastq_files(hc_ctx* ctx, FastqStorage& f) {
+    struct Mapping {
+        int fd = -1;
+        void* p = nullptr;
+        size_t n = 0;
+        bool given = false, ok = true;
+        char none = 0;
+        ~Mapping() {
+            if (p) munmap(p, n);
+            if (fd >= 0) close(fd);
+        }
+        void open_file(const std::string& path) {
+            given = !path.empty() && path != "None";
+            if (!given) return;
+            struct stat sb;
+            fd = ::open(path.c_str(), O_RDONLY);
+            ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+            if (!ok || sb.st_size == 0) return;
+            n = (size_t)sb.st_size;
+            void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) ok = false, n = 0;
+            else p = m;
+        }
+        const char* text() const { return !given ? nullptr : (p ? (const char*)p : &none); }  // (an empty file is still a file)
+    } m[3];
+    const ProgramSettings& ps = f.deferred_settings();
+    m[0].open_file(ps.singles_file);
+    m[1].open_file(ps.paired1_file);
+    if (m[1].given) m[2].open_file(ps.paired2_file);
+    if (m[0].ok && m[1].ok && m[2].ok && (!m[1].given || m[2].given)) {
+        hc_fastq_text tx;
+        memset(&tx, 0, sizeof tx);
+        tx.singles = m[0].text(), tx.n_singles = m[0].n;
+        tx.paired1 = m[1].text(), tx.n_paired1 = m[1].n;
+        tx.paired2 = m[2].text(), tx.n_paired2 = m[2].n;
+        tx.ids_path = ps.id_correspondence.empty() ? nullptr : ps.id_correspondence.c_str();
+        tx.max_reads = ps.max_reads;
+        hc_fastq_counts cn;
+        if (hc_set_reads_from_fastq_text(ctx, &tx, &cn) == HC_OK) {
+            std::vector<uint64_t> ids(cn.n_reads ? cn.n_reads : 1), off((size_t)cn.n_seq + 1);
+            std::vector<uint32_t> first((size_t)cn.n_reads + 1);
+            check(hc_fastq_fetch(ctx, ids.data(), cn.n_reads, off.data(), first.data(), cn.n_seq), "hc_fastq_fetch");
+            f.adopt(ids.data(), off.data(), first.data(), cn.n_single, cn.n_paired);
+            return;
+        }
+    }
+    f.load_host();
+    check(hc_set_reads(ctx, f.bases().data(), f.quals().data(), f.seq_off().data(), f.read_first_seq().data(), f.get_readcount()), "hc_set_reads");
+}
+
 EdgeCalculator::EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_ptr<OverlapGraph> graph,
                                const ProgramSettings& ps)
     : program_settings(ps), fastq_storage(std::move(fastq)), overlap_graph(std::move(graph)) {
@@ -106,6 +165,7 @@ EdgeCalculator::EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_
     }
     m_node_cpus = cpus_near_device(m_cs.device);
     if (ps.n_threads > 1) m_pool.reset(new WorkerPool(ps.n_threads - 1, [this] { bind_here(); }));
+    if (fastq_storage->deferred() && device_list(ps).size() != 1) fastq_storage->load_host();  // (the device reads the files for one device only)
     const FastqStorage& f = *fastq_storage;
     // The resident process (keep_devices_resident): the contexts, text blocks and small blocks of the stage before this one are taken over —
     // their streams, events, device scratch and page-locked buffers are what a stage's set-up and tear-down spend their time on — when
@@ -163,8 +223,11 @@ EdgeCalculator::EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_
                 blocks_s = now_s() - tb;
             });
         }
-        check(hc_set_reads(dv.ctx, f.bases().data(), f.quals().data(), f.seq_off().data(), f.read_first_seq().data(), f.get_readcount()),
-              "hc_set_reads");
+        if (f.deferred())
+            store_from_fastq_files(dv.ctx, *fastq_storage);
+        else
+            check(hc_set_reads(dv.ctx, f.bases().data(), f.quals().data(), f.seq_off().data(), f.read_first_seq().data(), f.get_readcount()),
+                  "hc_set_reads");
         const double tc2 = now_s();
         double tc3 = tc2;
         if (!m_host_parse) {  // the device's text parser looks read ids up itself

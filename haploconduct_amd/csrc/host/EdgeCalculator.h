@@ -65,6 +65,10 @@ Edge edge_from_admit(const hc_admit_rec& a, const ReadInfo* read_info, bool add_
 // The resident process: a stage's devices (contexts, text blocks, small blocks) outlive it and serve the process's next stage
 // (EdgeCalculator's constructor takes them over when the device list and block size fit).  off: frees what is parked.
 void keep_devices_resident(bool on);
+// hc_ec_fastq_on_device: while on, hc_ec_open hands EdgeCalculator a deferred FastqStorage, whose files the constructor reads on the
+// stage's device (one device, regular files; anything else takes the host reader).  Process-wide, off by default.
+void fastq_on_device(bool on);
+bool fastq_on_device();
 
 class EdgeCalculator {
 public:
@@ -74,6 +78,8 @@ public:
 
     EdgeCalculator(std::shared_ptr<FastqStorage> fastq, std::shared_ptr<OverlapGraph> graph, const ProgramSettings& ps);
     ~EdgeCalculator();
+    // (a stage opened with a deferred FastqStorage knows its reads, and so its graph, only after the constructor)
+    void set_graph(std::shared_ptr<OverlapGraph> graph) { overlap_graph = std::move(graph); }
     EdgeCalculator(const EdgeCalculator&) = delete;
     EdgeCalculator& operator=(const EdgeCalculator&) = delete;
 

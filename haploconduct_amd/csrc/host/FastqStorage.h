@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -37,15 +38,42 @@ public:
     unsigned int get_readcount() const { return (unsigned int)m_read_vec.size(); }
 
     // flat layout (hc_set_reads arguments)
-    const ByteVec& bases() const { return m_bases; }
-    const ByteVec& quals() const { return m_quals; }
+    const ByteVec& bases() const { if (m_lazy_bytes) fill_bytes(); return m_bases; }
+    const ByteVec& quals() const { if (m_lazy_bytes) fill_bytes(); return m_quals; }
     const std::vector<uint64_t>& seq_off() const { return m_seq_off; }
     const std::vector<uint32_t>& read_first_seq() const { return m_first; }
     // sequence index of mate i (0 = single, 1 = /1, 2 = /2) of read `index`
     uint32_t seq_index(unsigned int index, int i) const { return m_first[index] + (i == 2 ? 1u : 0u); }
     uint32_t seq_len(uint32_t q) const { return (uint32_t)(m_seq_off[q + 1] - m_seq_off[q]); }
 
+    // The id side of the readers on its own, for the device reader (hc_api_fastq.cpp: hc_set_reads_from_fastq_text): a storage that holds
+    // the --IDs map and nothing else (ids_path empty: no map), the header's token as `stream >> id` takes it, an id from a token, and one
+    // record's checks in the readers' order with the readers' messages (l2 / n2 are read for a pair only).  All throw as the readers do.
+    struct IdsOnly {};
+    FastqStorage(IdsOnly, const std::string& ids_path);
+    static void header_token(const char* s, size_t n, const char*& tok, size_t& tok_len);
+    read_id_t resolve_token(const char* tok, size_t n) const { return resolve_id(tok, n); }
+    read_id_t check_record(const char* const l1[4], const size_t n1[4], const char* const l2[4], const size_t n2[4], bool paired) const;
+
+    // The stage's opt-in route (hc_ec_fastq_on_device): a storage whose files are read later.  EdgeCalculator's constructor either lets
+    // the device read them into its store and hands over what hc_fastq_fetch returns (adopt: the ids, the offsets, the read vector and
+    // m_ID_to_index — the bases and qualities stay on the device, and bases() / quals() fill themselves on first use by the host
+    // reader's passes over the same files), or reads them here as the constructor above does (load_host).
+    struct Deferred {};
+    FastqStorage(Deferred, const ProgramSettings& ps);
+    bool deferred() const { return m_deferred; }
+    bool adopted() const { return m_lazy_bytes; }  // the device read the files (adopt)
+    const ProgramSettings& deferred_settings() const { return m_ps; }
+    void load_host();
+    void adopt(const uint64_t* read_ids, const uint64_t* seq_off, const uint32_t* read_first_seq, uint32_t n_single, uint32_t n_paired);
+
 private:
+    void load(const ProgramSettings& ps);
+    void index_reads();
+    void fill_bytes() const;
+    ProgramSettings m_ps;
+    bool m_deferred = false, m_lazy_bytes = false;
+    mutable std::once_flag m_fill_once;
     void read_new_ids(const std::string& path);
     void read_singles(const std::string& path, unsigned long max_reads);
     void read_pairs(const std::string& p1, const std::string& p2, unsigned long max_reads);
@@ -59,7 +87,7 @@ private:
 
     std::map<std::string, std::string> m_new_readIDs;    // fastq id -> overlaps-file id (--IDs)
     bool m_have_new_ids = false;
-    ByteVec m_bases, m_quals;
+    mutable ByteVec m_bases, m_quals;  // (mutable: the lazy fill)
     std::vector<uint64_t> m_seq_off{0};
     std::vector<uint32_t> m_first{0};
 };

@@ -114,7 +114,14 @@ int hc_ec_open(hc_ec** out, const hc_settings* settings, const hc_ec_paths* path
         // the device.  Not on a process's first open: asking where the device sits starts the HIP runtime, which that open
         // leaves to the warm-up thread beside the parsing (the stage's own threads find their place once it is up).
         hc::BoundForNow bound(first_open ? std::vector<int>() : hc::cpus_near_device(settings->device));
-        ec->fastq = std::make_shared<FastqStorage>(ec->ps);                                   // ViralQuasispecies.cpp:233
+        // hc_ec_fastq_on_device: the files are read by the constructor below, on the stage's device, before the graph is sized
+        const bool defer = hc::fastq_on_device();
+        if (defer) {
+            ec->fastq = std::make_shared<FastqStorage>(FastqStorage::Deferred{}, ec->ps);
+            ec->calc.reset(new EdgeCalculator(ec->fastq, nullptr, ec->ps));
+        } else {
+            ec->fastq = std::make_shared<FastqStorage>(ec->ps);                               // ViralQuasispecies.cpp:233
+        }
         const double t1 = now();
         const unsigned int R = ec->fastq->get_readcount();
         ec->graph = std::make_shared<OverlapGraph>(ec->ps.add_duplicates ? 2 * R : R, ec->fastq, ec->ps);  // :246-261
@@ -122,7 +129,8 @@ int hc_ec_open(hc_ec** out, const hc_settings* settings, const hc_ec_paths* path
         if (ec->ps.add_duplicates)  // a vertex for every reverse-complemented read as well, :265-271
             for (Read* r : ec->fastq->m_read_vec) r->set_vertex_id(false, ec->graph->addVertex(r->get_read_id()));
         const double t2 = now();
-        ec->calc.reset(new EdgeCalculator(ec->fastq, ec->graph, ec->ps));                     // :279
+        if (defer) ec->calc->set_graph(ec->graph);
+        else ec->calc.reset(new EdgeCalculator(ec->fastq, ec->graph, ec->ps));                // :279
         if (timing) fprintf(stderr, "[hc stage] open: FASTQ -> FastqStorage %.3f s, graph vertices %.3f s, device contexts + store + text blocks %.3f s\n", t1 - t0, t2 - t1, now() - t2);
     });
     if (rc) return rc;
@@ -235,6 +243,25 @@ int hc_ec_close(hc_ec* ec) {
 
 int hc_ec_keep_devices(int on) {
     hc::keep_devices_resident(on != 0);
+    return HC_OK;
+}
+
+int hc_ec_get_read_seq(hc_ec* ec, uint64_t index, int mate, int phred, char* out, uint64_t cap, uint64_t* n_out) {
+    if (!ec || !n_out) return set_last_error(HC_ERR_ARG, "hc_ec_get_read_seq: null");
+    if (index >= ec->fastq->m_read_vec.size()) return set_last_error(HC_ERR_ARG, "hc_ec_get_read_seq: no such read");
+    const Read* r = ec->fastq->m_read_vec[index];
+    if (mate < 0 || mate > 2 || (mate == 0) == r->is_paired()) return set_last_error(HC_ERR_ARG, "hc_ec_get_read_seq: mate 0 of a single read, 1 or 2 of a pair");
+    return guarded("Read", [&] {
+        const std::string s = phred ? r->get_phred(mate) : r->get_seq(mate);
+        *n_out = s.size();
+        if (out && cap >= s.size()) memcpy(out, s.data(), s.size());
+    });
+}
+
+int hc_ec_fastq_was_on_device(hc_ec* ec) { return ec && ec->fastq->adopted() ? 1 : 0; }
+
+int hc_ec_fastq_on_device(int on) {
+    hc::fastq_on_device(on != 0);
     return HC_OK;
 }
 

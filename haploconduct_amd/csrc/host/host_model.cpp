@@ -483,7 +483,76 @@ void FastqStorage::read_pairs(const std::string& p1, const std::string& p2, unsi
     }
 }
 
-FastqStorage::FastqStorage(const ProgramSettings& ps) {  // src/FastqStorage.h:58-98
+// ---- for the device reader (hc_api_fastq.cpp) ------------------------------------------------------------------------
+FastqStorage::FastqStorage(IdsOnly, const std::string& ids_path) {
+    if (!ids_path.empty()) read_new_ids(ids_path);
+}
+
+void FastqStorage::header_token(const char* s, size_t n, const char*& tok, size_t& tok_len) { first_token(s, n, tok, tok_len); }
+
+// one record as read_singles / read_pairs take it: the checks in their order, their messages
+read_id_t FastqStorage::check_record(const char* const l1[4], const size_t n1[4], const char* const l2[4], const size_t n2[4], bool paired) const {
+    if (n1[0] == 0 || l1[0][0] != '@')
+        throw FatalError{HC_ERR_FORMAT, paired ? "Read ID does not start with @. Exiting read_pairs." : "Read ID does not start with @. Exiting read_singles."};
+    const char *t1, *t2;
+    size_t tn1, tn2;
+    first_token(l1[0], n1[0], t1, tn1);
+    if (paired) {
+        first_token(l2[0], n2[0], t2, tn2);
+        if (tn1 != tn2 || memcmp(t1, t2, tn1) != 0) throw FatalError{HC_ERR_FORMAT, "Fastq files /1 /2 are not ordered identically. Exiting read_pairs."};
+    }
+    const read_id_t id = resolve_id(t1, tn1);
+    if (paired) {
+        if (n1[1] == 0 || n2[1] == 0) throw FatalError{HC_ERR_BAD_READ, "paired read with ID " + std::to_string(id) + " has an empty sequence... exiting."};
+    } else if (n1[1] == 0) {
+        throw FatalError{HC_ERR_BAD_READ, "single read with ID " + std::to_string(id) + " has an empty sequence... exiting."};
+    }
+    if (n1[1] != n1[3] || (paired && n2[1] != n2[3]))
+        throw FatalError{HC_ERR_BAD_READ, "FASTQ record with sequence and quality strings of different length"};
+    return id;
+}
+
+FastqStorage::FastqStorage(const ProgramSettings& ps) { load(ps); }
+
+FastqStorage::FastqStorage(Deferred, const ProgramSettings& ps) : m_ps(ps), m_deferred(true) {}
+
+void FastqStorage::load_host() {
+    m_deferred = false;
+    load(m_ps);
+}
+
+void FastqStorage::adopt(const uint64_t* read_ids, const uint64_t* seq_off, const uint32_t* read_first_seq, uint32_t n_single, uint32_t n_paired) {
+    const size_t n_reads = (size_t)n_single + n_paired, n_seq = (size_t)n_single + 2 * (size_t)n_paired;
+    m_deferred = false;
+    m_lazy_bytes = true;
+    m_seq_off.assign(seq_off, seq_off + n_seq + 1);
+    m_first.assign(read_first_seq, read_first_seq + n_reads + 1);
+    m_singles_vec.reserve(n_single);
+    m_paired_vec.reserve(n_paired);
+    for (size_t r = 0; r < n_single; r++) m_singles_vec.emplace_back(this, 0u, false, (read_id_t)read_ids[r]);
+    for (size_t r = n_single; r < n_reads; r++) m_paired_vec.emplace_back(this, 0u, true, (read_id_t)read_ids[r]);
+    m_readcount_single = n_single;
+    m_readcount_paired = n_paired;
+    if (m_ps.verbose) {
+        printf("Singles: %u\n", m_readcount_single);
+        printf("Pairs: %u\n", m_readcount_paired);
+    }
+    index_reads();
+}
+
+// the bases and the qualities of an adopted storage: the host reader's passes over the same files, once
+void FastqStorage::fill_bytes() const {
+    std::call_once(m_fill_once, [this] {
+        ProgramSettings ps = m_ps;
+        ps.verbose = false;
+        FastqStorage files(ps);
+        if (files.m_seq_off != m_seq_off) throw FatalError{HC_ERR_IO, "FastqStorage: the FASTQ files changed after the device read them"};
+        m_bases = std::move(files.m_bases);
+        m_quals = std::move(files.m_quals);
+    });
+}
+
+void FastqStorage::load(const ProgramSettings& ps) {  // src/FastqStorage.h:58-98
     const bool timing = env::given(Knob::STAGE_TIMING);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
@@ -507,6 +576,10 @@ FastqStorage::FastqStorage(const ProgramSettings& ps) {  // src/FastqStorage.h:5
         printf("Singles: %u\n", m_readcount_single);
         printf("Pairs: %u\n", m_readcount_paired);
     }
+    index_reads();
+}
+
+void FastqStorage::index_reads() {  // src/FastqStorage.h:88-97
     unsigned int count = 0;
     m_read_vec.reserve(m_singles_vec.size() + m_paired_vec.size());
     for (auto& r : m_singles_vec) {

@@ -67,6 +67,9 @@ _sig = {
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hc_ec_close": (C.c_int, [_vp]),
     "hc_ec_keep_devices": (C.c_int, [C.c_int]),
+    "hc_ec_fastq_on_device": (C.c_int, [C.c_int]),
+    "hc_ec_fastq_was_on_device": (C.c_int, [_vp]),
+    "hc_ec_get_read_seq": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_host_split_line": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, _vp, _vp, C.c_int]),
     "hc_host_parse_overlap": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(hc_overlap_fields), C.c_char_p]),
     "hc_host_fastq_load": (C.c_int, [C.POINTER(_vp), C.POINTER(hc_ec_paths), C.POINTER(hc_fastq_view)]),
@@ -372,6 +375,12 @@ def keep_devices(on=True):
     N.check(N.lib.hc_ec_keep_devices(1 if on else 0), "hc_ec_keep_devices")
 
 
+def fastq_on_device(on=True):
+    """hc_ec_fastq_on_device: while on, a stage opened on one device with regular files reads its FASTQ files on the device
+    (EdgeScorer.set_reads_from_fastq's call) and keeps no bases or qualities on the host.  Process-wide, off by default."""
+    N.check(N.lib.hc_ec_fastq_on_device(1 if on else 0), "hc_ec_fastq_on_device")
+
+
 class EdgeCalculatorStage:
     """FastqStorage + OverlapGraph + EdgeCalculator, driven like src/ViralQuasispecies.cpp:233-283."""
 
@@ -443,6 +452,18 @@ class EdgeCalculatorStage:
         out = np.zeros(self.vertex_count(), np.uint8)
         N.check(N.lib.hc_ec_get_inclusions(self._h, out.ctypes.data, out.size), "hc_ec_get_inclusions")
         return out
+
+    def fastq_was_on_device(self):
+        """hc_ec_fastq_was_on_device: True when this stage's FASTQ files were read on the device (fastq_on_device)."""
+        return bool(N.lib.hc_ec_fastq_was_on_device(self._h))
+
+    def read_seq(self, index, mate=0, phred=False):
+        """Read::get_seq / get_phred of read `index` (mate 0: a single-end read, 1 / 2: a pair's) as bytes."""
+        n = C.c_uint64()
+        N.check(N.lib.hc_ec_get_read_seq(self._h, int(index), int(mate), int(bool(phred)), None, 0, C.byref(n)), "hc_ec_get_read_seq")
+        buf = C.create_string_buffer(max(1, n.value))
+        N.check(N.lib.hc_ec_get_read_seq(self._h, int(index), int(mate), int(bool(phred)), buf, n.value, C.byref(n)), "hc_ec_get_read_seq")
+        return buf.raw[:n.value]
 
     def sort_edges(self):
         """overlap_graph->sortEdges(), the call after construct_edges in src/ViralQuasispecies.cpp:297."""

@@ -55,6 +55,28 @@ class EdgeScorer:
             "hc_set_reads",
         )
 
+    def set_reads_from_fastq(self, singles=None, paired1=None, paired2=None, ids=None, max_reads=0):
+        """hc_set_reads_from_fastq_text: the FASTQ files (paths or bytes; ids: the --IDs file's path) read on the device into the store, as
+        host.Fastq followed by set_reads would leave it.  Returns the fastq_reader.hc_fastq_counts; the ids and offsets: fastq_fetch."""
+        from . import fastq_reader as FR
+
+        cn = FR.set_reads_from_fastq(self._ctx, singles, paired1, paired2, ids, max_reads)
+        self._reads, self._fastq_counts = None, cn  # (the reads live on the device)
+        return cn
+
+    def fastq_fetch(self):
+        """hc_fastq_fetch: (read_ids, seq_off, read_first_seq) of the store the last set_reads_from_fastq read."""
+        from . import fastq_reader as FR
+
+        cn = getattr(self, "_fastq_counts", None)
+        return FR.fetch(self._ctx, cn if cn is not None else FR.hc_fastq_counts())
+
+    def fastq_set_chunk_bytes(self, n_bytes):
+        """hc_fastq_set_chunk_bytes: a test switch — the upload's chunk (0: the default)."""
+        from . import fastq_reader as FR
+
+        FR.set_chunk_bytes(self._ctx, n_bytes)
+
     # -- super-read consensus (include/hcsr.h) --------------------------------
     def sr_consensus(self, layouts, members, min_qual=0.99, min_clique_size=2, error_correction=False, subreads_needed=False, n_threads=16):
         """hc_sr_consensus: SRBuilder::consensus (src/SRBuilder.cpp:413-535) for every layout, on the device against the store of

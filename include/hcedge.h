@@ -179,6 +179,59 @@ int hc_reset(hc_ctx* ctx, const hc_settings* settings);
 int hc_set_reads(hc_ctx* ctx, const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off,
                  const uint32_t* read_first_seq, uint32_t n_reads);
 
+/* ---- the FASTQ files' text read on the device into the read store ----
+ * Replaces FastqStorage's constructor (src/FastqStorage.h:58-98) with fastq_to_stream, read_singles and read_pairs
+ * (src/FastqStorage.cpp:41-57, 92-152, 154-235) and str_to_read_id (src/Types.h:99-102) for a caller that holds the files' bytes:
+ * hc_set_reads_from_fastq_text EQUALS hc_host_fastq_load followed by hc_set_reads on files holding those bytes — the same read_ids, seq_off,
+ * read_first_seq, n_single, n_paired (singles first, then pairs), the same store (quality map, encoding, slot alignment, `regular`, locality
+ * order, tables; the same dependent state invalidated) and, with hc_sr_keep_device on, the same kept raw arrays (hc_sr_next_reads_fetch).
+ * The text goes to the device in chunks through the context's page-locked stations into one grow-only buffer per file; the newlines are
+ * counted per 4 KiB tile beside the next chunk's copy, one sum gives the line starts, one lane per record checks it and reads its id, one
+ * wave per sequence copies its bases and qualities into the raw arrays, and the store is planned and encoded from them where they lie.
+ *
+ * What is read: lines end at '\n' only (a '\r' stays in its line); a last line without a newline counts; at most
+ * 4 * (unsigned int)max_reads lines of each file; an incomplete last record is ignored; pairs run up to the shorter file; the id token is
+ * the first run of non-isspace bytes behind the header's first character, after skipping isspace bytes (C locale); singles are upper-cased
+ * (a-z only), pairs are not; the '+' line is not looked at.
+ * The checks of a record, IN THIS ORDER: (1) the header of file 1 is non-empty and starts with '@' (file 2's first character is not
+ * checked); (2) the two id tokens are byte-equal; (3) the id resolves; (4) no sequence line is empty; (5) sequence and quality lines have
+ * equal length.  The first bad record in file order wins — every record of the singles file in front of the pairs — and inside a record
+ * the first failing check.  On an error the status and the text of hc_last_error are the host reader's for the same files, err_file /
+ * err_record name the place, and the old store stays usable.  What hc_set_reads refuses (a sequence of 2^28 bytes and more, more than
+ * 2^32 - 1 sequences) is refused with its status.
+ * Ids: a token of the form 0 or [1-9][0-9]{0,17} is read on the device; every other token (empty, a leading zero, hex, a sign, 19 digits
+ * and more, a name) is flagged and resolved inside the call by the host's own parse_id from the text the caller holds; n_host_ids counts
+ * them.  With ids_path every token is resolved by the host's own --IDs map (read_new_ids) on the host's threads from the (offset, length)
+ * spans the device returns — n_host_ids is then the number of reads —, and a missing id is check (3).  The read vector and the id index
+ * stay the caller's (hc_fastq_fetch hands out what they are built from).
+ * NOT on the device — HC_ERR_NOT_ON_DEVICE, nothing changed, the caller takes the host reader: a file of 2^32 - 4096 bytes and more (line
+ * starts are 32-bit offsets; the line count is bounded with them), and a context whose hc_settings.device_mask names more than one device.
+ * hc_fastq_fetch is count, then fetch: the counts of the last successful call are in its hc_fastq_counts; read_ids takes n_reads entries
+ * (cap_reads), seq_off n_seq + 1 and read_first_seq n_reads + 1 (cap_seq >= n_seq, cap_reads >= n_reads, else HC_ERR_ARG); before any
+ * successful call: HC_ERR_STATE.  hc_fastq_set_chunk_bytes is a test switch of the context: the upload's chunk, rounded down to whole
+ * 4 KiB tiles (0 = the default, 32 MiB; below 4096: HC_ERR_ARG). */
+typedef struct hc_fastq_text {
+    const char* singles;  uint64_t n_singles;   /* the files' bytes as they are (a mapping will do); NULL / 0: no such file */
+    const char* paired1;  uint64_t n_paired1;
+    const char* paired2;  uint64_t n_paired2;
+    const char* ids_path;                       /* the --IDs file, or NULL */
+    uint64_t max_reads;                         /* program_settings.max_reads: 4 * (unsigned int)max_reads lines per file */
+} hc_fastq_text;
+typedef struct hc_fastq_counts {
+    uint32_t n_reads, n_seq, n_single, n_paired;
+    uint64_t n_bytes;      /* bases (= qualities) in the raw arrays */
+    uint64_t n_host_ids;   /* tokens the host resolved */
+    uint64_t err_record;   /* the bad record's number in its file(s) */
+    int32_t err_file;      /* -1 none, 0 singles, 1 pairs */
+    uint32_t reserved;
+    double ms_copy;        /* the upload with the newline counts beside it (wall clock) */
+    double ms_device;      /* line starts, records, gather, histograms (device events) */
+    double ms_plan;        /* the host's plan of the store */
+} hc_fastq_counts;
+int hc_set_reads_from_fastq_text(hc_ctx* ctx, const hc_fastq_text* text, hc_fastq_counts* counts);
+int hc_fastq_fetch(hc_ctx* ctx, uint64_t* read_ids, uint64_t cap_reads, uint64_t* seq_off, uint32_t* read_first_seq, uint64_t cap_seq);
+int hc_fastq_set_chunk_bytes(hc_ctx* ctx, uint64_t bytes);
+
 /* Replaces the omp-for of process_overlaps (EdgeCalculator.cpp:400-414).
  * Synchronous; out[i] <-> in[i]; host buffers. */
 int hc_score_batch(hc_ctx* ctx, const hc_overlap_rec* in, uint64_t n, hc_result_rec* out);

@@ -114,6 +114,17 @@ int hc_ec_close(hc_ec* ec);
  * closing a stage then cost milliseconds instead of the 0.06 s + 0.1 s of making and freeing those.  on == 0 frees what is parked.
  * Results do not depend on it.  Process-wide; call it from the thread that opens and closes the stages. */
 int hc_ec_keep_devices(int on);
+/* The FASTQ files read on the stage's device (hcedge.h: hc_set_reads_from_fastq_text), opt-in: with on != 0, hc_ec_open with ONE device and
+ * regular files maps the files, lets the device read them into the stage's context and builds its FastqStorage — ids, offsets, the read
+ * vector, m_ID_to_index — from hc_fastq_fetch.  No base and no quality comes to the host: Read::get_seq and its kin fill them on first use
+ * by the host reader's passes over the same files.  Anything else — several devices, a pipe, HC_ERR_NOT_ON_DEVICE, an input the reader
+ * refuses — takes the default route without a message, and that route owns every error.  Graph, inclusions, counters and
+ * nonedge_overlaps.txt are byte-identical to the default route.  Process-wide, off by default, not an environment knob. */
+int hc_ec_fastq_on_device(int on);
+int hc_ec_fastq_was_on_device(hc_ec* ec); /* 1: this stage's FASTQ files were read on the device; 0: by the host reader */
+/* Read::get_seq (phred == 0) / Read::get_phred (phred != 0) of read `index` of the stage's FastqStorage (src/Read.h:144-170): mate 0 of a
+ * single-end read, 1 or 2 of a pair.  *n_out = the length; the bytes are written when out has room for them (count, then fetch). */
+int hc_ec_get_read_seq(hc_ec* ec, uint64_t index, int mate, int phred, char* out, uint64_t cap, uint64_t* n_out);
 
 /* ---- host-only pieces (no device needed): exercised by the CPU test-suite ---- */
 
