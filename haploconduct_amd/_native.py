@@ -244,6 +244,12 @@ _sig = {
     "hc_set_found_from_sfo_text": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_found_to_lines_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "hc_found_lines_fetch": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "hc_set_sam_records": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64]),
+    "hc_sam_plan": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_uint64)]),
+    "hc_sam_lines_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "hc_sam_lines_fetch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "hc_sam_plan_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hc_sam_lines_slot": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
     "hc_score_pack_device": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     "hc_narrow_payload_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
     "hc_pack_cands": (None, [_vp, C.c_uint64, _vp]),

@@ -324,6 +324,20 @@ struct hc_ctx {
         hc_fastq_counts counts{};
         bool valid = false;
     } fastq;
+    // hc_set_sam_records / hc_sam_plan / hc_sam_lines_device (hc_api_sam.cpp): the uploaded records (alignments, records, operations,
+    // reference lengths, the references' first records), the plan's workspace (keys, permutation, counts, the sort's and the sum's scratch,
+    // the prefix maximum) and what stays of a plan: the records in the script's order, e_j, the windows' starts and the line offsets
+    struct Sam {
+        hc_scratch alns, recs, ops, ref_len, seg_begin, proc_end;
+        hc_scratch keys, keys_out, iota, perm, cnt, temp, pmax, tiles, status, range, stage;
+        hc_scratch pos, len, ref, rec, e, lo, off;
+        hc_scratch slot[16];  // hc_sam_lines_slot
+        uint32_t n_alns = 0, n_recs = 0, n_refs = 0;
+        uint64_t n_ops = 0, n_lines = 0, n_candidates = 0, n_window = 0;
+        int64_t mol = 0;
+        int key_bits = 64;
+        bool loaded = false, planned = false;
+    } sam;
     // hc_sr_fastq_write_text / hc_sr_fastq_text_fetch (hc_api_sr_fastq.cpp): grow-only scratch — the items' characters (their exclusive
     // sum after the scan), the scan's workspace, the counters, the tips' reads — and the text of the four files in one block, file f at
     // [bound[f], bound[f + 1]), kept until the next hc_sr_fastq_write_text or until raw arrays it was made from are replaced (drop())

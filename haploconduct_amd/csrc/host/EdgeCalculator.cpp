@@ -4,6 +4,7 @@
 // resolution of all admitted candidates at once (hc_graph_resolve).  nonedge_overlaps.txt bookkeeping and the per-edge
 // insert into a graph that already holds edges stay on the host.
 #include "EdgeCalculator.h"
+#include "../../../include/hcedge_host.h"
 #include "EnvKnobs.h"
 #include "NumaBind.h"
 
@@ -30,6 +31,7 @@ int hc_found_to_overlaps_text(hc_ctx* c, uint64_t num_singles, uint64_t num_pair
 namespace hc {
 bool sfo_text_to_records(const char* sfo_text, size_t sfo_bytes, std::vector<hc_sfo_rec, DefaultInitAllocator<hc_sfo_rec>>& recs);  // Sfo2Overlaps.cpp
 std::string sfo_to_overlaps(const char* sfo_text, size_t sfo_bytes, long ns, long np, uint64_t& n_lines);  // Sfo2Overlaps.cpp
+void sam_view_to_overlaps_text(const hc_sam_view& v, int64_t min_overlap_len, std::string& out, uint64_t& n_lines);  // Sam2Overlaps.cpp
 }
 
 namespace hc {
@@ -83,6 +85,11 @@ void EdgeCalculator::bind_here() const { bind_thread_to(m_node_cpus); }
 static std::atomic<bool> g_fastq_on_device{false};
 void fastq_on_device(bool on) { g_fastq_on_device.store(on); }
 bool fastq_on_device() { return g_fastq_on_device.load(); }
+
+// hc_ec_sam_on_device: process-wide, on by default
+static std::atomic<bool> g_sam_on_device{true};
+void sam_on_device(bool on) { g_sam_on_device.store(on); }
+bool sam_on_device() { return g_sam_on_device.load(); }
 
 // The store of a deferred FastqStorage (hc_ec_fastq_on_device): the files are mapped and read on the device (hc_set_reads_from_fastq_text),
 // and the storage adopts what hc_fastq_fetch returns — no base and no quality comes to the host.  Files that cannot be mapped, an input
@@ -1167,7 +1174,7 @@ void EdgeCalculator::score_device_parsed(OverlapsParser& parser, std::vector<Ove
 // back is consumed strictly in order, as score_device_parsed's collectors do.  No text, no host tokeniser: every line is plain by construction.
 void EdgeCalculator::score_device_lines(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc) {
     Device& dev = m_dev[0];
-    const size_t D = m_text_depth;
+    const size_t D = m_lines_producer ? std::min<size_t>(m_text_depth, 16) : m_text_depth;  // (hc_sam_lines_slot has 16 slots)
     make_text_blocks(dev);
     uint64_t L = hc_textblock_max_lines(dev.tblk[0]);
     if (L == 0) throw FatalError{HC_ERR_STATE, "construct_edges: a text block without room for lines"};
@@ -1192,7 +1199,9 @@ void EdgeCalculator::score_device_lines(OverlapsParser& parser, std::vector<Over
         uint64_t submitted = 0, waited = 0;  // blocks [waited, submitted) are in flight on the device
         auto submit = [&](uint64_t k) {
             const uint64_t lo = k * L, n = std::min(L, n_use - lo);
-            check(hc_textblock_submit_lines(dev.tblk[k % D], m_lines_override + lo, n, lo, 0), "hc_textblock_submit_lines");
+            // (lines made range by range — construct_edges_from_sam — land in slot k % D of the context: free again once block k - D was waited for)
+            const hc_line_rec* src = m_lines_producer ? m_lines_producer((uint32_t)(k % D), lo, n) : m_lines_override + lo;
+            check(hc_textblock_submit_lines(dev.tblk[k % D], src, n, lo, 0), "hc_textblock_submit_lines");
             submitted = k + 1;
         };
         gate.guarded([&] {
@@ -1591,6 +1600,60 @@ void EdgeCalculator::construct_edges_from_sfo(const std::string& sfo_path, bool 
         std::shared_ptr<const std::string>& p;
         ~Reset() { p.reset(); }
     } reset{m_text_override};
+    m_text_override = out;
+    run_stage(then_sort);
+}
+
+void EdgeCalculator::construct_edges_from_sam(const char* sam_s, const char* sam_p, const char* ref_fasta, int64_t min_overlap_len, bool then_sort,
+                                              uint64_t* n_records, uint64_t* n_lines, int* device_route) {
+    const double t0 = now_s();
+    hc_sam* sam = nullptr;
+    hc_sam_view v;
+    check(hc_host_sam_read(&sam, sam_s, sam_p, ref_fasta, &v), "hc_host_sam_read");  // the reader owns the script's reading errors
+    struct Free {
+        hc_sam* s;
+        ~Free() { hc_host_sam_free(s); }
+    } free_sam{sam};
+    if (n_records) *n_records = v.n_recs;
+    const double t1 = now_s();
+    uint64_t lines = 0;
+    int rc = HC_ERR_NOT_ON_DEVICE;
+    if (sam_on_device()) {
+        rc = hc_set_sam_records(m_ctx, v.alns, v.n_alns, v.recs, v.n_recs, v.ops, v.n_ops, v.ref_len, v.n_refs);
+        if (rc == HC_OK) rc = hc_sam_plan(m_ctx, min_overlap_len, &lines);
+        if (rc != HC_ERR_NOT_ON_DEVICE) check(rc, "hc_sam_plan");
+    }
+    struct Reset {
+        EdgeCalculator* self;
+        ~Reset() {
+            self->m_lines_override = nullptr;
+            self->m_lines_override_n = 0;
+            self->m_lines_producer = nullptr;
+            self->m_text_override.reset();
+        }
+    } reset{this};
+    if (rc == HC_OK) {  // reader, plan, then line ranges of at most a text block's lines into hc_textblock_submit_lines (score_device_lines)
+        static const hc_line_rec none{};
+        m_lines_override = &none;  // (the lines exist range by range only)
+        m_lines_override_n = lines;
+        m_lines_producer = [this](uint32_t slot, uint64_t lo, uint64_t n) {
+            const hc_line_rec* d = nullptr;
+            check(hc_sam_lines_slot(m_ctx, slot, lo, n, &d), "hc_sam_lines_slot");
+            return d;
+        };
+        if (device_route) *device_route = 1;
+        if (n_lines) *n_lines = lines;
+        run_stage(then_sort);
+        if (env::given(Knob::STAGE_TIMING))
+            fprintf(stderr, "[hc stage] SAM -> graph on the device: reader %.3f s (%lu records), plan + construct %.3f s (%lu lines, none of them text)\n", t1 - t0,
+                    (unsigned long)v.n_recs, now_s() - t1, (unsigned long)lines);
+        return;
+    }
+    // an input the device does not decide (or hc_ec_sam_on_device(0)): the mirror's text in memory, the text blocks — every error is the script's
+    auto out = std::make_shared<std::string>();
+    sam_view_to_overlaps_text(v, min_overlap_len, *out, lines);
+    if (device_route) *device_route = 0;
+    if (n_lines) *n_lines = lines;
     m_text_override = out;
     run_stage(then_sort);
 }

@@ -69,6 +69,9 @@ void keep_devices_resident(bool on);
 // stage's device (one device, regular files; anything else takes the host reader).  Process-wide, off by default.
 void fastq_on_device(bool on);
 bool fastq_on_device();
+// hc_ec_sam_on_device: while off, construct_edges_from_sam takes the host mirror's text route
+void sam_on_device(bool on);
+bool sam_on_device();
 
 class EdgeCalculator {
 public:
@@ -109,6 +112,13 @@ public:
     // (hc_sfo2overlaps' code), its text in memory, and the text blocks — which raise what the script raises.  Pinned end to end: the ingest
     // by the script's own outputs (tests/golden/sfo), the stage by the reference's construct_edges + sortEdges.
     void construct_edges_from_sfo(const std::string& sfo_path, bool then_sort, uint64_t* n_records, uint64_t* n_lines, int* device_route);
+    // Reference-guided overlaps (savage.py:690-692, polyte.py:535: bwa, scripts/sam2overlaps.py, original_overlaps.txt) straight to the graph:
+    // the SAM files and the FASTA are read on the host (hc_host_sam_read), the script's enumeration is planned on the device (hc_sam_plan),
+    // and the file's lines are made there range by range, at most a text block's lines at a time, and handed to hc_textblock_submit_lines.
+    // Input the device does not decide, or hc_ec_sam_on_device(0): the host mirror's text through the text route.  Graph, inclusions,
+    // counters and nonedge_overlaps.txt are those of hc_host_sam2overlaps + construct_edges[_sorted] on the file, byte for byte.
+    void construct_edges_from_sam(const char* sam_s, const char* sam_p, const char* ref_fasta, int64_t min_overlap_len, bool then_sort,
+                                  uint64_t* n_records, uint64_t* n_lines, int* device_route);
     // src/EdgeCalculator.cpp:67-139 on arbitrary strings (used by SRBuilder::merge_self_overlap in the
     // reference): scored on the device through a two-read scratch store, finalised with the host libm.
     double overlap_score(const std::string& seq1, const std::string& seq2, const std::string& score1,
@@ -180,6 +190,8 @@ private:
     std::shared_ptr<const std::string> m_text_override;  // construct_edges_from_reads: the overlaps file's text, in memory
     const hc_line_rec* m_lines_override = nullptr;       // construct_edges_from_store: the overlaps file's lines, parsed, in device memory
     uint64_t m_lines_override_n = 0;
+    // construct_edges_from_sam: lines [lo, lo + n) made on demand into slot `slot` of the context, in device memory (else m_lines_override + lo)
+    std::function<const hc_line_rec*(uint32_t slot, uint64_t lo, uint64_t n)> m_lines_producer;
     void score_device_lines(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc);  // ... sent through the text blocks
     bool run_stage_from_found(bool then_sort, uint64_t* n_lines);  // the found records of m_ctx -> lines on the device -> run_stage; false: not the device's
     void score_host_parsed(OverlapsParser& parser, std::vector<Overlap>& rejected, ParseCounters& pc);   // the file tokenised on host threads

@@ -157,6 +157,17 @@ int hc_ec_construct_edges_from_sfo(hc_ec* ec, const char* sfo_path, int sorted, 
     return guarded("construct_edges", [&] { ec->calc->construct_edges_from_sfo(sfo_path, sorted != 0, n_records, n_lines, device_route); });
 }
 
+int hc_ec_construct_edges_from_sam(hc_ec* ec, const char* sam_s, const char* sam_p, const char* ref_fasta, int64_t min_overlap_len, int sorted,
+                                   uint64_t* n_records, uint64_t* n_lines, int* device_route) {
+    if (!ec || !ref_fasta) return set_last_error(HC_ERR_ARG, "hc_ec_construct_edges_from_sam: null");
+    return guarded("construct_edges", [&] { ec->calc->construct_edges_from_sam(sam_s, sam_p, ref_fasta, min_overlap_len, sorted != 0, n_records, n_lines, device_route); });
+}
+
+int hc_ec_sam_on_device(int on) {
+    hc::sam_on_device(on != 0);
+    return HC_OK;
+}
+
 int hc_ec_construct_edges_from_store(hc_ec* ec, double err_rate, uint32_t min_overlap, uint32_t find_flags, int sorted, uint64_t* n_found,
                                      uint64_t* n_lines, int* device_route) {
     if (!ec) return set_last_error(HC_ERR_ARG, "hc_ec_construct_edges_from_store: null");

@@ -81,6 +81,14 @@ _sig = {
     "hc_sfo2overlaps": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_sfo_records_to_overlaps": (C.c_int, [_vp, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hc_host_write_sfo": (C.c_int, [C.c_char_p, _vp, C.c_uint64]),
+    "hc_ec_sam_on_device": (C.c_int, [C.c_int]),
+    "hc_host_sam_read": (C.c_int, [C.POINTER(_vp), C.c_char_p, C.c_char_p, C.c_char_p, _vp]),
+    "hc_host_sam_free": (C.c_int, [_vp]),
+    "hc_host_sam_records_to_lines": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "hc_host_sam_write_lines": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_char_p]),
+    "hc_host_sam2overlaps": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(C.c_uint64)]),
+    "hc_ec_construct_edges_from_sam": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "hc_host_write_overlaps": (C.c_int, [C.c_char_p, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32]),
     "hc_host_graph_new": (C.c_int, [C.POINTER(_vp), C.c_uint64, C.POINTER(N.hc_settings)]),
     "hc_host_graph_insert": (C.c_int, [_vp, _vp]),
@@ -171,6 +179,83 @@ def sfo2overlaps(sfo_path, out_path, num_singles, num_pairs):
     """scripts/sfo2overlaps.py --in --out --num_singles --num_pairs, natively (hc_sfo2overlaps)."""
     n = C.c_uint64()
     N.check(N.lib.hc_sfo2overlaps(_b(sfo_path), _b(out_path), num_singles, num_pairs, C.byref(n)), "hc_sfo2overlaps")
+    return int(n.value)
+
+
+class hc_sam_view(C.Structure):
+    _fields_ = [("alns", _vp), ("recs", _vp), ("ops", _vp), ("id_text", _vp), ("ref_len", _vp)] + \
+               [(k, C.c_uint64) for k in ("n_alns", "n_recs", "n_singles", "n_ops", "n_id_bytes", "n_refs")]
+
+
+class SamRecords:
+    """SAM records (include/hcedge.h: hc_sam_aln, hc_sam_rec, hc_sam_op) with the reference lengths and the ids' text: what
+    hc_host_sam_read makes of the files (SamRecords.read), or arrays a caller built."""
+
+    def __init__(self, alns, recs, ops, ref_len, id_text=b""):
+        from .records import SAM_ALN_DTYPE, SAM_OP_DTYPE, SAM_REC_DTYPE
+
+        self.alns = np.ascontiguousarray(alns, dtype=SAM_ALN_DTYPE)
+        self.recs = np.ascontiguousarray(recs, dtype=SAM_REC_DTYPE)
+        self.ops = np.ascontiguousarray(ops, dtype=SAM_OP_DTYPE)
+        self.ref_len = np.ascontiguousarray(ref_len, dtype=np.uint64)
+        self.id_text = bytes(id_text)
+
+    @classmethod
+    def read(cls, sam_s, sam_p, ref_fasta):
+        """scripts/sam2overlaps.py's reading of the two SAM files (None: absent) and the FASTA (hc_host_sam_read)."""
+        from .records import SAM_ALN_DTYPE, SAM_OP_DTYPE, SAM_REC_DTYPE
+
+        h, v = _vp(), hc_sam_view()
+        N.check(N.lib.hc_host_sam_read(C.byref(h), _b(sam_s), _b(sam_p), _b(ref_fasta), C.byref(v)), "hc_host_sam_read")
+        try:
+            def arr(ptr, n, dt):
+                return np.frombuffer(C.string_at(ptr, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dt)
+
+            return cls(arr(v.alns, v.n_alns, SAM_ALN_DTYPE), arr(v.recs, v.n_recs, SAM_REC_DTYPE), arr(v.ops, v.n_ops, SAM_OP_DTYPE),
+                       arr(v.ref_len, v.n_refs, np.dtype("<u8")), C.string_at(v.id_text, v.n_id_bytes) if v.n_id_bytes else b"")
+        finally:
+            N.lib.hc_host_sam_free(h)
+
+    @property
+    def n_singles(self):
+        from .records import SAM_NONE
+
+        return int((self.recs["second"] == SAM_NONE).sum())
+
+    def ids(self):
+        """the alignments' ids as bytes"""
+        return [self.id_text[int(a["id_off"]):int(a["id_off"]) + int(a["id_len"])] for a in self.alns]
+
+    def _view(self):
+        self._idbuf = C.create_string_buffer(self.id_text, len(self.id_text) + 1)
+        return hc_sam_view(self.alns.ctypes.data, self.recs.ctypes.data, self.ops.ctypes.data, C.addressof(self._idbuf), self.ref_len.ctypes.data,
+                           self.alns.size, self.recs.size, self.n_singles, self.ops.size, len(self.id_text), self.ref_len.size)
+
+    def to_lines(self, min_overlap_len):
+        """hc_host_sam_records_to_lines: the script's loops as written -> (lines as records.LINE_DTYPE, src: the two alignments of each line)."""
+        from .records import LINE_DTYPE
+
+        v, n = self._view(), C.c_uint64()
+        N.check(N.lib.hc_host_sam_records_to_lines(C.byref(v), int(min_overlap_len), None, None, 0, C.byref(n)), "hc_host_sam_records_to_lines")
+        lines, src = np.zeros(n.value, LINE_DTYPE), np.zeros((n.value, 2), np.uint32)
+        if n.value:
+            N.check(N.lib.hc_host_sam_records_to_lines(C.byref(v), int(min_overlap_len), lines.ctypes.data, src.ctypes.data, n.value, C.byref(n)),
+                    "hc_host_sam_records_to_lines")
+        return lines, src
+
+    def write_lines(self, lines, src, out_path):
+        """hc_host_sam_write_lines: lines as the script writes them; src None: the ids as decimal numbers (lines from the device)."""
+        lines = np.ascontiguousarray(lines)
+        v = self._view()
+        s = None if src is None else np.ascontiguousarray(src, dtype=np.uint32)
+        N.check(N.lib.hc_host_sam_write_lines(C.byref(v), lines.ctypes.data if lines.size else None, None if s is None else s.ctypes.data, lines.size,
+                                              _b(out_path)), "hc_host_sam_write_lines")
+
+
+def sam2overlaps(sam_s, sam_p, ref_fasta, out_path, min_overlap_len=0):
+    """scripts/sam2overlaps.py --sam_s --sam_p --ref --out --min_overlap_len, natively (hc_host_sam2overlaps).  Returns the number of lines."""
+    n = C.c_uint64()
+    N.check(N.lib.hc_host_sam2overlaps(_b(sam_s), _b(sam_p), _b(ref_fasta), _b(out_path), int(min_overlap_len), C.byref(n)), "hc_host_sam2overlaps")
     return int(n.value)
 
 
@@ -381,6 +466,11 @@ def fastq_on_device(on=True):
     N.check(N.lib.hc_ec_fastq_on_device(1 if on else 0), "hc_ec_fastq_on_device")
 
 
+def sam_on_device(on):
+    """hc_ec_sam_on_device: off = every construct_edges_from_sam takes the host mirror's text route.  Process-wide, on by default."""
+    N.check(N.lib.hc_ec_sam_on_device(1 if on else 0), "hc_ec_sam_on_device")
+
+
 class EdgeCalculatorStage:
     """FastqStorage + OverlapGraph + EdgeCalculator, driven like src/ViralQuasispecies.cpp:233-283."""
 
@@ -413,6 +503,14 @@ class EdgeCalculatorStage:
         nr, nl, dr = C.c_uint64(), C.c_uint64(), C.c_int()
         N.check(N.lib.hc_ec_construct_edges_from_sfo(self._h, _b(sfo_path), 1 if sorted_order else 0, C.byref(nr), C.byref(nl), C.byref(dr)),
                 "hc_ec_construct_edges_from_sfo")
+        return nr.value, nl.value, bool(dr.value)
+
+    def construct_edges_from_sam(self, sam_s, sam_p, ref_fasta, min_overlap_len=0, sorted_order=True):
+        """hc_ec_construct_edges_from_sam: bwa's SAM files and the reference -> graph (scripts/sam2overlaps.py + the overlaps file + the text
+        parser in one call; the lines are enumerated on the device and stay there).  Returns (records, overlap lines, on_device)."""
+        nr, nl, dr = C.c_uint64(), C.c_uint64(), C.c_int()
+        N.check(N.lib.hc_ec_construct_edges_from_sam(self._h, _b(sam_s), _b(sam_p), _b(ref_fasta), int(min_overlap_len), 1 if sorted_order else 0,
+                                                     C.byref(nr), C.byref(nl), C.byref(dr)), "hc_ec_construct_edges_from_sam")
         return nr.value, nl.value, bool(dr.value)
 
     def construct_edges_from_store(self, err_rate, min_overlap, reversals=True, inclusions=True, sorted_order=True):

@@ -29,6 +29,14 @@ assert ROW_DTYPE.itemsize == 32
 LINE_DTYPE = np.dtype([("id1", "<u8"), ("id2", "<u8"), ("pos1", "<u4"), ("pos2", "<u4"), ("perc1", "<u4"), ("perc2", "<u4"), ("len1", "<u4"),
                        ("len2", "<u4"), ("ord", "u1"), ("ori1", "u1"), ("ori2", "u1"), ("type1", "u1"), ("type2", "u1"), ("pad", "u1", (3,))], align=False)
 assert LINE_DTYPE.itemsize == 48
+# hc_sam_op / hc_sam_aln / hc_sam_rec (include/hcedge.h): bwa's SAM records as scripts/sam2overlaps.py keeps them
+SAM_OP_DTYPE = np.dtype([("count", "<u4"), ("letter", "<u4")], align=False)
+SAM_ALN_DTYPE = np.dtype([("id", "<u8"), ("cpos", "<i8"), ("len", "<u4"), ("flag", "<u4"), ("ref", "<u4"), ("op_first", "<u4"), ("op_count", "<u4"),
+                          ("id_off", "<u4"), ("id_len", "<u4"), ("marks", "<u4")], align=False)
+SAM_REC_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4"), ("reverse", "<u4"), ("pad", "<u4")], align=False)
+assert SAM_OP_DTYPE.itemsize == 8 and SAM_ALN_DTYPE.itemsize == 48 and SAM_REC_DTYPE.itemsize == 16
+SAM_NONE = 0xFFFFFFFF
+SAM_ID_PLAIN, SAM_CIGAR_PLAIN, SAM_CIGAR_VALUE_ERROR, SAM_CIGAR_INDEX_ERROR = 1, 2, 4, 8
 TEXT_ROW_DTYPE = np.dtype([("row", ROW_DTYPE), ("line", LINE_DTYPE)], align=False)
 assert TEXT_ROW_DTYPE.itemsize == 80
 TEXT_REJECT_DTYPE = np.dtype([("line_index", "<u4"), ("pad", "<u4"), ("line", LINE_DTYPE)], align=False)

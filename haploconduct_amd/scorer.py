@@ -707,6 +707,38 @@ class EdgeScorer:
         N.check(N.lib.hc_found_lines_fetch(self._ctx, p, n.value, _ptr(out)), "hc_found_lines_fetch")
         return out
 
+    def set_sam_records(self, sam):
+        """hc_set_sam_records: SAM records (host.SamRecords, or anything with alns / recs / ops / ref_len arrays of records.SAM_*_DTYPE) to
+        the device.  Raises HcError (HC_ERR_NOT_ON_DEVICE) for records the device does not decide."""
+        from .records import SAM_ALN_DTYPE, SAM_OP_DTYPE, SAM_REC_DTYPE
+
+        alns = np.ascontiguousarray(sam.alns, dtype=SAM_ALN_DTYPE)
+        recs = np.ascontiguousarray(sam.recs, dtype=SAM_REC_DTYPE)
+        ops = np.ascontiguousarray(sam.ops, dtype=SAM_OP_DTYPE)
+        ref_len = np.ascontiguousarray(sam.ref_len, dtype=np.uint64)
+        N.check(N.lib.hc_set_sam_records(self._ctx, _ptr(alns), alns.size, _ptr(recs), recs.size, _ptr(ops), ops.size, _ptr(ref_len), ref_len.size),
+                "hc_set_sam_records")
+
+    def sam_plan(self, min_overlap_len):
+        """hc_sam_plan: the enumeration's plan for one min_overlap_len; returns the number of lines of the whole file."""
+        n = C.c_uint64()
+        N.check(N.lib.hc_sam_plan(self._ctx, int(min_overlap_len), C.byref(n)), "hc_sam_plan")
+        return int(n.value)
+
+    def sam_plan_counts(self):
+        """hc_sam_plan_counts: (evaluated pairs, records the waves looked at) of the last plan."""
+        c, w = C.c_uint64(), C.c_uint64()
+        N.check(N.lib.hc_sam_plan_counts(self._ctx, C.byref(c), C.byref(w)), "hc_sam_plan_counts")
+        return int(c.value), int(w.value)
+
+    def sam_lines(self, first_line, n):
+        """hc_sam_lines_fetch: lines [first_line, first_line + n) of the planned file as records (records.LINE_DTYPE), in file order."""
+        from .records import LINE_DTYPE
+
+        out = np.zeros(int(n), dtype=LINE_DTYPE)
+        N.check(N.lib.hc_sam_lines_fetch(self._ctx, int(first_line), int(n), _ptr(out)), "hc_sam_lines_fetch")
+        return out
+
     def score_pack_device(self, d_in_ptr, n, d_out_ptr, cap, base_index, d_payload_ptr, stream=None, fmt=REC_FULL):
         """hc_score_pack_device: scoring + the collection payload in one kernel (rows unordered, count in row 0)."""
         N.check(N.lib.hc_score_pack_device(self._ctx, fmt, C.c_void_p(d_in_ptr), n, C.c_void_p(d_out_ptr), cap, base_index,

@@ -529,6 +529,56 @@ uint64_t hc_textblock_regrown(hc_textblock* b);
 int hc_textblock_reserve_rows(hc_textblock* b, uint64_t rows);
 int hc_textblock_destroy(hc_textblock* b);
 
+/* ---- reference-guided overlaps from SAM records (scripts/sam2overlaps.py: savage.py:690-692, polyte.py:535) ----------
+ * The script reads bwa's SAM files (singles, interleaved pairs) and the reference FASTA, and for every alignment walks the
+ * earlier alignments that still reach it (its `active_reads`, :372-394), corrects the offset through both CIGAR strings
+ * (compute_overlap_pos, :268-313) and writes a 13-column overlaps line.  The records below are what hc_host_sam_read
+ * (hcedge_host.h) makes of the files: one hc_sam_aln per mapped alignment the script keeps, one hc_sam_rec per single or
+ * pair — the singles first, each kind in the order of its file — and the CIGAR operations of all alignments in one array. */
+#define HC_SAM_ID_PLAIN          0x1u /* the id is "0" or [1-9][0-9]{0,17}: `id` is its value                      */
+#define HC_SAM_CIGAR_PLAIN       0x2u /* the CIGAR is ([0-9]+[A-Z=])+ with counts in 1 .. 2^31 - 1                 */
+#define HC_SAM_CIGAR_VALUE_ERROR 0x4u /* starts with a letter: compute_overlap_pos dies of int() (ValueError)       */
+#define HC_SAM_CIGAR_INDEX_ERROR 0x8u /* ends with a number: compute_overlap_pos dies of cigar[i + 1] (IndexError)  */
+#define HC_SAM_NONE 0xFFFFFFFFu
+typedef struct hc_sam_op {
+    uint32_t count;
+    uint32_t letter; /* the character; 0: a run of several letters (neither `D` nor `I` to the script) */
+} hc_sam_op;       /* 8 bytes */
+typedef struct hc_sam_aln {
+    uint64_t id;       /* with HC_SAM_ID_PLAIN */
+    int64_t cpos;      /* POS minus a leading S / H count (:162-176) */
+    uint32_t len;      /* len(cseq): SEQ plus the `N` of leading and trailing H (:171, :179) */
+    uint32_t flag;     /* |FLAG|: only bit 16 is read from here on */
+    uint32_t ref;      /* index of the reference in FASTA order; HC_SAM_NONE: a second mate whose name the script never looks up */
+    uint32_t op_first, op_count; /* its slice of the operations */
+    uint32_t id_off, id_len;     /* its id's bytes in the id text */
+    uint32_t marks;    /* HC_SAM_* */
+} hc_sam_aln;          /* 48 bytes */
+typedef struct hc_sam_rec {
+    uint32_t first, second; /* alignments in the order the script stores them (:248, :255); second == HC_SAM_NONE: a single */
+    uint32_t reverse;       /* the pair's mark (:248) */
+    uint32_t pad;
+} hc_sam_rec;               /* 16 bytes */
+/* hc_set_sam_records: the records go to the device (ref_len: the n_refs reference lengths; the ids' text stays with the caller).
+ * HC_ERR_NOT_ON_DEVICE — nothing changed, the caller takes the host mirror, which owns every status — for: no record; an id or a CIGAR
+ * that is not plain; |cpos|, len or a CIGAR's summed counts of 2^30 and more; n_refs >= 2^30, n_recs >= 2^31; a second mate of length 0.
+ * hc_sam_plan: the enumeration's plan for one min_overlap_len (SAM ingest): one stable radix sort, the processed count per
+ * reference, per record its last partner and the lowest record still active, a count pass that evaluates every pair, one exclusive sum;
+ * 16 bytes per record stay.  *n_lines = lines of the whole file.  HC_ERR_NOT_ON_DEVICE where the count pass meets one of the script's
+ * asserts or a number outside hc_line_rec, or where the windows hold more than 64 records per evaluated pair and record (one long read
+ * among short ones).
+ * hc_sam_lines_device: lines [first_line, first_line + n) of the file, in file order, into d_lines (DEVICE memory); synchronous.
+ * hc_sam_lines_fetch: the same into host memory.  hc_sam_lines_slot: the same into one of sixteen line buffers the context owns
+ * (*d_lines, valid until the next call with that slot): what the stage feeds hc_textblock_submit_lines from while earlier ranges are in flight.
+ * hc_sam_plan_counts: evaluated pairs, sum (e_j - j), and records the waves looked at, sum (i - lo_i), of the last plan. */
+int hc_set_sam_records(hc_ctx* ctx, const hc_sam_aln* alns, uint64_t n_alns, const hc_sam_rec* recs, uint64_t n_recs, const hc_sam_op* ops,
+                       uint64_t n_ops, const uint64_t* ref_len, uint64_t n_refs);
+int hc_sam_plan(hc_ctx* ctx, int64_t min_overlap_len, uint64_t* n_lines);
+int hc_sam_lines_device(hc_ctx* ctx, uint64_t first_line, uint64_t n, hc_line_rec* d_lines);
+int hc_sam_lines_fetch(hc_ctx* ctx, uint64_t first_line, uint64_t n, hc_line_rec* out);
+int hc_sam_plan_counts(hc_ctx* ctx, uint64_t* n_candidates, uint64_t* n_window);
+int hc_sam_lines_slot(hc_ctx* ctx, uint32_t slot, uint64_t first_line, uint64_t n, const hc_line_rec** d_lines);
+
 /* ---- duplicate resolution + adjacency on the device -----------------------------------------
  * The serial half of process_overlaps (EdgeCalculator.cpp:431-545) for a whole overlaps file at once, into an EMPTY
  * graph: the admitted candidates, in sequence order, become Edges (the tail of compute_overlap: pos3/pos4, lengths,

@@ -85,6 +85,17 @@ int hc_ec_construct_edges_from_store(hc_ec* ec, double err_rate, uint32_t min_ov
  * the script's own outputs, the stage by the reference's own code); hc_paths.overlaps_file is not read.
  * *n_records: SFO lines read (0 on the general path), *n_lines: overlap lines, *device_route: 1 = the lines stayed on the device. */
 int hc_ec_construct_edges_from_sfo(hc_ec* ec, const char* sfo_path, int sorted, uint64_t* n_records, uint64_t* n_lines, int* device_route);
+/* The reference-guided way to the graph — `savage --ref` (savage.py:690-692) and POLYTE's reference-guided start (polyte.py:535): bwa's SAM
+ * files (sam_s: single-end, sam_p: interleaved pairs; NULL or "": absent) and the reference FASTA, which scripts/sam2overlaps.py turns into
+ * original_overlaps.txt.  Order of work: the reader (hc_host_sam_read, on the host), the plan (hc_sam_plan on the stage's device), then line
+ * ranges of at most hc_textblock_max_lines into hc_textblock_submit_lines, as hc_ec_construct_edges_from_store does with the finder's lines.
+ * Graph, counters and nonedge_overlaps.txt equal, byte for byte, those of hc_host_sam2overlaps followed by hc_ec_construct_edges[_sorted] on
+ * the written file.  On HC_ERR_NOT_ON_DEVICE (hcedge.h: hc_set_sam_records, hc_sam_plan) the call takes the mirror's text through the text
+ * route itself: *device_route = 0, and every error is the script's.  hc_ec_sam_on_device(0) makes every call take that route (process-wide,
+ * on by default, not an environment knob).  *n_records: singles and pairs read, *n_lines: overlap lines. */
+int hc_ec_construct_edges_from_sam(hc_ec* ec, const char* sam_s, const char* sam_p, const char* ref_fasta, int64_t min_overlap_len, int sorted,
+                                   uint64_t* n_records, uint64_t* n_lines, int* device_route);
+int hc_ec_sam_on_device(int on);
 /* number of device contexts the stage scores on (hc_settings.device_mask) */
 uint32_t hc_ec_device_count(hc_ec* ec);
 int hc_ec_get_counters(hc_ec* ec, hc_ec_counters* out);
@@ -187,6 +198,33 @@ int hc_sfo2overlaps(const char* sfo_path, const char* out_path, uint64_t num_sin
  * hc_host_write_sfo writes for those records, without writing or parsing it. */
 int hc_sfo_records_to_overlaps(const hc_sfo_rec* recs, uint64_t n, const char* out_path, uint64_t num_singles, uint64_t num_pairs,
                                uint64_t* n_lines);
+
+/* SAM ingest (scripts/sam2overlaps.py --sam_s --sam_p --ref --out --min_overlap_len), the reference-guided way to an overlaps file.
+ * hc_host_sam_read: the script's reading (:46-101, :138-266) of the two SAM files (NULL or "": absent) and the FASTA into the records of
+ * hcedge.h; the view stays valid until hc_host_sam_free.  The SAM text is read on the host.
+ * hc_host_sam_records_to_lines: the script's loops as written (:489-554 with its list of active reads, :372-480) over any records of that
+ * layout; id1 / id2 = the ids' values (not plain: the alignment's index), src[2k], src[2k + 1] = the alignments the ids belong to (may be
+ * NULL); *n_lines may exceed cap (count, then fetch).  hc_host_sam_write_lines: lines as the script writes them, the ids through src from
+ * the view's text, or as decimal numbers when src is NULL (lines from the device).  hc_host_sam2overlaps: the three in one call.
+ * Every place the script dies is HC_ERR_FORMAT with the exception's name and the script's line in hc_last_error: IndexError, KeyError,
+ * ValueError, AssertionError, ZeroDivisionError, SystemExit.  Not the script's: a CIGAR count beyond 2^31 - 1 or a number beyond
+ * 2^32 - 1 in a line is refused the same way. */
+typedef struct hc_sam hc_sam;
+typedef struct hc_sam_view {
+    const hc_sam_aln* alns;
+    const hc_sam_rec* recs;
+    const hc_sam_op* ops;
+    const char* id_text;
+    const uint64_t* ref_len;
+    uint64_t n_alns, n_recs, n_singles, n_ops, n_id_bytes, n_refs;
+} hc_sam_view;
+int hc_host_sam_read(hc_sam** out, const char* sam_s, const char* sam_p, const char* ref_fasta, hc_sam_view* view);
+int hc_host_sam_free(hc_sam* s);
+int hc_host_sam_records_to_lines(const hc_sam_view* view, int64_t min_overlap_len, hc_line_rec* lines, uint32_t* src, uint64_t cap,
+                                 uint64_t* n_lines);
+int hc_host_sam_write_lines(const hc_sam_view* view, const hc_line_rec* lines, const uint32_t* src, uint64_t n, const char* out_path);
+int hc_host_sam2overlaps(const char* sam_s, const char* sam_p, const char* ref_fasta, const char* out_path, int64_t min_overlap_len,
+                         uint64_t* n_lines);
 
 /* The serial insert of process_overlaps (src/EdgeCalculator.cpp:441-538) on a bare graph. */
 typedef struct hc_host_graph hc_host_graph;
