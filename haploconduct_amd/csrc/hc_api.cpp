@@ -160,6 +160,7 @@ static void free_store(hc_ctx* c) {
     c->store_bytes = 0;
     c->loc_reads = 0;
     c->srn.prev_clear();  // (hc_sr_fastq_write_text: the raw arrays go or are replaced with the store)
+    c->sr_orig.fno3.drop();  // (hc_fno3_from_originals: its text and table describe the reads of this store)
     c->sr_fastq.drop();
     c->br.drop();  // (hc_br_evidence's tables were made from the old store)
     c->fastq.valid = false;  // (hc_fastq_fetch: the arrays described the old store)

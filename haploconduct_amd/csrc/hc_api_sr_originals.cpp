@@ -217,7 +217,7 @@ int hc_sr_originals_write_text(hc_ctx* c, hc_sr_originals_text_counts* counts) {
     if (!c || !counts) return fail(me, HC_ERR_ARG, "null argument");
     memset(counts, 0, sizeof *counts);
     hc_ctx::SrOriginals& O = c->sr_orig;
-    O.replaced();
+    O.text_replaced();
     if (!O.valid) return fail(me, HC_ERR_STATE, "no dict on the device (hc_sr_originals_init or hc_sr_originals_load first)");
     const uint64_t n_items = O.n_entries + O.n_reads;
     if (n_items + 1 >= (1ull << 32)) return fail(me, HC_ERR_ARG, "2^32 items or more");

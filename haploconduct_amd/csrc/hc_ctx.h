@@ -395,7 +395,19 @@ struct hc_ctx {
         hc_scratch sizes, text;
         uint64_t n_text = 0;
         bool text_valid = false;
-        void replaced() { text_valid = false, n_text = 0; }
+        // hc_fno3_from_originals (hc_api_fno3_resident.cpp): the blocks of hc_fno3_walk.h: Work by name, the walk ranks, the records and
+        // lines of fno3_deduce / fno3_format; the text (n_text bytes) and the candidate table (n_cands rows), built in next_* and traded
+        // at the end, kept until the dict or the store is replaced
+        struct Fno3 {
+            hc_scratch key1_in, key1, val1_in, val1, entry_read, head1, head1_pos, cnt, key2_in, key2, val2_in, val2, diff, head2, differs, head2_pos,
+                counters, temp, rank, items, rec, len, off;
+            hc_scratch text, next_text, cands, next_cands;
+            uint64_t n_text = 0, n_cands = 0;
+            bool valid = false;
+            void drop() { valid = false, n_text = 0, n_cands = 0; }
+        } fno3;
+        void text_replaced() { text_valid = false, n_text = 0; }
+        void replaced() { text_replaced(), fno3.drop(); }
     } sr_orig;
     // hc_br_* (hc_api_br.cpp): the original reads (orig_bases, orig_off: n_orig + 1 offsets) until replaced or hc_reset; the call's vertex
     // tables; grow-only work blocks, each carved into the arrays of hc_br.h: Work by the phase that sizes it (work_v: per vertex, edge and

@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "../../../include/hcfno.h"
+#include "../../../include/hcsr.h"
+#include "../hc_fno3_walk.h"
 #include "../hc_fno_items.h"
 #include "DefaultInit.h"
 #include "EnvKnobs.h"
@@ -1011,11 +1013,17 @@ public:
         emit(out);
     }
 
-private:
     struct Cand {
         uint32_t a, b;
         uint64_t original_id;
     };
+    // hc_host_fno3_from_originals: the candidates are the caller's, there is no walk.  prepare() once, then a candidate's line at p
+    // (room for kMaxLine bytes): the end of the line, or nullptr where it writes none.
+    static constexpr size_t kMaxLine = 160;
+    void prepare() { index_originals(); }
+    char* line(const Cand& c, char* p) const { return deduce(c, p); }
+
+private:
     const hc_fno3_input& in_;
     const uint64_t n_;
     PairSet found_;
@@ -1222,7 +1230,6 @@ private:
     }
 
     void emit(hc_fno_output& out) {
-        constexpr size_t kMaxLine = 160;
         const uint64_t n = cands_.size();
         if (hc::fno_device_wanted(n) && emit_on_device(out)) return;
         const unsigned T = (unsigned)std::min<uint64_t>(threads_, n ? n : 1);
@@ -1339,3 +1346,131 @@ int hc_fno_compute_overlap_data(const hc_fno_read* sr1, const hc_fno_read* sr2, 
 }
 
 }  // extern "C"
+
+// ---- FNO=3 from the kept dict: the mirror of hc_fno3_from_originals (include/hcsr.h) ------------------------------------------------------
+namespace hc {
+namespace fno3w {
+
+const char* check_input(const hc_fno3_resident_input* in, uint64_t n_reads) {
+    if (in->flags & ~HC_FNO_KNOWN_FLAGS) return "unknown bit in flags";
+    if (in->n_single > n_reads || in->n_trivial > n_reads || in->n_paired > n_reads || in->n_single + in->n_trivial + in->n_paired != n_reads)
+        return "n_single + n_trivial + n_paired is not the number of reads";
+    if (in->max_combos > kMaxCombos) return "max_combos above 2^31 - 16";
+    if (in->walk_rank) {
+        std::vector<bool> seen(n_reads, false);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint32_t k = in->walk_rank[r];
+            if (k >= n_reads || seen[k]) return "walk_rank is not a permutation of the reads";
+            seen[k] = true;
+        }
+    }
+    return nullptr;
+}
+
+}  // namespace fno3w
+}  // namespace hc
+
+extern "C" int hc_host_fno3_from_originals(const uint64_t* orig_off, const hc_sr_original* entries, uint64_t n_reads, const hc_fno_read* reads,
+                                           const hc_fno3_resident_input* in, hc_fno3_resident_counts* counts, char* text, uint64_t cap,
+                                           uint64_t* n_bytes, hc_fno3_candidate* cands, uint64_t cap_cands) {
+    namespace W3 = hc::fno3w;
+    const char* me = "hc_host_fno3_from_originals";
+    auto fail = [&](int status, const char* what) { return hc::set_last_error(status, std::string(me) + ": " + what); };
+    if (!orig_off || !in || !counts || !n_bytes || (n_reads && !reads)) return fail(HC_ERR_ARG, "null argument");
+    memset(counts, 0, sizeof *counts);
+    *n_bytes = 0;
+    if (n_reads >= (1ull << 31) || orig_off[0] != 0) return fail(HC_ERR_ARG, "2^31 reads or more, or orig_off[0] is not 0");
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (orig_off[r + 1] < orig_off[r]) return fail(HC_ERR_ARG, "orig_off descends");
+    const uint64_t ne = orig_off[n_reads];
+    if (ne >= (1ull << 31) || (ne && !entries)) return fail(HC_ERR_ARG, "2^31 entries or more, or null entries");
+    for (uint64_t r = 0; r < n_reads; r++) {
+        if (reads[r].len1 == 0 || (reads[r].paired && reads[r].len2 == 0)) return fail(HC_ERR_ARG, "a read of length 0");
+        for (uint64_t k = orig_off[r] + 1; k < orig_off[r + 1]; k++)
+            if (entries[k].id <= entries[k - 1].id) return fail(HC_ERR_ARG, "the ids of a read do not strictly ascend");
+    }
+    if (const char* what = W3::check_input(in, n_reads)) return fail(HC_ERR_ARG, what);
+    const uint64_t max_combos = in->max_combos ? in->max_combos : W3::kMaxCombos;
+    const W3::Ranks K{in->walk_rank, in->n_single, in->n_trivial, in->n_paired};
+    return guarded_fno(me, [&] {
+        std::vector<hc_sr_original> clean(entries, entries + ne);  // (index2 of a single-end original is the dict's 0)
+        for (hc_sr_original& e : clean)
+            if (!e.paired) e.index2 = 0;
+        const hc_sr_original* const entries = clean.data();
+        // the reads of every original, by walk rank
+        struct Member {
+            uint32_t id, rank, read, entry;
+        };
+        std::vector<Member> members(ne);
+        for (uint64_t r = 0; r < n_reads; r++)
+            for (uint64_t k = orig_off[r]; k < orig_off[r + 1]; k++) members[k] = Member{entries[k].id, W3::rank_of(K, r), (uint32_t)r, (uint32_t)k};
+        std::sort(members.begin(), members.end(), [](const Member& x, const Member& y) { return x.id != y.id ? x.id < y.id : x.rank < y.rank; });
+        uint64_t n_originals = 0, n_combos = 0;
+        for (uint64_t b = 0, e; b < ne; b = e) {
+            for (e = b + 1; e < ne && members[e].id == members[b].id; e++) {}
+            n_originals++;
+            n_combos += (e - b) * (e - b - 1) / 2;
+        }
+        counts->n_originals = n_originals;
+        counts->n_combos = n_combos;
+        if (n_originals > in->original_readcount) ref_abort("nodes_to_SR.at(index): more originals than original_readcount");
+        if (n_combos > max_combos) throw FatalError{HC_ERR_NOT_ON_DEVICE, "more (pair, original) combinations than max_combos"};
+        // every (pair, shared original), originals ascending; then by pair, the originals of a pair left in that order
+        struct Combo {
+            uint32_t rank_a, rank_b, ma, mb;  // the two members' places
+        };
+        std::vector<Combo> combos;
+        combos.reserve(n_combos);
+        for (uint64_t b = 0, e; b < ne; b = e) {
+            for (e = b + 1; e < ne && members[e].id == members[b].id; e++) {}
+            for (uint64_t i = b; i < e; i++)
+                for (uint64_t j = i + 1; j < e; j++) combos.push_back(Combo{members[i].rank, members[j].rank, (uint32_t)i, (uint32_t)j});
+        }
+        std::stable_sort(combos.begin(), combos.end(),
+                         [](const Combo& x, const Combo& y) { return x.rank_a != y.rank_a ? x.rank_a < y.rank_a : x.rank_b < y.rank_b; });
+        // the candidates: the first of every run, ambiguous where a later one reads differently
+        std::vector<hc_fno3_candidate> table;
+        for (uint64_t b = 0, e; b < n_combos; b = e) {
+            const Member &ma = members[combos[b].ma], &mb = members[combos[b].mb];
+            const bool either_paired = reads[ma.read].paired || reads[mb.read].paired;
+            const W3::Diff d0 = W3::diff_of(entries[ma.entry], entries[mb.entry], either_paired);
+            bool ambiguous = false;
+            for (e = b + 1; e < n_combos && combos[e].rank_a == combos[b].rank_a && combos[e].rank_b == combos[b].rank_b; e++) {
+                const W3::Diff d = W3::diff_of(entries[members[combos[e].ma].entry], entries[members[combos[e].mb].entry], either_paired);
+                ambiguous |= d.l != d0.l || d.r != d0.r;
+            }
+            table.push_back(hc_fno3_candidate{ma.read, mb.read, ma.id, ambiguous ? HC_FNO3_CAND_AMBIGUOUS : 0u});
+            counts->n_ambiguous += ambiguous;
+        }
+        counts->candidates = table.size();
+        // deduceOverlap on the chosen original: hc_fno3_run's own code
+        std::vector<hc_fno_original> originals(ne);
+        for (uint64_t k = 0; k < ne; k++) originals[k] = hc_fno_original{entries[k].id, entries[k].index1, entries[k].index2};
+        hc_fno3_input fi{};
+        fi.srs = reads;
+        fi.n_single = n_reads;
+        fi.orig_off = orig_off;
+        fi.originals = originals.data();
+        fi.original_readcount = in->original_readcount;
+        fi.flags = in->flags;
+        fi.n_threads = 1;
+        Fno3 deducer(fi);
+        deducer.prepare();
+        std::vector<char> lines;
+        char buf[Fno3::kMaxLine];
+        uint64_t n_lines = 0;
+        for (hc_fno3_candidate& cd : table) {
+            const char* end = deducer.line(Fno3::Cand{cd.a, cd.b, cd.original_id}, buf);
+            if (!end) continue;
+            lines.insert(lines.end(), (const char*)buf, end);
+            cd.flags |= HC_FNO3_CAND_LINE;
+            n_lines++;
+        }
+        counts->n_lines = n_lines;
+        counts->n_bytes = *n_bytes = lines.size();
+        if ((lines.size() && (!text || cap < lines.size())) || (table.size() && (!cands || cap_cands < table.size())))
+            throw FatalError{HC_ERR_ARG, "a buffer is missing or too small (the sizes are filled)"};
+        if (lines.size()) memcpy(text, lines.data(), lines.size());
+        if (table.size()) memcpy(cands, table.data(), table.size() * sizeof(hc_fno3_candidate));
+    });
+}

@@ -709,6 +709,14 @@ def sr_originals_parse(data):
     return OR.host_parse(data)
 
 
+def fno3_from_originals(off, entries, reads, counts3, original_readcount, walk_rank=None, max_combos=0, flags=0):
+    """hc_host_fno3_from_originals: the host mirror of EdgeScorer.fno3_from_originals on a dict (off, entries) and one fno.FNO_READ_DTYPE
+    record per read (id: what the lines print)."""
+    from . import originals as OR
+
+    return OR.host_fno3_from_originals(off, entries, reads, counts3, original_readcount, walk_rank, max_combos, flags)
+
+
 def sr_fastq_text(reads, file):
     """hc_host_sr_fastq_text: the bytes a ReadSet's reads put into singles.fastq (file 0), paired1.fastq (1) or paired2.fastq (2), in
     ascending id (src/SRBuilder.cpp:1434-1447, :1484-1487, :1528-1535)."""

@@ -219,3 +219,95 @@ def host_parse(data):
     N.check(N.lib.hc_host_sr_originals_parse(_ptr(buf), buf.size, off.ctypes.data, nr.value, _ptr(entries), ne.value, C.byref(nr), C.byref(ne), C.byref(bad)),
             "hc_host_sr_originals_parse")
     return off, entries
+
+
+# ---- FNO=3 from the kept dict: hc_fno3_from_originals and its mirror (include/hcsr.h) --------------------------------------------------
+FNO3_CANDIDATE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("original_id", "<u4"), ("flags", "<u4")])
+assert FNO3_CANDIDATE_DTYPE.itemsize == 16
+CAND_AMBIGUOUS, CAND_LINE = 1, 2  # HC_FNO3_CAND_*
+
+
+class hc_fno3_resident_input(C.Structure):
+    _fields_ = [("n_single", C.c_uint64), ("n_trivial", C.c_uint64), ("n_paired", C.c_uint64), ("walk_rank", _vp), ("original_readcount", C.c_uint64),
+                ("max_combos", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class hc_fno3_resident_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_bytes", "candidates", "n_combos", "n_ambiguous", "n_originals")] + [("ms_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+for _name, _args in (("hc_fno3_from_originals", [_vp, C.POINTER(hc_fno3_resident_input), C.POINTER(hc_fno3_resident_counts)]),
+                     ("hc_fno3_text_fetch", [_vp, C.c_uint64, C.c_uint64, _vp]),
+                     ("hc_fno3_candidates_fetch", [_vp, C.c_uint64, C.c_uint64, _vp]),
+                     ("hc_host_fno3_from_originals", [_vp, _vp, C.c_uint64, _vp, C.POINTER(hc_fno3_resident_input), C.POINTER(hc_fno3_resident_counts),
+                                                      _vp, C.c_uint64, _u64p, _vp, C.c_uint64])):
+    getattr(N.lib, _name).restype = C.c_int
+    getattr(N.lib, _name).argtypes = _args
+
+
+@dataclass
+class Fno3Resident:
+    text: bytes              # the lines, ascending (walk rank of SR1, walk rank of SR2)
+    counts: dict             # hc_fno3_resident_counts
+    candidates: np.ndarray   # FNO3_CANDIDATE_DTYPE, one per pair, in the order of the lines
+
+
+def _fno3_input(counts3, walk_rank, original_readcount, max_combos, flags):
+    inp = hc_fno3_resident_input()
+    inp.n_single, inp.n_trivial, inp.n_paired = (int(x) for x in counts3)
+    rank = None if walk_rank is None else _c(walk_rank, np.uint32)
+    inp.walk_rank = None if rank is None else rank.ctypes.data
+    inp.original_readcount, inp.max_combos, inp.flags = int(original_readcount), int(max_combos), int(flags)
+    return inp, rank
+
+
+def fno3_run(ctx, counts3, original_readcount, walk_rank=None, max_combos=0, flags=0):
+    """hc_fno3_from_originals on a context; the text and the table stay on the device -> the counts as a dict."""
+    inp, keep = _fno3_input(counts3, walk_rank, original_readcount, max_combos, flags)
+    cn = hc_fno3_resident_counts()
+    N.check(N.lib.hc_fno3_from_originals(ctx, C.byref(inp), C.byref(cn)), "hc_fno3_from_originals")
+    return cn.as_dict()
+
+
+def fno3_text(ctx, first, count):
+    buf = np.zeros(int(count), np.uint8)
+    N.check(N.lib.hc_fno3_text_fetch(ctx, int(first), buf.size, _ptr(buf)), "hc_fno3_text_fetch")
+    return buf.tobytes()
+
+
+def fno3_candidates(ctx, first, count):
+    buf = np.zeros(int(count), FNO3_CANDIDATE_DTYPE)
+    N.check(N.lib.hc_fno3_candidates_fetch(ctx, int(first), buf.size, _ptr(buf)), "hc_fno3_candidates_fetch")
+    return buf
+
+
+def fno3_from_originals(ctx, counts3, original_readcount, walk_rank=None, max_combos=0, flags=0):
+    """The call, then the whole text and the whole table (EdgeScorer.fno3_from_originals) -> Fno3Resident."""
+    cn = fno3_run(ctx, counts3, original_readcount, walk_rank, max_combos, flags)
+    return Fno3Resident(fno3_text(ctx, 0, cn["n_bytes"]), cn, fno3_candidates(ctx, 0, cn["candidates"]))
+
+
+def host_fno3_from_originals(off, entries, reads, counts3, original_readcount, walk_rank=None, max_combos=0, flags=0):
+    """hc_host_fno3_from_originals: the mirror.  reads: FNO_READ_DTYPE per read of the dict (id: what the lines print) -> Fno3Resident."""
+    off, entries = _dict(off, entries)
+    reads = _c(reads, FNO_READ_DTYPE)
+    if reads.size != off.size - 1:
+        raise ValueError("one read per read of the dict")
+    inp, keep = _fno3_input(counts3, walk_rank, original_readcount, max_combos, flags)
+    cn, nb = hc_fno3_resident_counts(), C.c_uint64()
+
+    def once(text, cands):
+        return N.lib.hc_host_fno3_from_originals(off.ctypes.data, _ptr(entries), off.size - 1, _ptr(reads), C.byref(inp), C.byref(cn), _ptr(text),
+                                                 text.size, C.byref(nb), _ptr(cands), cands.size)
+
+    text, cands = np.zeros(0, np.uint8), np.zeros(0, FNO3_CANDIDATE_DTYPE)
+    rc = once(text, cands)  # count ...
+    if rc != 0 and not (rc == -1 and (cn.n_bytes or cn.candidates)):
+        N.check(rc, "hc_host_fno3_from_originals")
+    if rc != 0:
+        text, cands = np.zeros(int(cn.n_bytes), np.uint8), np.zeros(int(cn.candidates), FNO3_CANDIDATE_DTYPE)
+        N.check(once(text, cands), "hc_host_fno3_from_originals")  # ... then fetch
+    return Fno3Resident(text.tobytes(), cn.as_dict(), cands)

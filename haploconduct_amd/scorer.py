@@ -235,6 +235,15 @@ class EdgeScorer:
 
         return OR.text(self._ctx)[0]
 
+    def fno3_from_originals(self, counts3, original_readcount, walk_rank=None, max_combos=0, flags=0):
+        """hc_fno3_from_originals + the fetch of the whole text and candidate table: findNextOverlaps3 (src/FindNextOverlaps3.cpp:20-173) from
+        the kept dict and the store's read descriptors.  counts3 = (n_single, n_trivial, n_paired) of the store in id order.  Lines come in
+        ascending (walk rank of SR1, walk rank of SR2); a pair that shares several originals is deduced from the one of smallest id, and is
+        flagged ambiguous where they disagree (include/hcsr.h).  Returns an originals.Fno3Resident."""
+        from . import originals as OR
+
+        return OR.fno3_from_originals(self._ctx, counts3, original_readcount, walk_rank, max_combos, flags)
+
     def br_set_original_reads(self, bases, seq_off):
         """hc_br_set_original_reads: the sequences of --original_fastq (single-end, one byte per base, n + 1 offsets), kept on the device."""
         from . import branch_evidence as BR

@@ -780,8 +780,8 @@ int hc_host_sr_clique_select(const uint64_t* clique_off, const uint32_t* clique_
  * iteration order; every reader puts the entries back into a map.  Here the entries of a read are in ASCENDING ORIGINAL ID, in the
  * arrays and in the text.  (2) index2 / len2 of a single-end original are never set nor printed by the reference: here they are 0 on
  * output and ignored on input.
- * Left to the caller: FNO=3, which reads the dict.  (BranchReduction's read evidence: hc_br_evidence, the section behind this one's
- * functions; the FASTQ text: hc_sr_fastq_write_text, the section after that.) */
+ * FNO=3, which reads the dict: hc_fno3_from_originals, behind this section's functions.  (BranchReduction's read evidence:
+ * hc_br_evidence, the section behind that one; the FASTQ text: hc_sr_fastq_write_text, the section after that.) */
 
 typedef struct hc_sr_original {
     uint32_t id;            /* the original read's id                                                                   */
@@ -912,6 +912,88 @@ int hc_host_sr_originals_text(const uint64_t* orig_off, const hc_sr_original* en
  * str_to_read_id would not take whole, or a value outside its type here. */
 int hc_host_sr_originals_parse(const char* text, uint64_t n_bytes, uint64_t* orig_off, uint64_t cap_reads, hc_sr_original* entries,
                                uint64_t cap_entries, uint64_t* n_reads, uint64_t* n_entries, uint64_t* bad_line);
+
+/* ---- FNO=3 from the kept dict: SRBuilder::findNextOverlaps3 on the device ----------------------------------------------------
+ *
+ * A clique iteration ends with findNextOverlaps3 (src/FindNextOverlaps3.cpp:20-173): every pair of reads of the new store that share an
+ * original read becomes a candidate, deduceOverlap (:176-406) turns it into one line of the next overlaps.txt.  hc_fno3_run
+ * (include/hcfno.h) walks the reference's unordered_map on the host, so that its lines come in the reference's order; this call reads
+ * the kept dict and the store's read descriptors (len1, len2, paired; a read's id is its index) where they are and never leaves the
+ * device.  The SET of candidate pairs is the reference's.  Two things are this call's own, because in the reference they follow
+ * libstdc++'s hash iteration order:
+ *  - the order of the lines: here ascending (walk rank of SR1, walk rank of SR2).  No reader depends on the file's order;
+ *  - for a pair that shares several originals, which one deduceOverlap uses: here the shared one of SMALLEST ID.  deduceOverlap reads
+ *    the chosen original through d_l = index1 in SR1 - index1 in SR2 and, when either read is paired, d_r = index2 in SR1 - index2 in
+ *    SR2 (int32 arithmetic, as the reference's int) and nothing else.  A pair is AMBIGUOUS when two of its shared originals give
+ *    different d_l (both reads single-end) or different (d_l, d_r) (otherwise); for every other pair the line is the reference's
+ *    whatever the hash order was.  Ambiguous pairs are counted and flagged in the candidate table.
+ * SR1 of a pair is the read of lower WALK RANK, the reference's i < j in SR_list: the place of a read in single_SR_vec ++
+ * paired_SR_vec ++ trivial_SR_vec (:29-76).  The stores hc_sr_merge_next and hc_sr_clique_next build number the single-end
+ * super-reads from 0, then the trivials, then the pairs, and each of the reference's three deques is in ascending id
+ * (src/SRBuilder.cpp:1142-1233, :1280-1378, writeSinglesToFile / writePairsToFile number a deque front to back, the trivials are pushed
+ * in the vertex order that numbers them), so walk_rank = NULL derives the rank from the three counts.  A paired super-read and a
+ * trivial single-end read behind it form the P-S branch (:240-281) with the pair as SR1.
+ * The tests of :157-165 apply as they are: with HC_FNO_NO_INCLUSIONS a pair whose get_perc() is 100 writes no line, nor does one with
+ * len1 <= 0.  Whatever the reference would stop at (the assert of :391, the Overlap constructor's checks): HC_ERR_FORMAT, no text.
+ * index2 of a single-end original is the dict's 0.
+ * A fixed number of launches whatever the sizes, no atomics on the outputs, the same bytes on every run: a lane per dict entry (its
+ * read by bisection) for the key original id << 32 | walk rank, one stable radix sort; the heads of the runs give n_originals and each
+ * entry's combinations with the later entries of its run; one exclusive sum; a lane per combination (its entry by bisection) for the
+ * key rank of SR1 << b | rank of SR2, b = bits of n_reads - 1, and (d_l, d_r); one stable radix sort over 2 b bits, which leaves the
+ * smallest shared original first in every run; the heads of the runs are the candidates, one sum over "differs from its predecessor
+ * in the run" read at the run boundaries marks the ambiguous ones; a lane per candidate fills the record hc_fno3_run's device form
+ * takes, and deduceOverlap, the exclusive sum and the text are that form's kernels.
+ * Memory: about 45 bytes per combination and the sort's scratch, in the context's blocks (grow-only).
+ * The text and the candidate table stay on the device until the next hc_fno3_from_originals or the next call that replaces the dict or
+ * the store (hc_sr_originals_write_text's rule; a store of another number of reads than the dict's is refused).
+ * HC_ERR_STATE: no store, no kept dict, or a dict over another number of reads than the store's.  HC_ERR_ARG: a null argument, counts
+ * that do not add up to the store's reads, a walk_rank that is no permutation, unknown bits in flags, max_combos above 2^31 - 16.
+ * HC_ERR_FORMAT: more distinct originals than original_readcount (nodes_to_SR.at, :37), or a stop of the reference.
+ * HC_ERR_NOT_ON_DEVICE: more than max_combos combinations — decided before anything of that size is allocated.  Every error leaves
+ * the text and the table of the call before in place, HC_ERR_FORMAT apart (nothing is kept after it). */
+typedef struct hc_fno3_resident_input {
+    uint64_t n_single, n_trivial, n_paired; /* reads of the current store in id order: singles, trivials, pairs */
+    const uint32_t* walk_rank;  /* optional [n_reads]: place of read r in single_SR_vec ++ paired_SR_vec ++ trivial_SR_vec
+                                   (FindNextOverlaps3.cpp:29-76); a permutation.  NULL: derived from the three counts
+                                   (single r -> r; pair r -> r - n_trivial; trivial r -> r + n_paired) */
+    uint64_t original_readcount; /* more distinct originals than this: HC_ERR_FORMAT (nodes_to_SR.at, :37) */
+    uint64_t max_combos;         /* 0 = 2^31 - 16; more (pair, original) combinations: HC_ERR_NOT_ON_DEVICE, nothing changed */
+    uint32_t flags;              /* HC_FNO_NO_INCLUSIONS; other HC_FNO_KNOWN_FLAGS accepted and ignored as hc_fno3_run does; unknown bits HC_ERR_ARG */
+    uint32_t reserved;
+} hc_fno3_resident_input;
+
+typedef struct hc_fno3_resident_counts {
+    uint64_t n_lines, n_bytes;
+    uint64_t candidates;   /* distinct pairs = overlaps_list.size(); equal to hc_fno3_run's counter on the same data */
+    uint64_t n_combos;     /* (pair, shared original) combinations */
+    uint64_t n_ambiguous;  /* pairs whose shared originals disagree (definition above) */
+    uint64_t n_originals;  /* distinct original ids in the dict */
+    double ms_device;      /* device call only: kernels, sorts and sums, by events on the stream */
+} hc_fno3_resident_counts;
+
+#define HC_FNO3_CAND_AMBIGUOUS 0x1u
+#define HC_FNO3_CAND_LINE      0x2u
+/* One candidate pair, in the order of the lines.  a, b: the reads (their index in the store = their id there; the mirror: their index
+ * in `reads`), rank(a) < rank(b); original_id: the shared original the line is deduced from. */
+typedef struct hc_fno3_candidate {
+    uint32_t a, b;
+    uint32_t original_id;
+    uint32_t flags; /* HC_FNO3_CAND_AMBIGUOUS | HC_FNO3_CAND_LINE (it wrote a line) */
+} hc_fno3_candidate; /* 16 bytes */
+
+int hc_fno3_from_originals(hc_ctx* ctx, const hc_fno3_resident_input* in, hc_fno3_resident_counts* counts);
+/* Bytes [first, first + count) of the text / candidates [first, first + count) of the table.  A range outside what is kept:
+ * HC_ERR_ARG; nothing kept: HC_ERR_STATE. */
+int hc_fno3_text_fetch(hc_ctx* ctx, uint64_t first, uint64_t count, char* dst);
+int hc_fno3_candidates_fetch(hc_ctx* ctx, uint64_t first, uint64_t count, hc_fno3_candidate* dst);
+
+/* The same rule on the host (no device, no context), as loops over plain arrays: the dict over n_reads reads, reads[r] = id (what the
+ * lines print; any distinct labels), len1, len2, paired of read r; in as above, with the counts adding up to n_reads.  *counts is
+ * always filled (ms_device 0), *n_bytes too; text: room for cap bytes, cands: room for cap_cands candidates — where either is NULL or
+ * too small nothing is copied and HC_ERR_ARG is returned (count, then fetch).  HC_ERR_ARG also for a read of length 0. */
+int hc_host_fno3_from_originals(const uint64_t* orig_off, const hc_sr_original* entries, uint64_t n_reads, const hc_fno_read* reads,
+                                const hc_fno3_resident_input* in, hc_fno3_resident_counts* counts, char* text, uint64_t cap,
+                                uint64_t* n_bytes, hc_fno3_candidate* cands, uint64_t cap_cands);
 
 /* ---- read evidence for branching edges: the first half of BranchReduction::readBasedBranchReduction -------------------------
  *
