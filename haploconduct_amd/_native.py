@@ -199,6 +199,25 @@ _sr_tail = [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_settings), _vp, _v
 _sr_self_tail = [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(hc_sr_self_settings), _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u64p,
                  C.POINTER(hc_sr_self_stats)]
 _sr_next_tail = [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(hc_sr_next_settings), _vp, _vp, C.POINTER(hc_sr_next_counts)]
+# hc_fno1_from_graph (include/hcsr.h): FNO=1 from the graph and the tables the context holds
+FNO1_TABLES_CALLER, FNO1_TABLES_KEPT = 0, 1
+
+
+class hc_fno1_resident_input(C.Structure):
+    _fields_ = [("tables", C.c_uint32), ("flags", C.c_uint32), ("nodes", C.c_void_p), ("n_nodes", C.c_uint64), ("srs", C.c_void_p), ("n_srs", C.c_uint64),
+                ("clique_off", C.c_void_p), ("clique_nodes", C.c_void_p), ("subread_off", C.c_void_p), ("subreads", C.c_void_p),
+                ("nonedges", C.c_void_p), ("n_nonedges", C.c_uint64), ("new_read_count", C.c_uint64), ("edge_threshold", C.c_double),
+                ("max_induced_pairs", C.c_uint64)]
+
+
+class hc_fno1_resident_counts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_bytes", "copied", "u2sr", "v2sr", "sr2sr", "n_graph_edges", "n_branching", "n_nonedges_kept",
+                                          "n_induced_pairs", "n_induced", "n_items")] + [("ms_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _sig = {
     "hc_sr_keep_device": (C.c_int, [_vp, C.c_int]),
     "hc_sr_set_next_reads": (C.c_int, [_vp] + _sr_next_tail),
@@ -263,6 +282,7 @@ _sig = {
     "hc_textblock_create": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
     "hc_textblock_buffer": (_vp, [_vp]),
     "hc_textblock_submit": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "hc_textblock_submit_lines": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
     "hc_textblock_submit_from": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64]),
     "hc_linechain_create": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
     "hc_linechain_destroy": (C.c_int, [_vp]),
@@ -310,6 +330,11 @@ _sig = {
     "hc_dev_exclusive_sum": (C.c_int, [C.c_uint32, _vp, _vp, C.c_uint64]),
     "hc_dev_select_flagged": (C.c_int, [_vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "hc_dev_unique_u64": (C.c_int, [_vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "hc_fno1_from_graph": (C.c_int, [_vp, C.POINTER(hc_fno1_resident_input), C.POINTER(hc_fno1_resident_counts)]),
+    "hc_fno1_text_fetch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "hc_fno1_edges_fetch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "hc_fno1_lines_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "hc_fno1_section_ms": (C.c_int, [_vp, C.POINTER(C.c_double * 4)]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

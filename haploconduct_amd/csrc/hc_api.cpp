@@ -161,6 +161,7 @@ static void free_store(hc_ctx* c) {
     c->loc_reads = 0;
     c->srn.prev_clear();  // (hc_sr_fastq_write_text: the raw arrays go or are replaced with the store)
     c->sr_orig.fno3.drop();  // (hc_fno3_from_originals: its text and table describe the reads of this store)
+    c->fno1.drop();          // (hc_fno1_from_graph: its lines name the reads of the store that follows this one)
     c->sr_fastq.drop();
     c->br.drop();  // (hc_br_evidence's tables were made from the old store)
     c->fastq.valid = false;  // (hc_fastq_fetch: the arrays described the old store)
@@ -857,6 +858,7 @@ int hc_reset(hc_ctx* c, const hc_settings* settings) {
     c->reorder_mode = HC_REORDER_AUTO;
     c->graph.valid = false;
     c->graph.n_appended = 0;
+    c->fno1.drop(), c->sr_mn.tables_drop();  // (hc_fno1_from_graph: the kept tables and what the fetches hand out)
     c->br.orig_valid = false;  // (hc_br_set_original_reads: until replaced or hc_reset)
     c->br.n_orig = 0;
     apply_settings(c, settings);

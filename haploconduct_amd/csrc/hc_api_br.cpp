@@ -123,7 +123,7 @@ int hc_br_evidence(hc_ctx* c, const uint32_t* vertex_read, const uint8_t* vertex
     double ms_device = 0;
     // sortAdjOut's side effect (:48): the records in target order, by hc_graph_remove_branches' step (timed with the rest: its host step
     // for lists that repeat a target lies between the two events too)
-    c->graph_text.drop();
+    c->graph_text.drop(), c->fno1.drop();
     if (E) {
         HC_HIP(hipEventRecord(c->ev0, s));
         const uint64_t E1 = E;

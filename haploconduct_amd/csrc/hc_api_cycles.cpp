@@ -157,7 +157,7 @@ int hc_graph_sort_edges(hc_ctx* c, const uint32_t* len_by_read, uint64_t n_reads
             HC_HIP(hipStreamSynchronize(s));
         }
     }
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     out.E = (uint32_t)E;
     hc::graph_clean_commit(c, out);
     g.sorted_at = g.edits;

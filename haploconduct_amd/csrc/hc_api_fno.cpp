@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/hcedge.h"
+#include "hc_fno1_resident.h"
 #include "hc_fno_device.h"
 #include "hc_hostcopy.h"
 #include "hc_overlap_finder.h"
@@ -24,9 +25,9 @@
 namespace hc {
 namespace {
 
-struct DeviceBuffers {  // freed on every way out
+struct DeviceBuffers final : FnoAlloc {  // hc_fno1_run's and hc_fno3_run's own blocks: freed on every way out
     std::vector<hc_scratch> all;
-    void release(void* p) {  // early, for buffers that are spent
+    void give_back(const void* p) override {  // early, for buffers that are spent
         if (!p) return;
         for (hc_scratch& q : all)
             if (q.p == p) {
@@ -34,13 +35,12 @@ struct DeviceBuffers {  // freed on every way out
                 return;
             }
     }
-    template <typename T>
-    T* get(uint64_t count) {
+    void* take(size_t bytes) override {
         hc_scratch b;
-        const hipError_t e = b.alloc(std::max<uint64_t>(count, 1) * sizeof(T));
+        const hipError_t e = b.alloc(bytes);
         if (e != hipSuccess) throw FatalError{HC_ERR_NOMEM, std::string("find-next-overlaps on the device: hipMalloc: ") + hipGetErrorString(e)};
         all.push_back(std::move(b));
-        return all.back().as<T>();
+        return all.back().p;
     }
 };
 void hip_check(hipError_t e, const char* what) {
@@ -65,10 +65,9 @@ bool fno_device_wanted(uint64_t n_items) {
 namespace {
 
 // the second half from items that already sit on the device: computeOverlapData, the four stable sorts, unique, scan, text
-bool lines_from_device_items(DeviceBuffers& d, const FnoItem* d_items, uint64_t n, bool no_inclusions, const std::function<char*(uint64_t)>& text_of,
-                             uint64_t counters[5], double* seconds, std::chrono::steady_clock::time_point t0) {
+bool lines_from_device_items(FnoAlloc& d, hipStream_t st, const FnoItem* d_items, uint64_t n, bool no_inclusions, FnoTextSink& sink, uint64_t counters[5],
+                             double* seconds, std::chrono::steady_clock::time_point t0) {
     auto now = [] { return std::chrono::steady_clock::now(); };
-    hipStream_t st = nullptr;  // the default stream of the calling thread's device
     FnoRec* d_rec = d.get<FnoRec>(n);
     uint64_t* d_k[4];
     for (auto& k : d_k) k = d.get<uint64_t>(n);
@@ -104,13 +103,31 @@ bool lines_from_device_items(DeviceBuffers& d, const FnoItem* d_items, uint64_t 
     hip_check(hipMemcpyAsync(h_counters, d_counters, sizeof h_counters, hipMemcpyDeviceToHost, st), "counters");
     hip_check(hipMemcpyAsync(&total_bytes, d_kb + n, 8, hipMemcpyDeviceToHost, st), "size of the text");
     hip_check(hipStreamSynchronize(st), "synchronize");
-    if (h_counters[4]) return false;
+    if (h_counters[4]) {
+        sink.left_status = h_counters[4];
+        return false;
+    }
     const auto t1 = now();
     for (auto& k : d_k) d.release(k);  // the keys are spent: room for the text
-    char* d_text = d.get<char>(total_bytes);
+    char* d_text = sink.text_device ? sink.text_device(total_bytes) : d.get<char>(total_bytes);
     hip_check(fno_format(d_rec, perm, d_ka, d_kb, n, d_text, st), "format");
-    char* h_text = text_of(total_bytes);
-    if (total_bytes) hip_check(copy_to_pageable_host(h_text, d_text, total_bytes), "copy of the text");
+    if (sink.lines_device) {  // the same lines as records, beside the text (hc_fno1_resident_kernels.hip)
+        const uint64_t n_lines = h_counters[5];
+        hc_line_rec* d_lines = sink.lines_device(n_lines);
+        uint32_t* d_rank = d.get<uint32_t>(n + 1);
+        const size_t rank_bytes = prims::scan_temp_bytes(n + 1, sizeof(uint32_t));
+        void* d_rank_tmp = d.get<char>(rank_bytes);
+        hip_check(fno1r::line_heads(d_ka, n, d_rank, st), "line heads");
+        hip_check(prims::exclusive_sum(d_rank_tmp, rank_bytes, d_rank, d_rank, n + 1, st), "scan");
+        hip_check(fno1r::line_records(d_rec, perm, d_ka, d_rank, n, d_lines, n_lines, st), "line records");
+    }
+    if (sink.text_host) {
+        char* h_text = sink.text_host(total_bytes);
+        if (total_bytes) hip_check(copy_to_pageable_host(h_text, d_text, total_bytes), "copy of the text");
+    } else {
+        hip_check(hipStreamSynchronize(st), "synchronize");
+    }
+    sink.n_bytes = total_bytes;
     for (int k = 0; k < 4; k++) counters[k] = h_counters[k];
     counters[4] = h_counters[5];
     if (seconds) {
@@ -128,7 +145,9 @@ bool fno_lines_on_device(const FnoItem* items, uint64_t n, bool no_inclusions, c
     DeviceBuffers d;
     FnoItem* d_items = d.get<FnoItem>(n);
     hip_check(hipMemcpyAsync(d_items, items, n * sizeof(FnoItem), hipMemcpyHostToDevice, nullptr), "copy of the combinations");
-    return lines_from_device_items(d, d_items, n, no_inclusions, text_of, counters, seconds, t0);
+    FnoTextSink sink;
+    sink.text_host = text_of;
+    return lines_from_device_items(d, nullptr, d_items, n, no_inclusions, sink, counters, seconds, t0);
 }
 
 // FNO=1 whole: the walk (updateOverlap's case analysis, the first combination per pair of new ids), the look-ups, then the second
@@ -207,42 +226,67 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
     w.n_edges = E;
     w.srs = upload((hc_fno_read*)nullptr, h.srs, h.n_srs, "copy of the super-reads");
     w.n_srs = h.n_srs;
+    FnoWalkTables t{};
+    t.clique_total = h.n_srs ? h.clique_off[h.n_srs] : 0;
+    if (t.clique_total >= 0x7FFFFFF0ull) return false;
+    t.clique_nodes = upload((uint64_t*)nullptr, h.clique_nodes, t.clique_total, "copy of the cliques");
+    t.clique_off = upload((uint64_t*)nullptr, h.clique_off, h.n_srs + 1, "copy of the cliques");
+    w.subread_off = upload((uint64_t*)nullptr, h.subread_off, h.n_srs + 1, "copy of the subread maps");
+    w.subreads = upload((hc_fno_subread*)nullptr, h.subreads, h.n_srs ? h.subread_off[h.n_srs] : 0, "copy of the subread maps");
+    w.new_read_count = h.new_read_count;
+    w.id_bits = id_bits;
+    w.resolve_orientations = h.resolve_orientations ? 1u : 0u;
+    FnoTextSink sink;
+    sink.text_host = text_of;
+    const bool ok = fno1_walk_from_device(d, st, w, t, h.no_inclusions, d_status, sink, counters, seconds, t0);
+    if (n_items_out && sink.n_items) *n_items_out = sink.n_items;  // (written once the items are built, as before the split)
+    return ok;
+}
+
+// The walk from device pointers: w holds everything but nodes_to_SR (built here from the cliques), its edges in walk order, its subread
+// maps sorted by node.  The launch sequence of hc_fno1_run and of hc_fno1_from_graph from fno_clique_pairs onwards; d_status: kFnoCounters
+// zeroed words.  false: sink.left says why.
+bool fno1_walk_from_device(FnoAlloc& d, hipStream_t st, FnoWalkInput w, const FnoWalkTables& t, bool no_inclusions, unsigned long long* d_status,
+                           FnoTextSink& sink, uint64_t counters[5], double* seconds, std::chrono::steady_clock::time_point t0) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const bool debug = env::given(env::Knob::FNO_DEBUG);
+    auto left = [&](const char* where, unsigned long long status, int why = kFnoLeftStatus) {  // why the host form takes over (HC_FNO_DEBUG)
+        if (debug) fprintf(stderr, "[hc fno] the device route ends at %s, status %llu\n", where, status);
+        sink.left = why;
+        sink.left_status = status;
+        return false;
+    };
+    unsigned long long h_status[kFnoCounters];
+    const uint64_t E = w.n_edges;
     {  // nodes_to_SR: (vertex, super-read) per clique member, a stable sort by vertex, the offsets
-        const uint64_t total = h.n_srs ? h.clique_off[h.n_srs] : 0;
-        if (total >= 0x7FFFFFF0ull) return false;
-        const uint64_t* d_cn = upload((uint64_t*)nullptr, h.clique_nodes, total, "copy of the cliques");
-        const uint64_t* d_co = upload((uint64_t*)nullptr, h.clique_off, h.n_srs + 1, "copy of the cliques");
+        const uint64_t total = t.clique_total;
+        const uint64_t *d_cn = t.clique_nodes, *d_co = t.clique_off;
         uint64_t *d_key = d.get<uint64_t>(total), *d_key_sorted = d.get<uint64_t>(total);
         uint32_t *d_sr = d.get<uint32_t>(total), *d_n2s = d.get<uint32_t>(total);
-        uint64_t* d_n2s_off = d.get<uint64_t>(h.n_nodes + 1);
-        hip_check(fno_clique_pairs(d_cn, d_co, h.n_srs, total, h.n_nodes, d_key, d_sr, d_status, st), "nodes_to_SR");
+        uint64_t* d_n2s_off = d.get<uint64_t>(w.n_nodes + 1);
+        hip_check(fno_clique_pairs(d_cn, d_co, w.n_srs, total, w.n_nodes, d_key, d_sr, d_status, st), "nodes_to_SR");
         if (total) {
             size_t sort_bytes = 0;
             hip_check(sort_pairs_u64_u32(nullptr, sort_bytes, d_key, d_key_sorted, d_sr, d_n2s, (uint32_t)total, 64, st), "sort size");
             void* d_tmp = d.get<char>(sort_bytes);
             uint32_t node_bits = 1;
-            while (node_bits < 64 && (h.n_nodes - 1) >> node_bits) node_bits++;
+            while (node_bits < 64 && (w.n_nodes - 1) >> node_bits) node_bits++;
             hip_check(sort_pairs_u64_u32(d_tmp, sort_bytes, d_key, d_key_sorted, d_sr, d_n2s, (uint32_t)total, (int)node_bits, st), "sort");
             hip_check(hipMemcpyAsync(h_status, d_status, sizeof h_status, hipMemcpyDeviceToHost, st), "status");
             hip_check(hipStreamSynchronize(st), "synchronize");
             if (h_status[4]) return left("nodes_to_SR", h_status[4]);  // a clique names a vertex the graph does not have
             d.release(d_tmp);
         }
-        hip_check(fno_offsets(d_key_sorted, total, h.n_nodes, d_n2s_off, st), "nodes_to_SR offsets");
+        hip_check(fno_offsets(d_key_sorted, total, w.n_nodes, d_n2s_off, st), "nodes_to_SR offsets");
         hip_check(hipStreamSynchronize(st), "synchronize");
-        d.release((void*)d_cn);
-        d.release((void*)d_co);
+        d.release(d_cn);
+        d.release(d_co);
         d.release(d_key);
         d.release(d_key_sorted);
         d.release(d_sr);
         w.n2s = d_n2s;
         w.n2s_off = d_n2s_off;
     }
-    w.subread_off = upload((uint64_t*)nullptr, h.subread_off, h.n_srs + 1, "copy of the subread maps");
-    w.subreads = upload((hc_fno_subread*)nullptr, h.subreads, h.n_srs ? h.subread_off[h.n_srs] : 0, "copy of the subread maps");
-    w.new_read_count = h.new_read_count;
-    w.id_bits = id_bits;
-    w.resolve_orientations = h.resolve_orientations ? 1u : 0u;
 
     uint64_t *d_off_comb = d.get<uint64_t>(E + 1), *d_off_direct = d.get<uint64_t>(E + 1);
     hip_check(fno_walk_count(w, d_off_comb, d_off_direct, d_status, st), "count");
@@ -260,7 +304,8 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
     hip_check(hipMemcpyAsync(&n_direct, d_off_direct + E, 8, hipMemcpyDeviceToHost, st), "count of the copied edges");
     hip_check(hipMemcpyAsync(h_status, d_status, sizeof h_status, hipMemcpyDeviceToHost, st), "status");
     hip_check(hipStreamSynchronize(st), "synchronize");
-    if (h_status[4] || n_comb >= 0x7FFFFFF0ull || n_direct + n_comb >= 0x7FFFFFF0ull) return left("the count of the combinations", h_status[4]);
+    if (h_status[4] || n_comb >= 0x7FFFFFF0ull || n_direct + n_comb >= 0x7FFFFFF0ull)
+        return left("the count of the combinations", h_status[4], h_status[4] ? kFnoLeftStatus : kFnoLeftSize);
 
     uint32_t* d_val_sorted = nullptr;
     uint32_t* d_head_pos = nullptr;
@@ -275,7 +320,7 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
         const size_t sel_bytes = prims::select_temp_bytes(n_comb);
         void* d_tmp = d.get<char>(std::max(sort_bytes, sel_bytes));
         size_t b = sort_bytes;
-        hip_check(sort_pairs_u64_u32(d_tmp, b, d_key, d_key_sorted, d_iota, d_val_sorted, (uint32_t)n_comb, (int)(2 * id_bits), st), "sort");
+        hip_check(sort_pairs_u64_u32(d_tmp, b, d_key, d_key_sorted, d_iota, d_val_sorted, (uint32_t)n_comb, (int)(2 * w.id_bits), st), "sort");
         uint8_t* d_flag = d.get<uint8_t>(n_comb);
         hip_check(fno_walk_heads(d_key_sorted, n_comb, d_flag, st), "heads");
         d_head_pos = d.get<uint32_t>(n_comb);
@@ -291,7 +336,7 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
         d.release(d_tmp);
     }
     const uint64_t n_items = n_direct + n_heads;
-    if (n_items == 0) return left("no combination kept", 0);  // (nothing to write: the host form says so in its own way)
+    if (n_items == 0) return left("no combination kept", 0, kFnoLeftEmpty);  // (nothing to write: the host form says so in its own way)
     uint32_t* d_direct_edge = d.get<uint32_t>(n_direct);
     hip_check(fno_walk_direct(d_off_direct, E, d_direct_edge, st), "copied edges");
     FnoItem* d_items = d.get<FnoItem>(n_items);
@@ -300,17 +345,17 @@ bool fno1_walk_on_device(const FnoWalkHost& h, const std::function<char*(uint64_
     hip_check(hipStreamSynchronize(st), "synchronize");
     if (h_status[4]) return left("the look-ups", h_status[4]);
     // the walk's inputs are spent
-    d.release((void*)w.edges);
+    d.release(w.edges);
     d.release(d_off_comb);
     d.release(d_off_direct);
     d.release(d_val_sorted);
     d.release(d_head_pos);
     d.release(d_direct_edge);
-    if (n_items_out) *n_items_out = n_items;
+    sink.n_items = n_items;
     const auto t1 = now();
     double sec2[2] = {0, 0};
-    const bool ok = lines_from_device_items(d, d_items, n_items, h.no_inclusions, text_of, counters, sec2, t1);
-    if (!ok) left("computeOverlapData", 0);
+    const bool ok = lines_from_device_items(d, st, d_items, n_items, no_inclusions, sink, counters, sec2, t1);
+    if (!ok) left("computeOverlapData", sink.left_status);
     if (seconds) {
         seconds[0] = std::chrono::duration<double>(t1 - t0).count();
         seconds[1] = sec2[0];

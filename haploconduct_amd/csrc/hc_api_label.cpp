@@ -85,7 +85,7 @@ int hc_graph_label_vertices(hc_ctx* c, const hc_label_settings* st, hc_label_cou
             return HC_OK;
         }
         Q.drop();
-        c->graph_text.drop(), c->cliques.drop();
+        c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
         HC_HIP(lb::components(in, w, s));
         HC_HIP(read_counters());
         counts->n_components = h[lb::kComponents];

@@ -33,6 +33,7 @@ int bits_for(uint64_t n) {  // bits that hold every value below n
 
 extern "C" int hc_sr_clique_next(hc_ctx* c, const hc_sr_clique_next_input* in, const hc_sr_clique_next_settings* st, hc_sr_clique_next_output* out) {
     if (!c || !in || !st || !out) return fail(HC_ERR_ARG, "null argument");
+    c->sr_mn.tables_drop();  // (hc_fno1_from_graph: cleared at the start, whatever this call returns, the tables an earlier one kept are no longer the iteration's)
     const uint64_t nc = in->n_cliques, nv = in->n_vertices, n_slots = nc + nv;
     if (nc >= (1ull << 31) || nv >= (1ull << 31) || n_slots >= (1ull << 31)) return fail(HC_ERR_ARG, "n_cliques + n_vertices is 2^31 or more");
     if ((nc && (!in->clique_off || !in->clique_status || !in->first_layout || !out->clique_kind || !out->clique_new_id || !out->overlap_pos ||
@@ -301,5 +302,6 @@ extern "C" int hc_sr_clique_next(hc_ctx* c, const hc_sr_clique_next_input* in, c
     // the store, by hc_sr_set_next_reads' own tail
     if ((rc = hc::sr_next_store(c, n_kept, 0, (uint32_t)n_kept, (uint32_t)cn.n_seq, cn.n_bytes, cn))) return rc;
     out->counts = cn;  // (counts.ms_device: the gather and the histograms; ms_device: this section's own kernels)
+    W.tables_valid = true, W.tables_vertices = nv, W.tables_srs = n_srs, W.tables_new_read_count = n_kept;
     return HC_OK;
 }

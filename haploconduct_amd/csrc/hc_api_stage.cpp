@@ -174,7 +174,7 @@ int hc_graph_resolve(hc_ctx* c, const hc_admit_rec* admitted, uint64_t n, uint64
     g.valid = false;
     g.have_groups = false;
     g.n_branching = g.n_tip_reads = 0;
-    c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
     g.sorted_at = ~0ull, c->cycles.drop();  // (and hc_graph_sort_edges' stamp, hc_graph_remove_cycles' pairs)
     const uint32_t m = (uint32_t)n, V = (uint32_t)n_vertices;
@@ -325,7 +325,7 @@ int hc_graph_load(hc_ctx* c, const hc_edge_rec* edges, const uint64_t* out_off, 
     g.valid = false;
     g.have_groups = false;
     g.n_branching = g.n_tip_reads = 0;
-    c->graph_text.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop(), c->label.drop();  // (hc_graph_write_text's text was the old graph's)
     c->br.drop();          // (and hc_br_evidence's tables)
     g.sorted_at = ~0ull, c->cycles.drop();  // (and hc_graph_sort_edges' stamp, hc_graph_remove_cycles' pairs)
     int rc;
@@ -386,7 +386,7 @@ static void clean_commit(hc_ctx::Graph& g, const hc::trans::Graph& out) {
 int hc_graph_remove_inclusions(hc_ctx* c, hc_clean_counts* counts) {
     if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_inclusions: null argument");
     memset(counts, 0, sizeof *counts);
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     hc_ctx::Graph& g = c->graph;
     if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_inclusions: no graph on the device");
     if (g.n_tied) return fail(HC_ERR_STATE, "hc_graph_remove_inclusions: the device holds out-lists whose order only the host knows (hc_graph_resolve's tied lists): hc_graph_load the host's lists first");
@@ -429,7 +429,7 @@ int hc_graph_remove_inclusions(hc_ctx* c, hc_clean_counts* counts) {
 int hc_graph_remove_transitive(hc_ctx* c, uint32_t remove_trans, uint32_t branch_reduction, hc_clean_counts* counts) {
     if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_transitive: null argument");
     memset(counts, 0, sizeof *counts);
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     hc_ctx::Graph& g = c->graph;
     if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_transitive: no graph on the device");
     if (g.n_tied) return fail(HC_ERR_STATE, "hc_graph_remove_transitive: the device holds out-lists whose order only the host knows (hc_graph_resolve's tied lists): hc_graph_load the host's lists first");
@@ -502,7 +502,7 @@ void hc::graph_clean_commit(hc_ctx* c, const hc::trans::Graph& out) { clean_comm
 int hc::graph_remove_records(hc_ctx* c, const char* who, const uint32_t* d_rec, const uint32_t* d_in_pos, uint64_t n, const hc_edge_rec* d_missing,
                              uint64_t n_missing) {
     hc_ctx::Graph& g = c->graph;
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     int rc = grow_keeping(g.branching, g.n_branching * sizeof(hc_edge_rec), (g.n_branching + n_missing + n + 1) * sizeof(hc_edge_rec), c->stream);
     if (rc) return rc;
     hc::trans::Graph in, out;
@@ -530,7 +530,7 @@ extern "C" {
 int hc_graph_remove_tips(hc_ctx* c, uint32_t max_tip_len, const hc_read_geom* reads, uint64_t n_reads, hc_tip_counts* counts) {
     if (!c || !counts || (n_reads && !reads)) return fail(HC_ERR_ARG, "hc_graph_remove_tips: null argument");
     memset(counts, 0, sizeof *counts);
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     if (n_reads >= (1ull << 31)) return fail(HC_ERR_ARG, "hc_graph_remove_tips: more than 2^31-1 reads");
     hc_ctx::Graph& g = c->graph;
     if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_tips: no graph on the device");
@@ -568,7 +568,7 @@ int hc_graph_remove_tips(hc_ctx* c, uint32_t max_tip_len, const hc_read_geom* re
 int hc_graph_remove_branches(hc_ctx* c, hc_branch_counts* counts) {
     if (!c || !counts) return fail(HC_ERR_ARG, "hc_graph_remove_branches: null argument");
     memset(counts, 0, sizeof *counts);
-    c->graph_text.drop(), c->cliques.drop();
+    c->graph_text.drop(), c->fno1.drop(), c->cliques.drop();
     hc_ctx::Graph& g = c->graph;
     if (!g.valid) return fail(HC_ERR_STATE, "hc_graph_remove_branches: no graph on the device");
     if (g.n_tied) return fail(HC_ERR_STATE, std::string("hc_graph_remove_branches") + kTiedRefusal);

@@ -374,6 +374,11 @@ struct hc_ctx {
         hc_scratch pairs, pair_status, first_layout, layouts, members, lay_status, out_off, sub, v_read, v_fwd, incl, tip_reads;
         hc_scratch entries, status, cnt, bytes, key, rank, overlap_pos, n_clique, visited, rewrite;
         hc_scratch t_kind, t_id, t_v_state, t_nodes, t_srs, t_sr_pair, t_clique_cnt, t_clique_off, t_clique_nodes, t_sub_off, t_sub, t_tips, temp;
+        // hc_fno1_from_graph (HC_FNO1_TABLES_KEPT) reads t_nodes, t_srs, t_clique_off, t_clique_nodes, t_sub_off and t_sub in place: valid from a
+        // successful hc_sr_merge_next / hc_sr_clique_next until the start of the next one (which may reallocate them) or hc_reset
+        bool tables_valid = false;
+        uint64_t tables_vertices = 0, tables_srs = 0, tables_new_read_count = 0;
+        void tables_drop() { tables_valid = false, tables_vertices = tables_srs = tables_new_read_count = 0; }
     } sr_mn;
     // hc_sr_clique_next (hc_api_sr_clique_next.cpp): grow-only scratch — the call's inputs, the host's verdicts (bad, own); the blocks of
     // hc_sr_clique_next.h: Work by name; the row and subread sizes before their sums; the sorts' and scans' workspace.  The slots, the
@@ -409,6 +414,21 @@ struct hc_ctx {
         void text_replaced() { text_valid = false, n_text = 0; }
         void replaced() { text_replaced(), fno3.drop(); }
     } sr_orig;
+    // hc_fno1_from_graph (hc_api_fno1_resident.cpp): grow-only scratch — the call's inputs (non-edges, caller tables), the flags and
+    // selections of checkEdge, the sorted subread maps, and `pool`, the blocks the shared walk (hc_api_fno.cpp: fno1_walk_from_device) takes
+    // in the order it asks for them — and what the fetches hand out: the walk's edge list (n_seg: its four segments), the text and the
+    // lines, built in next_* and traded at the end, kept until the next call or until the graph or the store is replaced (drop())
+    struct Fno1 {
+        hc_scratch nonedges, nodes, srs, clique_off, clique_nodes, sub_off, sub, sub_sorted, sub_key_in, sub_key, sub_val_in, sub_val;
+        hc_scratch pair_off, keep, is_long, long_idx, sel_idx, counts, status, temp;
+        std::vector<hc_scratch> pool;
+        std::vector<uint8_t> pool_busy;  // per block of `pool`, during a call: handed out and not given back yet
+        hc_scratch edges, next_edges, text, next_text, lines, next_lines;
+        uint64_t n_seg[4] = {0, 0, 0, 0}, n_text = 0, n_lines = 0;
+        double ms_section[4] = {0, 0, 0, 0};  // hc_fno1_section_ms: the last call's event pairs
+        bool valid = false;
+        void drop() { valid = false, n_text = n_lines = 0, n_seg[0] = n_seg[1] = n_seg[2] = n_seg[3] = 0; }
+    } fno1;
     // hc_br_* (hc_api_br.cpp): the original reads (orig_bases, orig_off: n_orig + 1 offsets) until replaced or hc_reset; the call's vertex
     // tables; grow-only work blocks, each carved into the arrays of hc_br.h: Work by the phase that sizes it (work_v: per vertex, edge and
     // record; work_b: per branch, neighbour and pair; work_d: per diff slot in use; work_e: per item key); the prims' workspace; and the

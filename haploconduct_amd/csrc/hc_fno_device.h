@@ -8,7 +8,9 @@
 #define HC_FNO_DEVICE_H_
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
+#include <functional>
 
 #include "../../include/hcfno.h"
 #include "hc_fno_items.h"
@@ -65,6 +67,37 @@ hipError_t fno_walk_heads(const uint64_t* key_sorted, uint64_t n_comb, uint8_t* 
 hipError_t fno_walk_direct(const uint64_t* off_direct, uint64_t n_edges, uint32_t* direct_edge, hipStream_t s);
 hipError_t fno_walk_items(const FnoWalkInput& w, const uint64_t* off_comb, const uint32_t* direct_edge, uint64_t n_direct, const uint32_t* val_sorted,
                           const uint32_t* head_pos, uint64_t n_heads, FnoItem* items, unsigned long long* counters, hipStream_t s);
+
+// ---- the walk from device pointers (hc_api_fno.cpp), shared by hc_fno1_run and hc_fno1_from_graph -----------------------------------
+// Where the device form's blocks come from: hc_fno1_run's own (freed on the way out) or a context's grow-only pool (hc_ctx.h: Fno1).
+struct FnoAlloc {
+    virtual void* take(size_t bytes) = 0;          // throws FatalError{HC_ERR_NOMEM}
+    virtual void give_back(const void* p) = 0;     // a block that is spent early; one the allocator does not own is left alone
+    template <typename T>
+    T* get(uint64_t count) {
+        return (T*)take((count ? count : 1) * sizeof(T));
+    }
+    void release(const void* p) { give_back(p); }
+
+protected:
+    ~FnoAlloc() = default;
+};
+enum { kFnoLeftNot = 0, kFnoLeftStatus = 1, kFnoLeftSize = 2, kFnoLeftEmpty = 3 };
+struct FnoTextSink {
+    std::function<char*(uint64_t)> text_host;             // where the host wants the text; empty: it stays on the device
+    std::function<char*(uint64_t)> text_device;           // where the text goes on the device; empty: a block of the allocator's
+    std::function<hc_line_rec*(uint64_t)> lines_device;   // where the lines go as records; empty: none are written
+    uint64_t n_items = 0, n_bytes = 0;
+    int left = kFnoLeftNot;  // why the call returned false: status bits, a count beyond 2^31 - 16, or nothing to write
+    unsigned long long left_status = 0;
+};
+struct FnoWalkTables {  // the cliques nodes_to_SR is made of (:893-906), on the device
+    const uint64_t* clique_off;
+    const uint64_t* clique_nodes;
+    uint64_t clique_total;
+};
+bool fno1_walk_from_device(FnoAlloc& d, hipStream_t st, FnoWalkInput w, const FnoWalkTables& t, bool no_inclusions, unsigned long long* d_status,
+                           FnoTextSink& sink, uint64_t counters[5], double* seconds, std::chrono::steady_clock::time_point t0);
 
 // FNO=3: deduceOverlap per candidate pair (in walk order); len[i] = bytes of its line (0: no line), len[n] = 0; counters[4] status
 // bits, counters[5] lines.  Then the text at off[i] (the exclusive scan of len).

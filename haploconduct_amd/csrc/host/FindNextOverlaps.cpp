@@ -29,6 +29,7 @@
 
 #include "../../../include/hcfno.h"
 #include "../../../include/hcsr.h"
+#include "../hc_fno1_induced.h"
 #include "../hc_fno3_walk.h"
 #include "../hc_fno_items.h"
 #include "DefaultInit.h"
@@ -283,6 +284,18 @@ public:
                     std::chrono::duration<double>(t3 - t2).count());
     }
 
+    // the edges updateOverlap is called on, in the reference's order (work_[0..3]): hc_host_fno1_walk_edges.  false: `out` is too small.
+    bool walk_edges(uint64_t n_seg[4], hc_fno_edge* out, uint64_t cap) {
+        threads_ = thread_count(in_.n_threads);
+        check_input();
+        collect_work();
+        for (int k = 0; k < 4; ++k) n_seg[k] = work_[k].n;
+        if (n_work_ && (!out || cap < n_work_)) return false;
+        for (uint64_t k = 0, at = 0; k < 4; at += work_[k].n, ++k)
+            if (work_[k].n) memcpy(out + at, work_[k].p, work_[k].n * sizeof(hc_fno_edge));
+        return true;
+    }
+
 private:
     struct Combo {  // one (edge, super-read, super-read) combination that competes for its pair of ids
         uint64_t lo, hi;  // the unordered pair of new ids
@@ -452,39 +465,16 @@ private:
             const unsigned l = (unsigned)(in_.inclusion_off[g + 1] - in_.inclusion_off[g]);
             for (unsigned i = 0; i < l; ++i)
                 for (unsigned j = i + 1; j < l; ++j) {
-                    const hc_fno_edge &e1 = grp[i], &e2 = grp[j];
-                    const hc_fno_edge *head, *tail;  // head->v1 = u, tail->v2 = v
-                    if (e1.v1 == e2.v1) continue;
-                    if (e1.v1 == e2.v2) {
-                        head = &e2;
-                        tail = &e1;
-                    } else if (e1.v2 == e2.v1) {
-                        head = &e1;
-                        tail = &e2;
-                    } else {
-                        FNO_REQUIRE(e1.v2 == e2.v2);
-                        continue;
+                    hc_fno_edge ne;  // the case analysis, the paired-read skip, len and perc: hc_fno1_induced.h, shared with the device
+                    switch (hc::fno1i::induced_edge(grp[i], grp[j], in_.nodes, in_.n_nodes, in_.edge_threshold, &ne)) {
+                        case hc::fno1i::kSkip: continue;
+                        case hc::fno1i::kCandidate: break;
+                        case hc::fno1i::kStopRelation: ref_abort("e1.v2 == e2.v2");
+                        case hc::fno1i::kStopVertex: ref_abort("edge vertex out of range");
+                        case hc::fno1i::kStopZeroLen: ref_abort("std::min(L1, L2) != 0");  // the reference divides by it
+                        case hc::fno1i::kStopThreshold: ref_abort("in_.edge_threshold == 0 || in_.edge_threshold == -1 || in_.edge_threshold > 0");  // Edge ctor, src/Edge.h:46
+                        default: ref_abort("len > 0");  // Edge::set_len
                     }
-                    if (head->v1 >= in_.n_nodes || tail->v2 >= in_.n_nodes) ref_abort("edge vertex out of range");
-                    const hc_fno_read &r1 = in_.nodes[head->v1], &r2 = in_.nodes[tail->v2];
-                    if (r1.paired || r2.paired) continue;
-                    const unsigned L1 = r1.len1, L2 = r2.len1;
-                    const int len = (int)std::min(L1 - (unsigned)head->pos1, L2);
-                    FNO_REQUIRE(std::min(L1, L2) != 0);  // the reference divides by it
-                    const int perc = (int)((unsigned)(100 * len) / std::min(L1, L2));
-                    FNO_REQUIRE(in_.edge_threshold == 0 || in_.edge_threshold == -1 || in_.edge_threshold > 0);  // Edge ctor, src/Edge.h:46
-                    FNO_REQUIRE(len > 0);                                                                        // Edge::set_len
-                    hc_fno_edge ne;
-                    memset(&ne, 0, sizeof ne);
-                    ne.v1 = head->v1;
-                    ne.v2 = tail->v2;
-                    ne.score = in_.edge_threshold;
-                    ne.pos1 = head->pos1;
-                    ne.len1 = len;
-                    ne.perc = perc;
-                    ne.ord = '-';
-                    ne.ori1 = head->ori1;
-                    ne.ori2 = tail->ori2;
                     if (check_edge(ne.v1, ne.v2) == -1) induced_.push_back(ne);
                 }
         }
@@ -1346,6 +1336,17 @@ int hc_fno_compute_overlap_data(const hc_fno_read* sr1, const hc_fno_read* sr2, 
 }
 
 }  // extern "C"
+
+extern "C" int hc_host_fno1_walk_edges(const hc_fno1_input* in, hc_fno_edge* out, uint64_t cap, uint64_t n_seg[4]) {
+    const char* me = "hc_host_fno1_walk_edges";
+    if (!in || !n_seg) return hc::set_last_error(HC_ERR_ARG, std::string(me) + ": null argument");
+    n_seg[0] = n_seg[1] = n_seg[2] = n_seg[3] = 0;
+    if (in->flags & ~HC_FNO_KNOWN_FLAGS) return hc::set_last_error(HC_ERR_ARG, std::string(me) + ": unknown bit in flags");
+    if (in->flags & HC_FNO_ADD_DUPLICATES) return hc::set_last_error(HC_ERR_ARG, std::string(me) + ": HC_FNO_ADD_DUPLICATES is hc_fno1_run's");
+    return guarded_fno(me, [&] {
+        if (!Fno1(*in).walk_edges(n_seg, out, cap)) throw FatalError{HC_ERR_ARG, "the buffer is missing or too small (the sizes are filled)"};
+    });
+}
 
 // ---- FNO=3 from the kept dict: the mirror of hc_fno3_from_originals (include/hcsr.h) ------------------------------------------------------
 namespace hc {

@@ -7,6 +7,7 @@ the oracle (oracle/fno_oracle.cpp) — the structures are plain data, not the or
 """
 import time
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -71,6 +72,7 @@ for _name, (_res, _args) in {
     "hc_fno_output_free": (None, [_vp]),
     "hc_fno_output_on_device": (C.c_int, [_vp]),
     "hc_fno_compute_overlap_data": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp]),
+    "hc_host_fno1_walk_edges": (C.c_int, [C.POINTER(hc_fno1_input), _vp, C.c_uint64, C.POINTER(C.c_uint64 * 4)]),
 }.items():
     _f = getattr(N.lib, _name)
     _f.restype = _res
@@ -248,3 +250,93 @@ def edges_from_graph(recs):
     for f in ("v1", "v2", "score", "pos1", "pos2", "len1", "len2", "perc", "ord", "ori1", "ori2"):
         e[f] = recs[f]
     return e
+
+
+# ---- FNO=1 from the context's graph: hc_fno1_from_graph (include/hcsr.h) -----------------------------------------------------------------
+
+
+@dataclasses.dataclass
+class Fno1Resident:
+    counts: dict  # hc_fno1_resident_counts
+
+
+def host_walk_edges(inp):
+    """hc_host_fno1_walk_edges: the edges updateOverlap is called on, in the reference's order — [adj_out][branching_edges][the stored
+    non-edges that pass :694][the inclusion-induced edges] — for a Fno1Input.  Returns (FNO_EDGE_DTYPE array, the four segment lengths)."""
+    s, seg = inp.struct(), (C.c_uint64 * 4)()
+    rc = N.lib.hc_host_fno1_walk_edges(C.byref(s), None, 0, C.byref(seg))  # count ...
+    n = sum(int(x) for x in seg)
+    if n == 0:
+        N.check(rc, "hc_host_fno1_walk_edges")
+        return np.zeros(0, FNO_EDGE_DTYPE), [int(x) for x in seg]
+    if rc not in (0, -1):
+        N.check(rc, "hc_host_fno1_walk_edges")
+    out = np.zeros(n, FNO_EDGE_DTYPE)
+    N.check(N.lib.hc_host_fno1_walk_edges(C.byref(s), out.ctypes.data, n, C.byref(seg)), "hc_host_fno1_walk_edges")  # ... then fetch
+    return out, [int(x) for x in seg]
+
+
+def input_from_context(scorer, tables, nonedges=None, **kw):
+    """The Fno1Input of the fetch route for the graph an EdgeScorer holds: hc_graph_fetch, hc_graph_fetch_branching_edges and
+    hc_graph_fetch_inclusion_edges, every record rewritten by edges_from_graph.  tables: a merge_next.MergeNext / clique_next.CliqueNext
+    (anything with nodes, srs, clique_off, clique_nodes, subread_off, subreads, new_read_count) or that tuple of seven.  kw: edge_threshold,
+    flags, n_threads as Fno1Input takes them."""
+    g = scorer.graph_fetch()
+    branching = scorer.graph_branching_edges()
+    try:
+        _, goff, grecs = scorer.graph_inclusion_edges()
+    except N.HcError:  # hc_graph_remove_inclusions has not run on this graph: no groups
+        goff, grecs = np.zeros(1, np.uint64), np.zeros(0, g["edges"].dtype)
+    if isinstance(tables, tuple):
+        nodes, srs, clique_off, clique_nodes, subread_off, subreads, new_read_count = tables
+    else:
+        nodes, srs, clique_off, clique_nodes, subread_off, subreads, new_read_count = (
+            tables.nodes, tables.srs, tables.clique_off, tables.clique_nodes, tables.subread_off, tables.subreads, tables.new_read_count)
+    inp = Fno1Input.from_tables(nodes, srs, clique_off, clique_nodes, subread_off, subreads, edges_from_graph(g["edges"]),
+                                branching_edges=edges_from_graph(branching), nonedges=nonedges, new_read_count=int(new_read_count), **kw)
+    inp.inclusion_off, inp.inclusion_edges = _arr(goff, np.uint64), edges_from_graph(grecs)
+    inp.n_inclusion_groups = len(goff) - 1
+    return inp
+
+
+def fno1_from_graph(ctx, tables=None, nonedges=None, edge_threshold=0.97, flags=RESOLVE_ORIENTATIONS, max_induced_pairs=0):
+    """hc_fno1_from_graph on a context (EdgeScorer.fno1_from_graph); the text, the edge list and the lines stay on the device -> Fno1Resident."""
+    inp, keep = N.hc_fno1_resident_input(), []
+    inp.flags, inp.edge_threshold, inp.max_induced_pairs = int(flags), float(edge_threshold), int(max_induced_pairs)
+    if tables is None:
+        inp.tables = N.FNO1_TABLES_KEPT
+    else:
+        if not isinstance(tables, tuple):
+            tables = (tables.nodes, tables.srs, tables.clique_off, tables.clique_nodes, tables.subread_off, tables.subreads, tables.new_read_count)
+        nodes, srs = _arr(tables[0], FNO_READ_DTYPE), _arr(tables[1], FNO_READ_DTYPE)
+        co, cn = _arr(tables[2], np.uint64), _arr(tables[3], np.uint64)
+        so, sub = _arr(tables[4], np.uint64), _arr(tables[5], FNO_SUBREAD_DTYPE)
+        if co.size != len(srs) + 1 or so.size != len(srs) + 1 or int(co[-1]) != cn.size or int(so[-1]) != sub.size:
+            raise ValueError("the offsets do not describe the tables")
+        keep = [nodes, srs, co, cn, so, sub]
+        inp.tables = N.FNO1_TABLES_CALLER
+        inp.nodes, inp.n_nodes, inp.srs, inp.n_srs = _ptr(nodes), len(nodes), _ptr(srs), len(srs)
+        inp.clique_off, inp.clique_nodes, inp.subread_off, inp.subreads = co.ctypes.data, _ptr(cn), so.ctypes.data, _ptr(sub)
+        inp.new_read_count = int(tables[6])
+    if nonedges is not None:
+        ne = _arr(nonedges, FNO_EDGE_DTYPE)
+        keep.append(ne)
+        inp.nonedges, inp.n_nonedges = _ptr(ne), len(ne)
+    cn_ = N.hc_fno1_resident_counts()
+    N.check(N.lib.hc_fno1_from_graph(ctx, C.byref(inp), C.byref(cn_)), "hc_fno1_from_graph")
+    return Fno1Resident(cn_.as_dict())
+
+
+def fno1_text(ctx, first=0, count=None, n_bytes=None):
+    """hc_fno1_text_fetch: bytes [first, first + count) of the kept text (count None: up to n_bytes)."""
+    count = int(n_bytes) - int(first) if count is None else int(count)
+    buf = np.empty(count, np.uint8)
+    N.check(N.lib.hc_fno1_text_fetch(ctx, int(first), count, _ptr(buf)), "hc_fno1_text_fetch")
+    return buf.tobytes()
+
+
+def fno1_edges(ctx, first, count):
+    """hc_fno1_edges_fetch: records [first, first + count) of the walk's edge list (FNO_EDGE_DTYPE)."""
+    buf = np.zeros(int(count), FNO_EDGE_DTYPE)
+    N.check(N.lib.hc_fno1_edges_fetch(ctx, int(first), buf.size, _ptr(buf)), "hc_fno1_edges_fetch")
+    return buf

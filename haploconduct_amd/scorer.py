@@ -244,6 +244,72 @@ class EdgeScorer:
 
         return OR.fno3_from_originals(self._ctx, counts3, original_readcount, walk_rank, max_combos, flags)
 
+    def fno1_from_graph(self, tables=None, nonedges=None, edge_threshold=0.97, flags=1, max_induced_pairs=0):
+        """hc_fno1_from_graph: findNextOverlaps (src/FindNextOverlaps.cpp:890-958) from the graph, the branching edges and the inclusion
+        groups the context holds.  tables: None = the tables the last sr_merge_next / sr_clique_next left on the device; a MergeNext /
+        CliqueNext or the tuple (nodes, srs, clique_off, clique_nodes, subread_off, subreads, new_read_count) = host tables.  nonedges:
+        fno.FNO_EDGE_DTYPE records of nonedge_overlaps.txt.  Returns a fno.Fno1Resident (counts); the text, the edge list and the lines stay
+        on the device: fno1_text, fno1_edges, fno1_lines_device."""
+        from . import fno as F
+
+        self._fno1 = F.fno1_from_graph(self._ctx, tables, nonedges, edge_threshold, flags, max_induced_pairs)
+        return self._fno1
+
+    def fno1_text(self, piece_bytes=None):
+        """hc_fno1_text_fetch: the whole text of the last fno1_from_graph (piece_bytes: fetched in pieces of that many bytes)."""
+        from . import fno as F
+
+        n = int(self._fno1.counts["n_bytes"])
+        step = int(piece_bytes) if piece_bytes else max(n, 1)
+        return b"".join(F.fno1_text(self._ctx, at, min(step, n - at)) for at in range(0, n, step))
+
+    def fno1_edges(self):
+        """hc_fno1_edges_fetch: the edge list the last fno1_from_graph walked and its four segment lengths
+        ([adj_out][branching_edges][stored non-edges kept][inclusion-induced edges])."""
+        from . import fno as F
+
+        c = self._fno1.counts
+        seg = [int(c[k]) for k in ("n_graph_edges", "n_branching", "n_nonedges_kept", "n_induced")]
+        return F.fno1_edges(self._ctx, 0, sum(seg)), seg
+
+    def fno1_lines_device(self):
+        """hc_fno1_lines_device: (device pointer, number) of the last fno1_from_graph's lines as hc_line_rec (records.LINE_DTYPE), what
+        hc_textblock_submit_lines takes; found_lines_fetch copies them out."""
+        p, n = C.c_void_p(), C.c_uint64()
+        N.check(N.lib.hc_fno1_lines_device(self._ctx, C.byref(p), C.byref(n)), "hc_fno1_lines_device")
+        return p.value, int(n.value)
+
+    def fno1_section_ms(self):
+        """hc_fno1_section_ms: the four parts of the last fno1_from_graph's ms_device — [pair counts, conversions + checkEdge + subread sort,
+        segments 3 and 4, the walk with its sorts, text and lines (host waits between its launches included)]."""
+        ms = (C.c_double * 4)()
+        N.check(N.lib.hc_fno1_section_ms(self._ctx, C.byref(ms)), "hc_fno1_section_ms")
+        return [float(x) for x in ms]
+
+    def found_lines_fetch(self, d_lines, n):
+        """hc_found_lines_fetch: n hc_line_rec from device memory (records.LINE_DTYPE)."""
+        from .records import LINE_DTYPE
+
+        out = np.zeros(int(n), dtype=LINE_DTYPE)
+        if n:
+            N.check(N.lib.hc_found_lines_fetch(self._ctx, C.c_void_p(d_lines), int(n), _ptr(out)), "hc_found_lines_fetch")
+        return out
+
+    def score_lines_device(self, d_lines, n_lines, first_line_no=0):
+        """hc_textblock_submit_lines + hc_textblock_wait: parsed lines in device memory through a text block of their own, as score_text
+        takes the text.  Returns the block's dict (the hc_text_result fields, rows / rejected as numpy copies)."""
+        b = C.c_void_p()
+        N.check(N.lib.hc_textblock_create(self._ctx, max(64 * int(n_lines), 4096), C.byref(b)), "hc_textblock_create")
+        try:
+            if int(N.lib.hc_textblock_max_lines(b)) < n_lines:
+                raise ValueError("more lines than a text block takes")
+            N.check(N.lib.hc_textblock_submit_lines(b, C.c_void_p(d_lines), int(n_lines), int(first_line_no), 0), "hc_textblock_submit_lines")
+            r = N.hc_text_result()
+            N.check(N.lib.hc_textblock_wait(b, C.byref(r)), "hc_textblock_wait")
+            return self._text_result(b, r, 0)
+        finally:
+            N.lib.hc_textblock_destroy(b)
+
     def br_set_original_reads(self, bases, seq_off):
         """hc_br_set_original_reads: the sequences of --original_fastq (single-end, one byte per base, n + 1 offsets), kept on the device."""
         from . import branch_evidence as BR

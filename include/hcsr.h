@@ -1370,6 +1370,85 @@ int hc_host_sr_fastq_text(const uint8_t* bases, const uint8_t* quals, const uint
 int hc_host_sr_fastq_tips_text(const uint8_t* bases, const uint8_t* quals, const uint64_t* seq_off, const uint32_t* read_first_seq,
                                uint32_t n_reads, const uint32_t* tip_reads, uint64_t n_tips, char* text, uint64_t cap, uint64_t* n_bytes);
 
+/* ---- FNO=1 from the context's graph: SRBuilder::findNextOverlaps on the device ------------------------------------------------
+ *
+ * Every edge-merge iteration ends with findNextOverlaps (src/FindNextOverlaps.cpp:890-958).  hc_fno1_run (include/hcfno.h) takes host
+ * arrays; hc_fno1_from_graph reads what the context holds where it is: adj_out (the graph's records and offsets), branching_edges
+ * (hc_graph_remove_tips / hc_graph_remove_branches), the inclusion groups (hc_graph_remove_inclusions) and, with HC_FNO1_TABLES_KEPT, the
+ * vertex and super-read tables the last hc_sr_merge_next / hc_sr_clique_next built.  Only the stored non-edges (nonedge_overlaps.txt) and,
+ * with HC_FNO1_TABLES_CALLER, the tables come from the host, one upload each.
+ *
+ * The result is what hc_fno1_run writes for the same facts: the same bytes of overlaps.txt and the same four counters.  adj_out is taken
+ * in the list order the graph has AT THE MOMENT OF THE CALL, vertex by vertex, each list front to back, as the reference walks it at
+ * :612; a caller that wants the lists in sortEdges' order sorts them first (hc_graph_sort_edges).
+ *
+ * The edge list updateOverlap is called on is, in this order,
+ *   1. adj_out vertex by vertex (:612-624),
+ *   2. branching_edges (:627-630),
+ *   3. the stored non-edges that pass :694 — checkEdge(v1, v2, true) > 0 drops a line; left out with HC_FNO_OPTIMIZE (:926),
+ *   4. the inclusion-induced edges (:816-887): per group every pair i < j in (group, i, j) order, the case analysis of :841-865, no
+ *      paired read, len and perc of :870-871, kept where checkEdge(node1, node2, true) == -1 — a record of score 0 IS an edge here.
+ * checkEdge answers with the first match in list order, v's list before w's (src/OverlapGraph.cpp:233-259).
+ * counts gives the four lengths; hc_fno1_edges_fetch returns the list, and hc_host_fno1_walk_edges builds the same list on the host
+ * from an hc_fno1_input, so that the two can be compared array by array.  Feeding the list to hc_fno1_run as plain graph_edges (no
+ * other source) reproduces the text.
+ *
+ * tables = HC_FNO1_TABLES_CALLER: nodes .. subreads are host arrays as in hc_fno1_input (n_nodes must be the graph's vertex count,
+ * the super-reads single-end first: anything else is HC_ERR_ARG).  HC_FNO1_TABLES_KEPT: the tables stay where hc_sr_merge_next /
+ * hc_sr_clique_next built them; the context remembers them from a successful call of either (HC_OK) until the start of the next one or
+ * hc_reset.  In both forms the subread maps are ordered on the device, by one stable radix sort of super-read << 32 | node.
+ *
+ * Statuses.  HC_ERR_ARG: a NULL argument, HC_FNO_ADD_DUPLICATES (the workflows never set it with this route: hc_fno1_run remains the
+ * route for it), a flag bit nobody defined, an unknown `tables`, max_induced_pairs above 2^31 - 16.  HC_ERR_STATE: no valid graph;
+ * HC_FNO1_TABLES_KEPT with no tables, or with tables for another vertex count than the graph's.  HC_ERR_NOT_ON_DEVICE: an input the
+ * device does not decide — something the reference would stop at (an assert, an .at()), an id >= 10^10 or ids that need more than 31
+ * bits, a perc > 999, a count >= 2^31 - 16, more pairs (i, j) than max_induced_pairs; the call then changes nothing, and the caller takes
+ * hc_graph_fetch + hc_fno1_run, which reports what the reference reports.  No line at all is HC_OK with n_lines = 0.
+ *
+ * The text, the edge list and the lines stay in the context until the next hc_fno1_from_graph or the next call that replaces or edits
+ * the graph or replaces the store (hc_graph_load, hc_graph_resolve, the cleaning calls, hc_set_reads, hc_reset); a fetch after that:
+ * HC_ERR_STATE.  hc_fno1_text_fetch / hc_fno1_edges_fetch: count, then fetch; ranges are 64-bit, a range outside is HC_ERR_ARG.
+ * hc_fno1_lines_device: the lines of the text as hc_line_rec in DEVICE memory, in file order — what hc_textblock_submit_lines takes —
+ * with the text's columns: perc2 = 0, pos1 / pos2 as the 32 bits of the int the text prints.
+ *
+ * On the device: a lane per 80-byte record writes one hc_fno_edge with 16-byte loads and stores; a lane per pair (i < j) of a group,
+ * found by bisection in one exclusive sum of l (l - 1) / 2, the pair from the triangular index in integer arithmetic; checkEdge by a
+ * lane for lists of fewer than 64 records, by a wave, 64 records at a time, for longer ones; survivors placed by ordered selection; the
+ * walk, the four stable radix sorts and the text are hc_fno1_run's own launches.  A fixed number of launches, all on the context's
+ * stream, grow-only memory, no atomics on the outputs. */
+#define HC_FNO1_TABLES_CALLER 0u /* the eight table fields below are host arrays, as in hc_fno1_input */
+#define HC_FNO1_TABLES_KEPT   1u /* the tables the last hc_sr_merge_next / hc_sr_clique_next left on the device; the eight fields and new_read_count are ignored */
+typedef struct hc_fno1_resident_input {
+    uint32_t tables, flags;            /* HC_FNO1_TABLES_*; HC_FNO_RESOLVE_ORIENTATIONS | HC_FNO_NO_INCLUSIONS | HC_FNO_OPTIMIZE */
+    const hc_fno_read* nodes;  uint64_t n_nodes;
+    const hc_fno_read* srs;    uint64_t n_srs;
+    const uint64_t* clique_off; const uint64_t* clique_nodes;
+    const uint64_t* subread_off; const hc_fno_subread* subreads;   /* any order inside a super-read */
+    const hc_fno_edge* nonedges; uint64_t n_nonedges;              /* host; nonedge_overlaps.txt as today; may be NULL */
+    uint64_t new_read_count;
+    double edge_threshold;
+    uint64_t max_induced_pairs;        /* 0: 2^31 - 16 */
+} hc_fno1_resident_input; /* 112 bytes */
+typedef struct hc_fno1_resident_counts {
+    uint64_t n_lines, n_bytes, copied, u2sr, v2sr, sr2sr;          /* hc_fno_counters' */
+    uint64_t n_graph_edges, n_branching, n_nonedges_kept, n_induced_pairs, n_induced, n_items;
+    double ms_device;                                              /* events on the context's stream: the sum of hc_fno1_section_ms' four parts */
+} hc_fno1_resident_counts; /* 104 bytes */
+int hc_fno1_from_graph(hc_ctx* ctx, const hc_fno1_resident_input* in, hc_fno1_resident_counts* counts);
+int hc_fno1_text_fetch(hc_ctx* ctx, uint64_t first, uint64_t n_bytes, char* dst);            /* count, then fetch; 64-bit ranges */
+int hc_fno1_edges_fetch(hc_ctx* ctx, uint64_t first, uint64_t n, hc_fno_edge* dst);          /* the walk's edge list, see above */
+int hc_fno1_lines_device(hc_ctx* ctx, const hc_line_rec** d_lines, uint64_t* n_lines);       /* what hc_textblock_submit_lines takes */
+/* The parts of the last call's counts.ms_device, each one event pair on the context's stream: ms[0] the groups' pair counts and their sum;
+ * ms[1] the two conversions, checkEdge for the non-edges and the pairs with their selections, the tables' check and the subread maps'
+ * sort; ms[2] segments 3 and 4; ms[3] the walk, the sorts, the text and the lines.  ms[3] spans hc_fno1_run's own launch sequence, which
+ * waits for the host several times (counts come back between its launches): it is the stream's elapsed time including those gaps, not
+ * the kernels' time alone.  A part the call did not reach is 0. */
+int hc_fno1_section_ms(hc_ctx* ctx, double ms[4]);
+/* The walk's edge list on the host (no device, no context) from an hc_fno1_input, as host/FindNextOverlaps.cpp builds it: n_seg = the
+ * four lengths, always filled; out has room for cap records, and where cap is too small or out is NULL nothing is copied and HC_ERR_ARG is
+ * returned (count, then fetch).  HC_ERR_FORMAT where the reference would stop, HC_ERR_ARG for HC_FNO_ADD_DUPLICATES. */
+int hc_host_fno1_walk_edges(const hc_fno1_input* in, hc_fno_edge* out, uint64_t cap, uint64_t n_seg[4]);  /* host, no device */
+
 #ifdef __cplusplus
 }
 #endif
